@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GFDM blocks/s on MI355X for the BASELINE.json configurations.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
 
 --config (default cfg2 = BASELINE configs[1], the configuration the headline metric is quoted on):
     cfg2  K=64  M=9  L=2 alpha=0.2   step = modulate + MF demodulate of 4096 blocks PER GPU           (weak scaling)
@@ -21,7 +21,16 @@ timed steps bracketed by barrier + synchronize on both sides; the time is the MA
 processed / that time.  (The garbage collector runs BEFORE the warm-up steps and is off until the timed steps are over: a collection between warm-up and timed
 steps left the GPU idle for tens of milliseconds in front of a region that is 0.3 ms long at the driver's --steps 20; GFDM_BENCH_EARLY_GC=0 restores the old order for A/B.)
 
-Beside the headline the JSON line carries
+A plain run does only that: set-up, the W + K steps of the headline loop and one JSON line (metric, value, unit, higher_is_better,
+dtype, ms_per_step = wall time of the K timed steps / K, and the configuration).  --dump-outputs DIR then also writes what the last
+timed step computed, as a caller of the path receives it, to DIR/<name>.npy (float32, last axis = re, im; rank 0's shard under N > 1):
+tx_frames (cfg2's modulator output) and rx_symbols (the receiver's output), at most 64 MB in all -- above that every array keeps an
+equal share of its blocks, chosen by a fixed seed.  The inputs are a function of the arguments alone, so two builds can be compared
+output for output.
+
+--full adds everything below (measured after the headline loop, which stays the first thing timed).  Beside the headline the JSON line
+then carries
+  output_checksum (sum re, sum im, sum |.|^2) of ring slot 0's output, summed over the ranks
   roofline        achieved HBM GB/s of the step's dominant (slowest) kernel = algorithmic bytes per launch (16 B/symbol,
                   24 B/symbol with the per-block equaliser vector) / its duration, measured with HIP events on
                   the launch stream.  Four readings of the duration, all in the object:
@@ -88,6 +97,8 @@ CONFIGS = {
 MODES = {"mod_demod_mf": (False, 0, 16, "mod_demod"), "zf_ic2": (True, 2, 24, "demod_ic"), "mf_ic2": (False, 2, 16, "demod_ic"),
          "zf": (True, 0, 24, "demod")}
 GEN_CHUNK = 8192              # blocks per chunk of the on-device input generation (bounds its temporaries)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together
+DUMP_SEED = 0x6FD2            # --dump-outputs: which blocks a larger output keeps
 
 
 def parse(argv=None):
@@ -119,7 +130,14 @@ def parse(argv=None):
     ap.add_argument("--selftest-launch", action="store_true",
                     help="no GPU, no GFDM compute: run launcher + rendezvous (gloo) + shard plan + synthetic-input checksum all-reduce "
                          "and print them (tests/test_bench_launcher.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else: roofline, sustained and same-slot rates, per-path and "
+                         "large-batch figures, host-buffer paths, single-block host call, CPU baseline, output checksum")
     a = ap.parse_args(argv)
+    if (a.steps is not None and a.steps < 1) or (a.warmup is not None and a.warmup < 0):
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     strong = CONFIGS[a.config]["total"] is not None
     if a.steps is None:
         a.steps = 100 if strong else 200
@@ -749,6 +767,48 @@ def single_block_host(cfg, taps, reps=300):
     return (time.perf_counter() - t0) / reps * 1e6
 
 
+def dump_outputs(arrays, out_dir):
+    """Write every complex (blocks, N) tensor of `arrays` ({name: tensor}) to out_dir/<name>.npy as float32 (blocks, N, 2) = (re, im).  Above
+    DUMP_LIMIT_BYTES in all, each array keeps an equal share of whole blocks, drawn by DUMP_SEED and in ascending order, so that two runs with
+    the same arguments write the same blocks.  Returns {name: {"shape", "blocks_of", "sample_seed"}} (sample_seed None: every block written)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // len(arrays)      # (4 KiB per file left for the .npy header)
+    info = {}
+    for name, t in arrays.items():
+        nb, n = t.shape
+        keep = min(nb, share // (n * 8))
+        if keep < nb:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(nb, keep, replace=False))
+            t = t.index_select(0, torch.as_tensor(rows, device=t.device))
+        a = torch.view_as_real(t).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(a.shape), "blocks_of": nb, "sample_seed": DUMP_SEED if keep < nb else None}
+    return info
+
+
+def finish(result, a, rank, world, local, ndev, use_dist):
+    """rank 0 prints the JSON line (with where the ranks ran); the process group is torn down"""
+    import torch
+    import torch.distributed as dist
+    pr = torch.cuda.get_device_properties(local)
+    rank_devices = gather_ranks({"rank": rank, "device": local, "name": pr.name,
+                                 "pci": "%04x:%02x:%02x.0" % (getattr(pr, "pci_domain_id", 0), getattr(pr, "pci_bus_id", 0), getattr(pr, "pci_device_id", 0))}, world)
+    if rank == 0:
+        try:
+            rccl = ".".join(str(v) for v in torch.cuda.nccl.version())
+        except Exception:                                                 # noqa: BLE001
+            rccl = None
+        result["distributed"] = {"initialized": bool(use_dist), "backend": (a.dist_backend + (" (RCCL)" if a.dist_backend == "nccl" else "")) if use_dist else None,
+                                 "world_size": world, "rccl_version": rccl, "devices_visible": ndev, "rank_devices": rank_devices,
+                                 "collectives": "2 barriers per timed loop + 2 all-reduces per statistic (sharding.reduce_stats); no payload collective",
+                                 "scaling_curve": "none measured so far: no multi-GPU node was available to the builder or the driver in rounds 1-6" if world == 1 else "this line is one point of it"}
+        print(json.dumps(result))
+    if use_dist:
+        dist.destroy_process_group()
+
+
 def main():
     argv = sys.argv[1:]
     # before torch / RCCL are imported, and also when the ranks were started by somebody else's torchrun: dmabuf IPC (RCCL needs it on
@@ -904,6 +964,36 @@ def main():
     total_blocks, _, wall_max = sharding.reduce_stats(B * a.steps, zeros3(), wall, dev)
     rank_wall_ms = gather_ranks(wall * 1e3, world)         # every rank's own time for its K steps: a shortfall at N > 1 can be read off one run
     value = total_blocks / wall_max
+    result = {
+        "metric": cfg["metric"],
+        "value": value, "unit": "blocks/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": wall_max / a.steps * 1e3, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+        # cfg4's cancellation rounds run as v_mfma_f32_16x16x32_f16 on exact f16 decisions and a three-term f16 split of the IC taps (33
+        # significant bits, not narrower than the reference's f32), everything else and every accumulation in f32
+        "dtype": "f32 (IC rounds: f16x3-split MFMA, f32 accumulate)" if ick == 2 else "f32", "data": "synthetic",
+        "config": {"workload": "%s; %d QPSK blocks per step %s, ring of %d buffer sets, independent steps pipelined over %d HIP streams%s"
+                               % (cfg["workload"], total_per_step if scaling == "strong" else B,
+                                  "in total, sharded contiguously over the GPUs" if scaling == "strong" else "per GPU", ns, S,
+                                  "; roofline: rank 0's kernels, cpu_baseline and per-path figures only in the 1-GPU run" if world > 1 else ""),
+                   "name": a.config, "block_size": N, "batch_per_gpu": B, "blocks_per_step_all_gpus": total_per_step, "streams": S,
+                   "sharding": "independent blocks per GPU (gfdm_amd.sharding.ShardedBatch: one handle + stream per device, contiguous shards), no data-path collective"},
+        "msym_per_s": value * N / 1e6,
+        # cfg2: `value` demodulates frames modulated `demod_lag_steps` steps earlier (cold: >= 256 MiB of traffic in between);
+        # value_same_slot (--full) demodulates the frames its own step has just written (may be served by the Infinity Cache)
+        "demod_lag_steps": lag,
+        "kernels": {"modulate": mod.kernel_name(), "demodulate": dem.kernel_name(), "advanced": adv.kernel_name()},
+    }
+    if use_dist:
+        result["rank_wall_ms"] = rank_wall_ms
+        result["rank_hosts_cpus"] = gather_ranks(rank_placement(cpu_slice, launch_cpu), world)
+    if a.dump_outputs and rank == 0:                       # the last timed step: its modulator output and what its receiver returned
+        last = (a.warmup + a.steps - 1) % ns
+        arrays = {"tx_frames": frames[last]} if two_kernel else {}
+        arrays["rx_symbols"] = outs[(last - lag) % ns]
+        result["outputs"] = dump_outputs(arrays, a.dump_outputs)
+    if not a.full:
+        return finish(result, a, rank, world, local, ndev, use_dist)
+
     value_hot = None
     if lag:
         hot = step_fns_on(lambda s: side[s % S].cuda_stream, 0)
@@ -953,33 +1043,14 @@ def main():
     roofline["build_id"] = build_id
     if world > 1:
         roofline["rank"] = 0
-    result = {
-        "metric": cfg["metric"],
-        "value": value, "unit": "blocks/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": wall_max / a.steps * 1e3, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-        # cfg4's cancellation rounds run as v_mfma_f32_16x16x32_f16 on exact f16 decisions and a three-term f16 split of the IC taps (33
-        # significant bits, not narrower than the reference's f32), everything else and every accumulation in f32
-        "dtype": "f32 (IC rounds: f16x3-split MFMA, f32 accumulate)" if ick == 2 else "f32", "data": "synthetic",
-        "config": {"workload": "%s; %d QPSK blocks per step %s, ring of %d buffer sets, independent steps pipelined over %d HIP streams%s"
-                               % (cfg["workload"], total_per_step if scaling == "strong" else B,
-                                  "in total, sharded contiguously over the GPUs" if scaling == "strong" else "per GPU", ns, S,
-                                  "; roofline: rank 0's kernels, cpu_baseline and per-path figures only in the 1-GPU run" if world > 1 else ""),
-                   "name": a.config, "block_size": N, "batch_per_gpu": B, "blocks_per_step_all_gpus": total_per_step, "streams": S,
-                   "sharding": "independent blocks per GPU (gfdm_amd.sharding.ShardedBatch: one handle + stream per device, contiguous shards), no data-path collective"},
-        "msym_per_s": value * N / 1e6,
+    result.update({
         "value_single_stream": total_per_step * a.steps / wall1_max,
-        # cfg2: `value` demodulates frames modulated `demod_lag_steps` steps earlier (cold: >= 256 MiB of traffic in between);
-        # value_same_slot demodulates the frames its own step has just written (may be served by the Infinity Cache)
-        "demod_lag_steps": lag, "value_same_slot": value_hot,
+        "value_same_slot": value_hot,
         "sustained": sustained,
         "roofline": roofline,
         "roofline_kernels": rk,
-        "kernels": {"modulate": mod.kernel_name(), "demodulate": dem.kernel_name(), "advanced": adv.kernel_name()},
         "output_checksum": [float(v) for v in chk],
-    }
-    if use_dist:
-        result["rank_wall_ms"] = rank_wall_ms
-        result["rank_hosts_cpus"] = gather_ranks(rank_placement(cpu_slice, launch_cpu), world)
+    })
     del sym, frames, eqs, outs, piped, single
 
     # ---- per-variant measurements (each alone on the stream, own ring): single GPU, K=64 M=9 only ---------------------------
@@ -1132,21 +1203,7 @@ def main():
         result["cpu_baseline"] = cpu_baseline(cfg, taps, a.cpu_seconds)
     elif rank == 0:
         result["cpu_baseline"] = None
-    pr = torch.cuda.get_device_properties(local)
-    rank_devices = gather_ranks({"rank": rank, "device": local, "name": pr.name,
-                                 "pci": "%04x:%02x:%02x.0" % (getattr(pr, "pci_domain_id", 0), getattr(pr, "pci_bus_id", 0), getattr(pr, "pci_device_id", 0))}, world)
-    if rank == 0:
-        try:
-            rccl = ".".join(str(v) for v in torch.cuda.nccl.version())
-        except Exception:                                                 # noqa: BLE001
-            rccl = None
-        result["distributed"] = {"initialized": bool(use_dist), "backend": (a.dist_backend + (" (RCCL)" if a.dist_backend == "nccl" else "")) if use_dist else None,
-                                 "world_size": world, "rccl_version": rccl, "devices_visible": ndev, "rank_devices": rank_devices,
-                                 "collectives": "2 barriers per timed loop + 2 all-reduces per statistic (sharding.reduce_stats); no payload collective",
-                                 "scaling_curve": "none measured so far: no multi-GPU node was available to the builder or the driver in rounds 1-6" if world == 1 else "this line is one point of it"}
-        print(json.dumps(result))
-    if use_dist:
-        dist.destroy_process_group()
+    finish(result, a, rank, world, local, ndev, use_dist)
 
 
 if __name__ == "__main__":

@@ -32,8 +32,8 @@ probe)     # PROBE_SPECS: "path blocks K M L" entries separated by ';' (default:
   done ;;
 bench)
   cd $R
-  python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; cut -c1-300 $O/bench_default.json
-  for c in cfg3 cfg4 cfg5; do python3 bench.py --config $c --no-cpu-baseline --no-host-paths > $O/bench_$c.json 2>/dev/null; cut -c1-200 $O/bench_$c.json; done
+  python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; cut -c1-300 $O/bench_default.json
+  for c in cfg3 cfg4 cfg5; do python3 bench.py --full --config $c --no-cpu-baseline --no-host-paths > $O/bench_$c.json 2>/dev/null; cut -c1-200 $O/bench_$c.json; done
   python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_line.json 2>/dev/null; cut -c1-200 $O/bench_driver_line.json ;;
 alone)
   python3 -c "import sys; sys.path.insert(0, '$R/gr-gfdm_amd/python'); import gfdm_amd; print(gfdm_amd.build_id())" > $O/build_id.txt

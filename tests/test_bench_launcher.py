@@ -157,7 +157,7 @@ def test_rccl_process_group_runs_on_the_one_gpu_of_the_box():
     env = dict(os.environ, OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    common = ["--config", "cfg4", "--batch", "512", "--steps", "3", "--warmup", "1", "--sustained-seconds", "0", "--no-paths", "--no-cpu-baseline",
+    common = ["--config", "cfg4", "--batch", "512", "--steps", "3", "--warmup", "1", "--full", "--sustained-seconds", "0", "--no-paths", "--no-cpu-baseline",
               "--ring-mib", "256"]
     bench_py = os.path.join(ROOT, "bench.py")
     runs = {"plain": [sys.executable, bench_py] + common,
@@ -192,7 +192,7 @@ def test_whole_multi_rank_bench_path_on_one_gpu():
     res = {}
     for n in (1, 2, 3):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dist-backend", "gloo", "--config", "cfg4", "--batch", "6000",
-                            "--steps", "3", "--warmup", "1", "--sustained-seconds", "0", "--no-cpu-baseline", "--ring-mib", "512"],
+                            "--steps", "3", "--warmup", "1", "--full", "--sustained-seconds", "0", "--no-cpu-baseline", "--ring-mib", "512"],
                            env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -221,7 +221,7 @@ def test_eight_rank_bench_on_one_gpu(cfg, batch):
     res = {}
     for n in (1, 8):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dist-backend", "gloo", "--config", cfg, "--batch", str(batch),
-                            "--steps", "3", "--warmup", "1", "--sustained-seconds", "0", "--kernel-seconds", "0.05", "--no-cpu-baseline", "--no-paths",
+                            "--steps", "3", "--warmup", "1", "--full", "--sustained-seconds", "0", "--kernel-seconds", "0.05", "--no-cpu-baseline", "--no-paths",
                             "--ring-mib", "256"] + (["--force-dist"] if n == 1 else []), env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-2000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -277,3 +277,67 @@ def test_a_rendezvous_that_never_completes_ends_in_an_error_line_not_in_a_hang()
                                 {"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "2", "LOCAL_WORLD_SIZE": "2", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port())})
     assert rc == 4 and len(lines) == 1 and "failed to form" in lines[0]["error"] and lines[0]["n_gpus"] == 2, (rc, lines, err[-1500:])
     assert time.time() - t0 < 120
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_size_limit(tmp_path):
+    """--dump-outputs writes complex (blocks, N) outputs as float32 (blocks, N, 2); an output that fits is written whole, above 64 MB in all
+    every array keeps an equal share of its blocks, in ascending order and the same blocks on every run.  --full is off by default and
+    --steps 0 is refused."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None and bench.parse(["--full", "--dump-outputs", "d"]).full is True
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    g = torch.Generator().manual_seed(5)
+    big = torch.complex(torch.randn(9000, 1920, generator=g), torch.randn(9000, 1920, generator=g))         # 138 MB as complex64
+    small = torch.complex(torch.randn(5, 576, generator=g), torch.randn(5, 576, generator=g))
+    infos = [bench.dump_outputs({"tx_frames": big, "rx_symbols": small}, str(tmp_path / d)) for d in ("a", "b")]
+    assert infos[0] == infos[1]
+    assert infos[0]["rx_symbols"] == {"shape": [5, 576, 2], "blocks_of": 5, "sample_seed": None}
+    assert infos[0]["tx_frames"]["blocks_of"] == 9000 and infos[0]["tx_frames"]["sample_seed"] is not None
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 10 ** 6
+    assert sorted(os.listdir(tmp_path / "a")) == ["rx_symbols.npy", "tx_frames.npy"]
+    rx = np.load(tmp_path / "a" / "rx_symbols.npy")
+    assert rx.dtype == np.float32 and np.array_equal(rx, torch.view_as_real(small).numpy())
+    tx = np.load(tmp_path / "a" / "tx_frames.npy")
+    assert tx.dtype == np.float32 and tx.shape[1:] == (1920, 2) and 1000 < tx.shape[0] < 9000
+    assert np.array_equal(tx, np.load(tmp_path / "b" / "tx_frames.npy"))
+    full = torch.view_as_real(big).numpy()
+    rows = [int(np.flatnonzero(full[:, 0, 0] == r[0, 0])[0]) for r in tx]                # (random floats: the first one names the block)
+    assert rows == sorted(set(rows)) and all(np.array_equal(tx[i], full[r]) for i, r in enumerate(rows))
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_run_times_the_steps_it_is_given_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) is the headline alone: exactly --steps timed steps, `ms_per_step` = their wall time / steps, none of the
+    --full figures.  --dump-outputs writes what the last timed step computed: cfg2 the modulated frames and the demodulated symbols, cfg3
+    the ZF + 2 IC receiver's symbols, which sit on the transmitted QPSK points; a second run with the same arguments writes the same values."""
+    import numpy as np
+    runs = {}
+    for name, cfg in (("cfg2", "cfg2"), ("cfg2_again", "cfg2"), ("cfg3", "cfg3")):
+        rc, lines, err = _raw_bench(["--gpus", "1", "--config", cfg, "--batch", "256", "--steps", "7", "--warmup", "2", "--ring-mib", "64",
+                                     "--dump-outputs", str(tmp_path / name)], timeout=600)
+        assert rc == 0 and len(lines) == 1, err[-2000:]
+        runs[name] = lines[0]
+    for name, r in runs.items():
+        assert (r["steps"], r["warmup"], r["n_gpus"], r["unit"], r["higher_is_better"], r["dtype"]) == (7, 2, 1, "blocks/s", True, "f32")
+        assert r["value"] == pytest.approx(256 * 1e3 / r["ms_per_step"], rel=1e-9)
+        assert not {"roofline", "sustained", "paths", "large_batch", "cpu_baseline", "output_checksum", "single_block_host_us"} & set(r)
+    assert set(runs["cfg2"]["outputs"]) == {"tx_frames", "rx_symbols"} and set(runs["cfg3"]["outputs"]) == {"rx_symbols"}
+    for name in ("tx_frames", "rx_symbols"):
+        x = np.load(tmp_path / "cfg2" / (name + ".npy"))
+        assert x.dtype == np.float32 and x.shape == (256, 576, 2) and np.all(np.isfinite(x)) and np.abs(x).max() > 0.1
+        assert np.array_equal(x, np.load(tmp_path / "cfg2_again" / (name + ".npy")))
+    z = np.load(tmp_path / "cfg3" / "rx_symbols.npy")
+    assert z.shape == (256, 576, 2) and np.max(np.abs(np.abs(z) - np.sqrt(0.5))) < 0.2
