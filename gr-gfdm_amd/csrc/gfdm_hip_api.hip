@@ -872,13 +872,14 @@ int gfdm_hip_advanced_receiver_create(gfdm_hip_advanced_receiver** out, int time
 
     const size_t pts_bytes = (size_t)n_points * sizeof(cf);
     const size_t smap_bytes = (size_t)(n_subcarrier_map > 0 ? n_subcarrier_map : 1) * sizeof(int);
-    const size_t act_bytes = (size_t)subcarriers;
+    const size_t act_bytes = (size_t)subcarriers * sizeof(int);     // (4-byte aligned: pts and smap are whole multiples of 4 bytes)
     std::vector<unsigned char> blob(pts_bytes + smap_bytes + act_bytes, 0);
     memcpy(blob.data(), pts, pts_bytes);
     if (n_subcarrier_map > 0) memcpy(blob.data() + pts_bytes, subcarrier_map, (size_t)n_subcarrier_map * sizeof(int));
-    for (int i = 0; i < n_subcarrier_map; ++i) {            // multiplicity of each subcarrier in the map (saturating)
-        unsigned char& c = blob[pts_bytes + smap_bytes + subcarrier_map[i]];
-        if (c < 255) ++c;
+    {                                                        // multiplicity of each subcarrier in the map: the full count, no saturation
+        std::vector<int> act(subcarriers, 0);
+        for (int i = 0; i < n_subcarrier_map; ++i) ++act[subcarrier_map[i]];
+        memcpy(blob.data() + pts_bytes + smap_bytes, act.data(), act_bytes);
     }
     {
         DeviceGuard guard(device);
@@ -892,7 +893,7 @@ int gfdm_hip_advanced_receiver_create(gfdm_hip_advanced_receiver** out, int time
     a->ic.npoints = n_points;
     a->ic.points = reinterpret_cast<const cf*>(a->d_ic);
     a->ic.smap = reinterpret_cast<const int*>(reinterpret_cast<unsigned char*>(a->d_ic) + pts_bytes);
-    a->ic.active = reinterpret_cast<unsigned char*>(a->d_ic) + pts_bytes + smap_bytes;
+    a->ic.active = reinterpret_cast<const int*>(reinterpret_cast<unsigned char*>(a->d_ic) + pts_bytes + smap_bytes);
     a->ic.n_active = n_subcarrier_map;
     *out = a;
     return GFDM_HIP_OK;

@@ -63,7 +63,7 @@ struct IcParams {
     int decision;              // gfdm_hip_decision (never AUTO on the device)
     int npoints;
     const cf* points;          // [npoints]
-    const unsigned char* active;   // [K] how often the subcarrier occurs in subcarrier_map (0 = inactive)
+    const int* active;         // [K] how often the subcarrier occurs in subcarrier_map (0 = inactive; the row-lane phase sums weigh by it)
     int n_active;              // subcarrier_map.size() (duplicates counted, as the reference does)
     const int* smap;           // [n_active] the subcarrier_map itself (order matters for the phase sum)
     RxIo io;

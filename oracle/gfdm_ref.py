@@ -45,7 +45,9 @@ derived from its definition:
     tests/test_parity_gpu.py::test_duplicate_subcarrier_map_entry_counts_twice_in_the_phase_mean;
   * the tie rule of constellation_qpsk::decision_maker, zero -> the negative point (from GNU Radio's source; called
     at :119): tests/test_parity_gpu.py::test_all_zero_and_tie_inputs_follow_the_reference_decision_rule.
-  Every other constellation: nearest point, first minimum wins -- parity unpinned.
+  Every other constellation: nearest point, first minimum wins (constellation::decision_maker); the BPSK sign test
+  sends zero to the negative point: tests/test_decisions.py (against the C oracle and decision_maker, exact ties) and
+  tests/test_constellations_gpu.py (known answers for ties, zero and a subcarrier listed 300 times).
 
 All arithmetic is complex128; callers round to complex64 where they compare
 with float32 results.
@@ -55,7 +57,7 @@ import numpy as np
 __all__ = [
     "normalize_taps", "ic_filter_taps", "modulate", "fft_filter_downsample",
     "transform_subcarriers_to_td", "cancel_sc_interference", "demodulate",
-    "qpsk_points", "decide", "advanced_receive", "phase_offset",
+    "qpsk_points", "decide", "decision_margin", "phase_cut_margin", "advanced_receive", "phase_offset",
 ]
 
 
@@ -174,6 +176,40 @@ def decide(x, points, kind="nearest"):
     return p[idx]
 
 
+def decision_margin(x, points, kind="nearest"):
+    """Distance of each sample from the nearest boundary of the decision region decide() puts it in: a float32 path may
+    decide differently only where this is below its rounding noise.  'qpsk': min(|re|, |im|); 'bpsk': |re|; 'nearest':
+    distance to the closest perpendicular bisector between the chosen point p_i and any other point p_j,
+    min_j (|x - p_j|^2 - |x - p_i|^2) / (2 |p_j - p_i|) -- 0 at an exact tie, +inf with a single point."""
+    x = _c128(x)
+    if kind == "qpsk":
+        return np.minimum(np.abs(x.real), np.abs(x.imag))
+    if kind == "bpsk":
+        return np.abs(x.real)
+    p = _c128(points).ravel()
+    flat = x.ravel()
+    out = np.empty(flat.shape, dtype=np.float64)
+    step = max(1, (1 << 22) // max(1, p.size))               # bounds the (samples x points) temporaries
+    for s in range(0, flat.size, step):
+        v = flat[s:s + step]
+        dist = np.abs(v[:, None] - p) ** 2
+        i = np.argmin(dist, axis=-1)
+        sep = np.abs(p[None, :] - p[i][:, None])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m = (dist - dist[np.arange(v.size), i][:, None]) / (2.0 * sep)
+        m[sep == 0] = np.inf                                  # the chosen point itself (and exact duplicates of it)
+        out[s:s + step] = m.min(axis=-1)
+    return out.reshape(x.shape)
+
+
+def phase_cut_margin(x):
+    """Distance of each sample from the branch cut of arg (the negative real axis): |im x| where re x < 0, else +inf.
+    calculate_phase_offset sums arg differences without unwrapping, so a sample that crosses the cut moves the phase
+    mean by 2 pi / (map size * timeslots)."""
+    x = _c128(x)
+    return np.where(x.real < 0, np.abs(x.imag), np.inf)
+
+
 def phase_offset(detected, demod, smap, M, K):
     """advanced_receiver_kernel_cc::calculate_phase_offset -- .cc:78-91:
     mean over active (k, m) of arg(detected) - arg(demod), no unwrapping."""
@@ -193,18 +229,25 @@ def advanced_receive(frame, ntaps, M, K, L, smap, points, ic_iter, f_eq=None,
     out = transform_subcarriers_to_td(S, M, K)
     batch = out.shape[:-1]
     stages = {"S": S.copy(), "d0": out.copy(), "iters": []}
+    margin = np.full(batch, np.inf)
+    red = lambda v: v.reshape(batch + (-1,)).min(axis=-1, initial=np.inf)
     for j in range(ic_iter):
+        act = out.reshape(batch + (K, M))[..., smap, :]
+        margin = np.minimum(margin, red(decision_margin(act, points, kind)))
         dec = np.zeros(batch + (K, M), dtype=np.complex128)                  # memset :112
-        dec[..., smap, :] = decide(out.reshape(batch + (K, M))[..., smap, :], points, kind)
+        dec[..., smap, :] = decide(act, points, kind)
         dec = dec.reshape(batch + (K * M,))
         if do_phase_compensation > 0 and j == 0:                            # :59-71
+            margin = np.minimum(margin, red(phase_cut_margin(act)))
             phi = phase_offset(dec, out, smap, M, K)
             S = S * np.exp(1j * np.asarray(phi))[..., None]
         fd = cancel_sc_interference(dec, S, ic, M, K)                        # :72-73
         out = transform_subcarriers_to_td(fd, M, K)                          # :74
         stages["iters"].append(out.copy())
     if return_stages:
-        stages["dec_margin"] = None
+        # per block: the smallest decision margin of any decided component in any round, and with phase compensation
+        # the smallest distance of a round-0 symbol from arg's branch cut (+inf without rounds)
+        stages["dec_margin"] = margin
         return out, stages
     return out
 
