@@ -167,6 +167,9 @@ enum EqSource {
     EQ_PREAMBLE = 2       // f_eq points at the received preambles; the kernel runs the channel estimator itself
 };
 
+// interference-cancellation rounds of k_row_receive (gfdm_rowlane_impl.h): vector ALU, vector ALU with a real even IC kernel, matrix cores
+enum IcKind { ICK_GENERAL = 0, ICK_REALSYM = 1, ICK_MFMA = 2 };
+
 #ifndef __HIPCC_RTC__
 // stages of the estimator chain; a launch runs in_stage -> out_stage inside one kernel
 enum EstStage { EST_RX_PREAMBLE = 0, EST_PREAMBLE_CHANNEL = 1, EST_FILTERED = 2, EST_FRAME = 3 };

@@ -1,5 +1,5 @@
 // Launch geometry of the row-lane kernels as plain constexpr functions of the shape: ONE definition for the kernels
-// (gfdm_rowlane_impl.h, compile-time shapes) and for the host code that launches run-time instantiated kernels (gfdm_jit.hip).
+// (gfdm_rowlane_impl.h) and for the host code that launches them, compiled or instantiated at run time (gfdm_rowvariants.h).
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <stddef.h>

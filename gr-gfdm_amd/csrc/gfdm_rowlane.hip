@@ -1,95 +1,82 @@
-// Row-lane kernel family: shape table and dispatch.  The kernels live in gfdm_rowlane_impl.h and are instantiated by
-// gfdm_rowlane_shape.hip, compiled once per shape and part (Makefile: ROW_SHAPES must list the same shapes as GFDM_ROW_SHAPES;
-// the library is linked with --no-undefined, so a shape missing there fails the build).
-#include "gfdm_plan.h"
-#include "gfdm_tx.h"
-#include "gfdm_rowgeom.h"
+// Row-lane kernel family: dispatch over the shapes compiled into the library (gfdm_row_shapes.h).  The kernels live in
+// gfdm_rowlane_impl.h; gfdm_rowlane_shape.hip instantiates the kernels of one part of one shape (the library is linked with
+// --no-undefined, so a shape the Makefile did not build fails the link).  Which kernel a call runs and its launch geometry:
+// gfdm_rowvariants.h, shared with the run-time instantiation (gfdm_jit.hip).
+#include "gfdm_rowvariants.h"
+#include "gfdm_row_shapes.h"
 
-#define GFDM_ROW_SHAPES(X) \
-    X(64, 9, 2)            \
-    X(32, 5, 2)            \
-    X(32, 9, 2)            \
-    X(128, 15, 4)          \
-    X(256, 31, 2)          \
-    X(64, 5, 2)            \
-    X(64, 15, 2)           \
-    X(128, 9, 2)           \
-    X(128, 15, 2)          \
-    X(128, 21, 2)          \
-    X(4, 16, 2)            \
-    X(4, 8, 2)             \
-    X(96, 25, 2)
+#include <array>
 
 namespace gfdm {
 
-#define RX_DECL(NAME_)                                                                                                              \
-    hipError_t NAME_(const DevicePlan& p, const IcParams& ic, const EstPlan* est, const cf* twT, int mode, cf* out, const cf* in,   \
-                     const cf* f_eq, int64_t nblocks, hipStream_t s);
-#define X(K_, M_, L_)                                                                                                               \
-    RX_DECL(rowlane_rx0_##K_##_##M_##_##L_)                                                                                         \
-    RX_DECL(rowlane_rx1_##K_##_##M_##_##L_)                                                                                         \
-    RX_DECL(rowlane_rx2_##K_##_##M_##_##L_)                                                                                         \
-    RX_DECL(rowlane_rx4_##K_##_##M_##_##L_)                                                                                         \
-    hipError_t rowlane_mod_##K_##_##M_##_##L_(const DevicePlan& p, const TxParams& tx, const cf* twT, cf* out, const cf* in,        \
-                                              int64_t nblocks, hipStream_t s);                                                      \
-    hipError_t rowlane_est_##K_##_##M_##_##L_(const EstPlan& e, cf* out, const cf* in, int64_t nframes, hipStream_t s);
+typedef const void* const* KernelList;        // the kernels of one part of a shape, in rowvar::part_variants order
+#define GFDM_ROWLANE_PART(K_, M_, L_, P_) rowlane_##K_##_##M_##_##L_##_p##P_
+#define X(K_, M_, L_)                                                                                                                  \
+    extern const KernelList GFDM_ROWLANE_PART(K_, M_, L_, 0), GFDM_ROWLANE_PART(K_, M_, L_, 1), GFDM_ROWLANE_PART(K_, M_, L_, 2),       \
+        GFDM_ROWLANE_PART(K_, M_, L_, 3), GFDM_ROWLANE_PART(K_, M_, L_, 4);
 GFDM_ROW_SHAPES(X)
 #undef X
-#undef RX_DECL
 
-bool rowlane_supports(int M, int K, int L)
+namespace {
+
+// L < 0: the first shape with this (K, M) (the estimator does not depend on the overlap); nullptr: not compiled
+KernelList compiled_part(int K, int M, int L, int part)
 {
-#define X(K_, M_, L_) if (K == K_ && M == M_ && L == L_) return true;
+#define X(K_, M_, L_)                                                                                                                  \
+    if (K == K_ && M == M_ && (L < 0 || L == L_))                                                                                      \
+        return std::array<KernelList, JIT_NUM_PARTS>{ GFDM_ROWLANE_PART(K_, M_, L_, 0), GFDM_ROWLANE_PART(K_, M_, L_, 1),              \
+                                                      GFDM_ROWLANE_PART(K_, M_, L_, 2), GFDM_ROWLANE_PART(K_, M_, L_, 3),              \
+                                                      GFDM_ROWLANE_PART(K_, M_, L_, 4) }[part];
     GFDM_ROW_SHAPES(X)
 #undef X
-    return false;
+    return nullptr;
 }
 
-// the estimator does not depend on the overlap: the first shape with this (K, M)
-bool rowlane_supports_estimate(int M, int K)
+hipError_t launch(KernelList kernels, const rowvar::Choice& c, int K, int M, int64_t nblocks, hipStream_t s, void** args)
 {
-#define X(K_, M_, L_) if (K == K_ && M == M_) return true;
-    GFDM_ROW_SHAPES(X)
-#undef X
-    return false;
+    if (!kernels || c.index < 0) return hipErrorInvalidValue;
+    const void* f = kernels[c.index];
+    const rowvar::Geometry g = rowvar::geometry(K, M, c.v, nblocks);
+    const hipError_t e = rowvar::allow_lds(f, g.lds);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(f, dim3(g.grid), dim3(g.block), args, g.lds, s);
 }
+
+}  // namespace
+
+bool rowlane_supports(int M, int K, int L) { return compiled_part(K, M, L, JIT_PART_RX) != nullptr; }
+
+bool rowlane_supports_estimate(int M, int K) { return compiled_part(K, M, -1, JIT_PART_EST) != nullptr; }
 
 hipError_t launch_rowlane_estimate(const EstPlan& e, cf* out, const cf* in, int64_t nframes, hipStream_t s)
 {
     if (nframes <= 0) return hipSuccess;
-#define X(K_, M_, L_) if (e.K == K_ && e.M == M_) return rowlane_est_##K_##_##M_##_##L_(e, out, in, nframes, s);
-    GFDM_ROW_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    EstPlan a_e = e;
+    void* args[] = { &a_e, &out, &in, &nframes };
+    return launch(compiled_part(e.K, e.M, -1, JIT_PART_EST), rowvar::select_estimate(e), e.K, e.M, nframes, s, args);
 }
 
 hipError_t launch_rowlane_modulate(const DevicePlan& p, const TxParams& tx, const cf* twT, cf* out, const cf* in, int64_t nblocks,
                                    hipStream_t s)
 {
     if (nblocks <= 0) return hipSuccess;
-#define X(K_, M_, L_) if (p.K == K_ && p.M == M_ && p.L == L_) return rowlane_mod_##K_##_##M_##_##L_(p, tx, twT, out, in, nblocks, s);
-    GFDM_ROW_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    DevicePlan a_p = p;
+    TxParams a_tx = tx;
+    void* args[] = { &a_p, &a_tx, &twT, &out, &in, &nblocks };
+    return launch(compiled_part(p.K, p.M, p.L, JIT_PART_MOD), rowvar::select_modulate(p, tx), p.K, p.M, nblocks, s, args);
 }
 
 hipError_t launch_rowlane_receive(const DevicePlan& p, const IcParams& ic, const EstPlan* est, const cf* twT, int mode, cf* out, const cf* in,
                                   const cf* f_eq, int64_t nblocks, hipStream_t s)
 {
     if (nblocks <= 0) return hipSuccess;
-    const bool ic_rounds = (mode == RX_IC && ic.ic_iter > 0);
-    // which translation unit holds the kernel (launch_rx); 4: cancellation rounds on the matrix cores
-    const int part = (ic_rounds && ic_mfma_applies(p, ic) && rowgeom::ic_mfma(p.K, p.M)) ? 4 : est ? 2 : ic_rounds ? 1 : 0;
-#define X(K_, M_, L_)                                                                                              \
-    if (p.K == K_ && p.M == M_ && p.L == L_) {                                                                    \
-        if (part == 4) return rowlane_rx4_##K_##_##M_##_##L_(p, ic, est, twT, mode, out, in, f_eq, nblocks, s);   \
-        if (part == 2) return rowlane_rx2_##K_##_##M_##_##L_(p, ic, est, twT, mode, out, in, f_eq, nblocks, s);   \
-        if (part == 1) return rowlane_rx1_##K_##_##M_##_##L_(p, ic, est, twT, mode, out, in, f_eq, nblocks, s);   \
-        return rowlane_rx0_##K_##_##M_##_##L_(p, ic, est, twT, mode, out, in, f_eq, nblocks, s);                  \
-    }
-    GFDM_ROW_SHAPES(X)
-#undef X
-    return hipErrorInvalidValue;
+    const rowvar::Choice c = rowvar::select_receive(p, ic, est, mode, f_eq);
+    static const EstPlan kNoEst = {};
+    DevicePlan a_p = p;
+    IcParams a_ic = ic;
+    EstPlan a_est = est ? *est : kNoEst;
+    void* args[] = { &a_p, &a_ic, &a_est, &twT, &out, &in, &f_eq, &nblocks };
+    return launch(compiled_part(p.K, p.M, p.L, c.v.part), c, p.K, p.M, nblocks, s, args);
 }
 
 }  // namespace gfdm

@@ -541,7 +541,6 @@ __device__ __forceinline__ cf decide_point(cf x, const IcParams& ic)
 //   * Blocks of several wavefronts (K >= 128) pass the decisions of each wavefront's first and last row through a small double-buffered LDS
 //     area behind the tiles (128 bytes per wavefront and buffer), one workgroup barrier per round.
 // Rows p >= M of the 16 x 16 tile are padding: A is zero there and in the columns of timeslots >= M, d0 is zero there.
-enum IcKind { ICK_GENERAL = 0, ICK_REALSYM = 1, ICK_MFMA = 2 };
 
 // How d0 reaches the C / D layout of the matrix-core rounds:
 //   true   phase D runs with the block's rows dealt to the lanes in IcMfma's interleaved order and 32 v_permlane*_swap transpose the registers
@@ -1179,75 +1178,6 @@ __global__ __launch_bounds__(RowShape<K>::WG) void k_row_modulate(DevicePlan p, 
     }
 }
 
-#ifndef __HIPCC_RTC__
-// PART selects which receive kernels a translation unit instantiates (compile time is dominated by the largest shape):
-//   0  frequency-domain output and plain demodulation, equaliser none / vector
-//   1  interference cancellation on the vector ALU (any constellation, phase compensation, complex IC kernel), equaliser none / vector
-//   2  every mode with the equaliser estimated from the preamble inside the kernel (EQ_PREAMBLE), IC rounds on the vector ALU
-//   4  interference cancellation with the rounds on the matrix cores (IcMfma: QPSK, real even IC kernel, no phase compensation),
-//      equaliser none / vector / preamble  (3 = the modulators)
-template <int K, int M, int L, int PART>
-hipError_t launch_rx(const DevicePlan& p, const IcParams& ic, const EstPlan* est, const cf* twT, int mode, cf* out, const cf* in, const cf* f_eq,
-                     int64_t nblocks, hipStream_t st)
-{
-    static_assert(row_lds_bytes<K, M>() <= 64 * 1024, "row-lane tile exceeds the default dynamic LDS limit");
-    const dim3 grid((unsigned)((nblocks + RowShape<K>::BPW - 1) / RowShape<K>::BPW)), block(RowShape<K>::WG);
-    static const EstPlan kNoEst = {};
-    const EstPlan& e = est ? *est : kNoEst;
-    const bool pre = (PART == 2) || (PART == 4 && est);                          // EQ_PREAMBLE: two more tile columns + the estimate behind the tiles
-    size_t lds = pre ? row_lds_bytes<K, M + 2>() + EstTile<K>::bytes : row_lds_bytes<K, M>();
-    if (PART == 4) lds += rowgeom::ic_mfma_edge_bytes(K);       // behind everything else: the wavefronts' edge rows of the IcMfma rounds
-#define GFDM_RX(MODE_, EQ_, ICK_)                                                                                                       \
-    do {                                                                                                                            \
-        if (lds > 64 * 1024) {      /* only the largest shape with the estimate behind its tile */                                 \
-            hipError_t err_ = hipFuncSetAttribute(reinterpret_cast<const void*>(k_row_receive<K, M, L, MODE_, EQ_, ICK_>),          \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
-            if (err_ != hipSuccess) return err_;                                                                                    \
-        }                                                                                                                           \
-        hipLaunchKernelGGL((k_row_receive<K, M, L, MODE_, EQ_, ICK_>), grid, block, lds, st, p, ic, e, twT, out, in, f_eq, nblocks); \
-    } while (0)
-    const bool ic_rounds = (mode == RX_IC && ic.ic_iter > 0);
-    if constexpr (PART == 4) {
-        if constexpr (rowgeom::ic_mfma(K, M)) {
-            if (!ic_rounds || !ic_mfma_applies(p, ic)) return hipErrorInvalidValue;
-            if (est) GFDM_RX(RX_IC, EQ_PREAMBLE, ICK_MFMA);
-            else if (f_eq) GFDM_RX(RX_IC, EQ_VECTOR, ICK_MFMA);
-            else GFDM_RX(RX_IC, EQ_NONE, ICK_MFMA);
-        } else {
-            return hipErrorInvalidValue;
-        }
-    } else if constexpr (PART == 2) {
-        if (!est) return hipErrorInvalidValue;
-        if (mode == RX_FD) GFDM_RX(RX_FD, EQ_PREAMBLE, ICK_GENERAL);
-        else if (!ic_rounds) GFDM_RX(RX_DEMOD, EQ_PREAMBLE, ICK_GENERAL);
-        else if (p.ic_real_sym) GFDM_RX(RX_IC, EQ_PREAMBLE, ICK_REALSYM);
-        else GFDM_RX(RX_IC, EQ_PREAMBLE, ICK_GENERAL);
-    } else if constexpr (PART == 1) {
-        if (est || !ic_rounds) return hipErrorInvalidValue;
-        if (p.ic_real_sym) { if (f_eq) GFDM_RX(RX_IC, EQ_VECTOR, ICK_REALSYM); else GFDM_RX(RX_IC, EQ_NONE, ICK_REALSYM); }
-        else { if (f_eq) GFDM_RX(RX_IC, EQ_VECTOR, ICK_GENERAL); else GFDM_RX(RX_IC, EQ_NONE, ICK_GENERAL); }
-    } else {
-        if (est || ic_rounds) return hipErrorInvalidValue;
-        if (mode == RX_FD) { if (f_eq) GFDM_RX(RX_FD, EQ_VECTOR, ICK_GENERAL); else GFDM_RX(RX_FD, EQ_NONE, ICK_GENERAL); }
-        else { if (f_eq) GFDM_RX(RX_DEMOD, EQ_VECTOR, ICK_GENERAL); else GFDM_RX(RX_DEMOD, EQ_NONE, ICK_GENERAL); }
-    }
-#undef GFDM_RX
-    return hipGetLastError();
-}
-
-template <int K, int M, int L>
-hipError_t launch_mod(const DevicePlan& p, const TxParams& tx, const cf* twT, cf* out, const cf* in, int64_t nblocks, hipStream_t st)
-{
-    constexpr size_t lds = row_lds_bytes<K, M>();
-    const dim3 grid((unsigned)((nblocks + RowShape<K>::BPW - 1) / RowShape<K>::BPW)), block(RowShape<K>::WG);
-    if (tx.mapped && tx.framed) hipLaunchKernelGGL((k_row_modulate<K, M, L, 2>), grid, block, lds, st, p, tx, twT, out, in, nblocks);
-    else if (tx.mapped) hipLaunchKernelGGL((k_row_modulate<K, M, L, 1>), grid, block, lds, st, p, tx, twT, out, in, nblocks);
-    else hipLaunchKernelGGL((k_row_modulate<K, M, L, 0>), grid, block, lds, st, p, tx, twT, out, in, nblocks);
-    return hipGetLastError();
-}
-
-#endif  // !__HIPCC_RTC__
-
 // =====================================================================================================================
 // estimate_frame of preamble_channel_estimator_cc (lib/preamble_channel_estimator_cc.cc:284-295) in the row-lane layout: K lanes per
 // received preamble.  Same pieces as the EQ_PREAMBLE path of k_row_receive; the frame estimate of row q (bins M q .. M q + M - 1)
@@ -1326,47 +1256,5 @@ __global__ __launch_bounds__(RowShape<K>::WG) void k_row_estimate(EstPlan est, c
     }
 }
 
-#ifndef __HIPCC_RTC__
-template <int K, int M>
-hipError_t launch_est(const EstPlan& e, cf* out, const cf* in, int64_t nframes, hipStream_t st)
-{
-    constexpr size_t lds = row_lds_bytes<K, M>() + EstTile<K>::bytes;
-    const dim3 grid((unsigned)((nframes + RowShape<K>::BPW - 1) / RowShape<K>::BPW)), block(RowShape<K>::WG);
-    if (lds > 64 * 1024) {
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_row_estimate<K, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return err;
-    }
-    hipLaunchKernelGGL((k_row_estimate<K, M>), grid, block, lds, st, e, out, in, nframes);
-    return hipGetLastError();
-}
-
-#endif  // !__HIPCC_RTC__
-
 }  // namespace GFDM_ROWLANE_NS (anonymous in the library build)
 }  // namespace gfdm
-
-// gfdm_rowlane_shape.hip is compiled once per (shape, part) -- see the Makefile -- so that the instantiations build in parallel.
-#define GFDM_ROWLANE_RX_PART_I(K_, M_, L_, PART_)                                                                                   \
-    namespace gfdm {                                                                                                                \
-    hipError_t rowlane_rx##PART_##_##K_##_##M_##_##L_(const DevicePlan& p, const IcParams& ic, const EstPlan* est, const cf* twT,  \
-                                                      int mode, cf* out, const cf* in, const cf* f_eq, int64_t nblocks,             \
-                                                      hipStream_t s)                                                                \
-    {                                                                                                                               \
-        return launch_rx<K_, M_, L_, PART_>(p, ic, est, twT, mode, out, in, f_eq, nblocks, s);                                      \
-    }                                                                                                                               \
-    }
-#define GFDM_ROWLANE_MOD_I(K_, M_, L_)                                                                                              \
-    namespace gfdm {                                                                                                                \
-    hipError_t rowlane_mod_##K_##_##M_##_##L_(const DevicePlan& p, const TxParams& tx, const cf* twT, cf* out, const cf* in,        \
-                                              int64_t nblocks, hipStream_t s)                                                       \
-    {                                                                                                                               \
-        return launch_mod<K_, M_, L_>(p, tx, twT, out, in, nblocks, s);                                                             \
-    }                                                                                                                               \
-    hipError_t rowlane_est_##K_##_##M_##_##L_(const EstPlan& e, cf* out, const cf* in, int64_t nframes, hipStream_t s)              \
-    {                                                                                                                               \
-        return launch_est<K_, M_>(e, out, in, nframes, s);                                                                          \
-    }                                                                                                                               \
-    }
-// argument macros (-DGFDM_SHAPE_K=..) must be expanded before they are pasted into the function names
-#define GFDM_ROWLANE_RX_PART(K_, M_, L_, PART_) GFDM_ROWLANE_RX_PART_I(K_, M_, L_, PART_)
-#define GFDM_ROWLANE_MOD(K_, M_, L_) GFDM_ROWLANE_MOD_I(K_, M_, L_)

@@ -33,8 +33,7 @@ def run(s):
     elif path == "demod_mf_ic2": adv.demodulate(x, out=o)
 for s in range(slots - 1): run(s)                       # warm-up without stamps
 torch.cuda.synchronize()
-mx = gfdm_amd.capi.lib().gfdm_hip_set_ic_matrix_cores(1); gfdm_amd.capi.lib().gfdm_hip_set_ic_matrix_cores(mx)
-part = 0 if "ic" not in path else (4 if (mx == 2 or (mx == 1 and K >= 128)) and 4 <= M <= 16 else 1)
+part = 0 if "ic" not in path else 1                     # JIT_PART_RX / JIT_PART_RX_IC (the matrix-core rounds included)
 setter = getattr(ctypes.CDLL(sys.argv[1]), "gfdm_debug_set_stamp_buffer_%d_%d_%d_p%d" % (K, M, L, part))
 setter.argtypes = [ctypes.c_void_p]
 assert setter(ctypes.c_void_p(stamps.data_ptr())) == 0

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gfdm_plan.h"
+#include "gfdm_row_shapes.h"
 #include "gfdm_tx.h"
 #include "loopback_transform.h"
 
@@ -156,9 +157,10 @@ hipError_t est_enqueue(const gfdm::EstPlan& e, int in_stage, int out_stage, cf* 
     });
 }
 
-// the shapes compiled into the library (ROW_SHAPES of gr-gfdm_amd/Makefile, as K_M_L)
-const int kRowShapes[][3] = { { 64, 9, 2 }, { 32, 5, 2 }, { 32, 9, 2 }, { 128, 15, 4 }, { 256, 31, 2 }, { 64, 5, 2 }, { 64, 15, 2 },
-                              { 128, 9, 2 }, { 128, 15, 2 }, { 128, 21, 2 }, { 4, 16, 2 }, { 4, 8, 2 }, { 96, 25, 2 } };
+// the shapes compiled into the library (gr-gfdm_amd/csrc/gfdm_row_shapes.h, as K, M, L)
+#define X(K_, M_, L_) { K_, M_, L_ },
+const int kRowShapes[][3] = { GFDM_ROW_SHAPES(X) };
+#undef X
 
 }  // namespace
 
