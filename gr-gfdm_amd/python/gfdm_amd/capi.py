@@ -167,6 +167,24 @@ def lib():
         "gfdm_hip_receiver_demodulate_estimated_device": (i32, [vp, vp, vp, vp, i32, i32, i64, vp]),
         "gfdm_hip_advanced_receiver_work_estimated_host": (i32, [vp, vp, vp, vp, i32, i32, i64]),
         "gfdm_hip_advanced_receiver_work_estimated_device": (i32, [vp, vp, vp, vp, i32, i32, i64, vp]),
+        "gfdm_hip_burst_sync_create": (i32, [ctypes.POINTER(vp), i32, i32, vp, i32, i64, i32]),
+        "gfdm_hip_burst_sync_destroy": (i32, [vp]),
+        "gfdm_hip_burst_sync_fft_len": (i32, [vp]),
+        "gfdm_hip_burst_sync_cp_len": (i32, [vp]),
+        "gfdm_hip_burst_sync_window_len": (i64, [vp]),
+        "gfdm_hip_burst_sync_corr_len": (i64, [vp]),
+        "gfdm_hip_burst_sync_find_frame_start_host": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64]),
+        "gfdm_hip_burst_sync_find_frame_start_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
+        "gfdm_hip_burst_sync_auto_correlate_host": (i32, [vp, vp, vp, vp, i64, i64, i64, i64]),
+        "gfdm_hip_burst_sync_auto_correlate_device": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
+        "gfdm_hip_burst_extractor_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, i32]),
+        "gfdm_hip_burst_extractor_destroy": (i32, [vp]),
+        "gfdm_hip_burst_extractor_burst_len": (i32, [vp]),
+        "gfdm_hip_burst_extractor_tag_backoff": (i32, [vp]),
+        "gfdm_hip_burst_extractor_set_cfo_correction": (i32, [vp, i32]),
+        "gfdm_hip_burst_extractor_get_cfo_correction": (i32, [vp]),
+        "gfdm_hip_burst_extractor_extract_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i64]),
+        "gfdm_hip_burst_extractor_extract_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == the library does not export a declared symbol
@@ -1001,3 +1019,137 @@ class ChannelEstimator(_Kernel):
         if a.ndim <= 1 and nf == 1:
             return float(snr[0]), cnrs[0]
         return snr, cnrs
+
+
+def _dev_arg(t, dtype, n_elems, what, device):
+    """device pointer of a contiguous torch tensor of `dtype` with n_elems elements on `device`"""
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise TypeError("%s must be a contiguous %s CUDA/HIP tensor" % (what, dtype))
+    if t.device.index != device:
+        raise RuntimeError("%s lives on GPU %d, the handle on GPU %d" % (what, t.device.index, device))
+    if t.numel() != n_elems:
+        raise RuntimeError("%s has %d elements, expected %d" % (what, t.numel(), n_elems))
+    return t.data_ptr()
+
+
+class BurstSync(_Kernel):
+    """Preamble timing / CFO synchronisation: pygfdm's find_frame_start (python/pygfdm/synchronization.py:154-263) on every window
+    stream[first + b * stride : ... + window_len] of a capture buffer (contract in include/gfdm_hip.h).  numpy samples -> numpy results
+    (host path), a torch complex64 device tensor -> torch results on its device (device path, current stream unless given)."""
+    _destroy = "gfdm_hip_burst_sync_destroy"
+
+    def __init__(self, fft_len, cp_len, core_preamble, window_len, device=0):
+        p = _c64(core_preamble).ravel()
+        h = ctypes.c_void_p()
+        _check(lib().gfdm_hip_burst_sync_create(ctypes.byref(h), int(fft_len), int(cp_len), p.ctypes.data, p.size, int(window_len), device))
+        self._h = h
+        self._dev = int(device)
+
+    def fft_len(self):
+        return lib().gfdm_hip_burst_sync_fft_len(self._h)
+
+    def cp_len(self):
+        return lib().gfdm_hip_burst_sync_cp_len(self._h)
+
+    def window_len(self):
+        return lib().gfdm_hip_burst_sync_window_len(self._h)
+
+    def corr_len(self):
+        """ac / ic values per window: window_len - 2 fft_len"""
+        return lib().gfdm_hip_burst_sync_corr_len(self._h)
+
+    def _grid(self, samples, first, stride, n_windows):
+        n = samples.numel() if _is_tensor(samples) else np.asarray(samples).size
+        return n, int(first), self.window_len() if stride is None else int(stride), int(n_windows)
+
+    def find_frame_start(self, samples, first=0, stride=None, n_windows=1, stream=None):
+        """dict of per-window arrays: frame_start, coarse (stream indices, int64), cfo, metric (float32), sc_rot (complex64).
+        stride defaults to window_len (windows back to back)."""
+        L = lib()
+        n, first, stride, nw = self._grid(samples, first, stride, n_windows)
+        if _is_tensor(samples):
+            import torch
+            d = samples.device
+            r = {"frame_start": torch.empty(nw, dtype=torch.int64, device=d), "coarse": torch.empty(nw, dtype=torch.int64, device=d),
+                 "cfo": torch.empty(nw, dtype=torch.float32, device=d), "metric": torch.empty(nw, dtype=torch.float32, device=d),
+                 "sc_rot": torch.empty(nw, dtype=torch.complex64, device=d)}
+            _check(L.gfdm_hip_burst_sync_find_frame_start_device(self._h, *[r[k].data_ptr() for k in ("frame_start", "coarse", "cfo", "metric", "sc_rot")],
+                                                                 self._dp(samples, n, "samples"), n, first, stride, nw, self._sp(stream)))
+            return r
+        a = _c64(samples).ravel()
+        r = {"frame_start": np.empty(nw, np.int64), "coarse": np.empty(nw, np.int64), "cfo": np.empty(nw, np.float32),
+             "metric": np.empty(nw, np.float32), "sc_rot": np.empty(nw, np.complex64)}
+        _check(L.gfdm_hip_burst_sync_find_frame_start_host(self._h, *[r[k].ctypes.data for k in ("frame_start", "coarse", "cfo", "metric", "sc_rot")],
+                                                           a.ctypes.data, n, first, stride, nw))
+        return r
+
+    def auto_correlate(self, samples, first=0, stride=None, n_windows=1, stream=None):
+        """(ac, ic): [n_windows][corr_len] complex64 / float32 (pygfdm's auto_correlate_signal and abs_integrate)."""
+        L = lib()
+        n, first, stride, nw = self._grid(samples, first, stride, n_windows)
+        P = self.corr_len()
+        if _is_tensor(samples):
+            import torch
+            ac = torch.empty(nw, P, dtype=torch.complex64, device=samples.device)
+            ic = torch.empty(nw, P, dtype=torch.float32, device=samples.device)
+            _check(L.gfdm_hip_burst_sync_auto_correlate_device(self._h, ac.data_ptr(), ic.data_ptr(), self._dp(samples, n, "samples"), n, first, stride, nw,
+                                                               self._sp(stream)))
+            return ac, ic
+        a = _c64(samples).ravel()
+        ac = np.empty((nw, P), np.complex64)
+        ic = np.empty((nw, P), np.float32)
+        _check(L.gfdm_hip_burst_sync_auto_correlate_host(self._h, ac.ctypes.data, ic.ctypes.data, a.ctypes.data, n, first, stride, nw))
+        return ac, ic
+
+
+class BurstExtractor(_Kernel):
+    """extract_burst_cc (lib/extract_burst_cc_impl.cc:72-242): burst_len samples from each offset - tag_backoff, scaled and (with CFO
+    correction on) rotated by (conj(r) / |r|)^n; samples outside the stream read as zero.  numpy in -> numpy out (host path); torch
+    device tensors in (samples, offsets int64, scale float32, sc_rot complex64) -> torch out (device path)."""
+    _destroy = "gfdm_hip_burst_extractor_destroy"
+
+    def __init__(self, burst_len, tag_backoff=0, activate_cfo_correction=True, device=0):
+        h = ctypes.c_void_p()
+        _check(lib().gfdm_hip_burst_extractor_create(ctypes.byref(h), int(burst_len), int(tag_backoff), int(bool(activate_cfo_correction)), device))
+        self._h = h
+        self._dev = int(device)
+
+    def burst_len(self):
+        return lib().gfdm_hip_burst_extractor_burst_len(self._h)
+
+    def tag_backoff(self):
+        return lib().gfdm_hip_burst_extractor_tag_backoff(self._h)
+
+    def activate_cfo_compensation(self, activate):
+        _check(lib().gfdm_hip_burst_extractor_set_cfo_correction(self._h, int(bool(activate))))
+
+    set_cfo_correction = activate_cfo_compensation
+
+    def cfo_correction(self):
+        return bool(lib().gfdm_hip_burst_extractor_get_cfo_correction(self._h))
+
+    def extract(self, samples, offsets, scale=None, sc_rot=None, stream=None):
+        """[n][burst_len] bursts; offsets are tag positions in `samples` (the extractor subtracts tag_backoff)."""
+        L = lib()
+        B = self.burst_len()
+        if _is_tensor(samples):
+            import torch
+            n = offsets.numel()
+            out = torch.empty(n, B, dtype=torch.complex64, device=samples.device)
+            sp = None if scale is None else _dev_arg(scale, torch.float32, n, "scale", self._dev)
+            rp = None if sc_rot is None else _dev_arg(sc_rot, torch.complex64, n, "sc_rot", self._dev)
+            _check(L.gfdm_hip_burst_extractor_extract_device(self._h, out.data_ptr(), self._dp(samples, samples.numel(), "samples"), samples.numel(),
+                                                             _dev_arg(offsets, torch.int64, n, "offsets", self._dev), sp, rp, n, self._sp(stream)))
+            return out
+        a = _c64(samples).ravel()
+        off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+        n = off.size
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32).ravel()
+        rot = None if sc_rot is None else _c64(sc_rot).ravel()
+        for v, what in ((sc, "scale"), (rot, "sc_rot")):
+            if v is not None and v.size != n:
+                raise RuntimeError("%s has %d elements, expected %d" % (what, v.size, n))
+        out = np.empty((n, B), np.complex64)
+        _check(L.gfdm_hip_burst_extractor_extract_host(self._h, out.ctypes.data, a.ctypes.data, a.size, off.ctypes.data,
+                                                       None if sc is None else sc.ctypes.data, None if rot is None else rot.ctypes.data, n))
+        return out

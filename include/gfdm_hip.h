@@ -400,6 +400,62 @@ int gfdm_hip_cyclic_prefixer_add_device(gfdm_hip_cyclic_prefixer* c, void* out, 
 int gfdm_hip_cyclic_prefixer_remove_host(gfdm_hip_cyclic_prefixer* c, float* out, const float* in, int64_t nblocks);
 int gfdm_hip_cyclic_prefixer_remove_device(gfdm_hip_cyclic_prefixer* c, void* out, const void* in, int64_t nblocks, void* stream);
 
+/* ---- burst acquisition: timing / CFO synchronisation and burst extraction ------------------------------------------------------
+ * The two steps in front of the receivers above, on device-resident capture buffers: find each burst's core preamble and CFO, then
+ * cut the bursts out, scaled and CFO-corrected.  The synchroniser's outputs feed the extractor's device entry point as they are.
+ *
+ * gfdm_hip_burst_sync: pygfdm's find_frame_start(s, preamble, K, cp_len) (python/pygfdm/synchronization.py:154-263) on every window
+ * s = stream[start_b : start_b + W] of a regular grid start_b = first + b * stride, b < n_windows (W = window_len; a window running past
+ * stream_len is GFDM_HIP_EINVAL).  With p the core preamble scaled to unit average energy (initialize_sync_algorithm, :225-236):
+ *   ac[i]  = 2 sum_{n<K} conj(s[i+n]) s[i+n+K] / sum_{n<2K} |s[i+n]|^2      i < W - 2K   (auto_correlate_signal, :127-137)
+ *            DEVIATION: ac = 0 where the energy is 0; pygfdm yields NaN there
+ *   ic[n]  = mean(|ac|[n - cp_len .. n]) for n >= cp_len, else 0                          (abs_integrate, :146-151)
+ *   nm     = argmax(ic);  cfo = angle(ac[nm]) / 2 pi, in subcarrier spacings           (auto_correlation_sync, :154-163)
+ *   s'[n]  = s[n] exp(j pi cfo n / K): the correction pygfdm applies (:255 with :187-190).  It is not the physical one (half the rate,
+ *            opposite sign); it only changes |pcc| and is kept for parity.  It leaves 1.5x the CFO in the signal: beyond about
+ *            |cfo| = 0.3 the fine timing can lock to a +-K side peak of the two-half preamble, as pygfdm's does.
+ *   pcc[i] = sum_{n<2K} s'[i+n] conj(p[n]) / 2K;  nc = argmax(|pcc[i]| ic[i]) over i < W - 2K   (improved_cross_correlation_peak, :175-187)
+ *   every argmax takes the first index of equal values.
+ * Outputs per window: frame_start = start_b + nc (int64), coarse = start_b + nm (int64), cfo (float), metric = ic[nm] (float: a window
+ * without a burst has a low one), sc_rot = exp(j angle(ac[nm]) / K) (complex: the per-sample rotation present in the signal, in
+ * extract_burst_cc's tag convention).  Every position's sums are computed on their own (no running sums), in fp32.
+ * auto_correlate: the first stage alone, ac (complex) and ic (float), W - 2K values each per window (either may be NULL, not both).
+ * create: EINVAL for n_preamble != 2 fft_len, fft_len outside [2, 1024], cp_len < 0, window_len < 2 fft_len + cp_len + 1. */
+typedef struct gfdm_hip_burst_sync gfdm_hip_burst_sync;
+int gfdm_hip_burst_sync_create(gfdm_hip_burst_sync** out, int fft_len, int cp_len, const float* core_preamble, int n_preamble, int64_t window_len,
+                               int device);
+int gfdm_hip_burst_sync_destroy(gfdm_hip_burst_sync* s);
+int gfdm_hip_burst_sync_fft_len(const gfdm_hip_burst_sync* s);
+int gfdm_hip_burst_sync_cp_len(const gfdm_hip_burst_sync* s);
+int64_t gfdm_hip_burst_sync_window_len(const gfdm_hip_burst_sync* s);
+int64_t gfdm_hip_burst_sync_corr_len(const gfdm_hip_burst_sync* s);          /* window_len - 2 fft_len: ac / ic values per window */
+int gfdm_hip_burst_sync_find_frame_start_host(gfdm_hip_burst_sync* s, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                              const float* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows);
+int gfdm_hip_burst_sync_find_frame_start_device(gfdm_hip_burst_sync* s, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                                const void* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows, void* stream);
+int gfdm_hip_burst_sync_auto_correlate_host(gfdm_hip_burst_sync* s, float* ac, float* ic, const float* samples, int64_t stream_len, int64_t first,
+                                            int64_t stride, int64_t n_windows);
+int gfdm_hip_burst_sync_auto_correlate_device(gfdm_hip_burst_sync* s, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
+                                              int64_t stride, int64_t n_windows, void* stream);
+
+/* gfdm_hip_burst_extractor: extract_burst_cc (lib/extract_burst_cc_impl.cc:72-242) for n bursts given by their tag offsets:
+ *   out[b][n] = scale_b * s[off_b - tag_backoff + n] * (conj(r_b) / |r_b|)^n,   n < burst_len   (n counted from the burst start)
+ * scale NULL = 1; sc_rot (complex r_b) NULL, |r_b| = 0 or CFO correction off = no rotation.  Samples before 0 read as zero (the
+ * reference's prepend); samples at or after stream_len read as zero too -- an EXTENSION: the device entry point takes offsets,
+ * scale and sc_rot as device arrays (e.g. the synchroniser's outputs) and cannot check them on the host.  The phase of sample n is
+ * reduced in fp64: within 2e-5 of a float64 rotation for any burst_len. */
+typedef struct gfdm_hip_burst_extractor gfdm_hip_burst_extractor;
+int gfdm_hip_burst_extractor_create(gfdm_hip_burst_extractor** out, int burst_len, int tag_backoff, int activate_cfo_correction, int device);
+int gfdm_hip_burst_extractor_destroy(gfdm_hip_burst_extractor* e);
+int gfdm_hip_burst_extractor_burst_len(const gfdm_hip_burst_extractor* e);
+int gfdm_hip_burst_extractor_tag_backoff(const gfdm_hip_burst_extractor* e);
+int gfdm_hip_burst_extractor_set_cfo_correction(gfdm_hip_burst_extractor* e, int activate);   /* activate_cfo_compensation, :100-104 */
+int gfdm_hip_burst_extractor_get_cfo_correction(const gfdm_hip_burst_extractor* e);
+int gfdm_hip_burst_extractor_extract_host(gfdm_hip_burst_extractor* e, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
+                                          const float* scale, const float* sc_rot, int64_t n_bursts);
+int gfdm_hip_burst_extractor_extract_device(gfdm_hip_burst_extractor* e, void* out, const void* samples, int64_t stream_len, const void* offsets,
+                                            const void* scale, const void* sc_rot, int64_t n_bursts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Golden vectors for the burst synchroniser (gfdm_hip_burst_sync), produced with the reference's own Python model of it:
+
+    pygfdm.synchronization.auto_correlation_sync            (python/pygfdm/synchronization.py:157-166)
+    pygfdm.synchronization.find_frame_start                 (:239-263, which runs improved_cross_correlation_peak, :175-187)
+
+Each fixture holds one window of a stream: noise, plus (in most cases) a burst [cp | half | half | data] built from a
+pygfdm preamble (get_sync_symbol, as make_golden_est.py composes it) with a carrier frequency offset, a phase and a gain.
+The filter taps come from gfdm_amd.filters because pygfdm's need commpy (see make_golden.py for the import notes).
+
+Written to tests/golden/sync/ (conftest.golden_names() feeds every top-level *.npz to the receiver parity tests).
+Build container only (imports /root/reference/python/pygfdm).
+"""
+import contextlib
+import io
+import os
+import sys
+import types
+
+sys.dont_write_bytecode = True
+import numpy as np
+import scipy.signal as signal
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+OUT = os.path.join(HERE, "sync")
+np.complex = complex
+sys.modules.setdefault("commpy", types.ModuleType("commpy"))
+if not hasattr(signal, "gaussian"):
+    signal.gaussian = signal.windows.gaussian
+sys.path.insert(0, "/root/reference/python")
+sys.path.insert(0, os.path.join(ROOT, "gr-gfdm_amd", "python"))
+
+from pygfdm.mapping import get_subcarrier_map, map_to_waveform_resources       # noqa: E402
+from pygfdm.preamble import get_sync_symbol                                    # noqa: E402
+from pygfdm.synchronization import auto_correlation_sync, find_frame_start     # noqa: E402
+from pygfdm.utils import calculate_signal_energy, get_random_qpsk              # noqa: E402
+from gfdm_amd.filters import get_frequency_domain_filter                       # noqa: E402
+
+# name, K, cp_len, cfo (subcarrier spacings), snr_db, kind
+#   burst:     the window holds a whole burst, the core preamble `lead` samples after the window start
+#   cut:       the window starts inside the burst's cyclic prefix (its CP plateau is cut)
+#   noise:     noise only (frame_start means nothing there; only ac, ic and metric are compared)
+#   zeros:     the window starts with a run of K zeros (shorter than 2K: pygfdm yields no NaN)
+CASES = [
+    ("k32_cp32_cfo0", 32, 32, 0.0, 20.0, "burst"),
+    ("k32_cp32_cfo045", 32, 32, 0.45, 25.0, "burst"),
+    ("k64_cfo0_30db", 64, 32, 0.0, 30.0, "burst"),
+    ("k64_cfop02_20db", 64, 32, 0.2, 20.0, "burst"),
+    ("k64_cfom02_10db", 64, 32, -0.2, 10.0, "burst"),
+    ("k64_cfo045_25db", 64, 32, 0.45, 25.0, "burst"),
+    ("k128_cfom02_15db", 128, 64, -0.2, 15.0, "burst"),
+    ("k128_cfo045_30db", 128, 64, 0.45, 30.0, "burst"),
+    ("k256_cfop02_20db", 256, 128, 0.2, 20.0, "burst"),
+    ("k256_cfo0_10db", 256, 128, 0.0, 10.0, "burst"),
+    ("k64_cut_cfop02_20db", 64, 32, 0.2, 20.0, "cut"),
+    ("k64_noise", 64, 32, 0.0, 20.0, "noise"),
+    ("k64_zeros_cfom02_20db", 64, 32, -0.2, 20.0, "zeros"),
+]
+DATA_BLOCKS = 5          # data samples after the preamble: DATA_BLOCKS * K
+CONTEXT = 37             # stream samples before the window (the window starts at `first`, not at 0)
+
+
+def make_case(name, K, cp, cfo, snr_db, kind):
+    rng = np.random.default_rng(sum(map(ord, name)))
+    A = K - K // 4 if K > 32 else 24
+    smap = get_subcarrier_map(K, A, dc_free=True)
+    pn_sym = map_to_waveform_resources(get_random_qpsk(A, int(rng.integers(1 << 30))), A, K, smap)
+    H = get_frequency_domain_filter("rrc", 0.2, 2, K, 2)
+    H = H / np.sqrt(calculate_signal_energy(H) / 2.0)                          # generate_sync_symbol, preamble.py:128-132
+    full, core = get_sync_symbol(pn_sym, H, K, 2, cp, 0)                       # [cp | core (2K)]
+    data = (rng.standard_normal(DATA_BLOCKS * K) + 1j * rng.standard_normal(DATA_BLOCKS * K)) * np.sqrt(np.mean(np.abs(core) ** 2) / 2)
+    burst = np.concatenate((full, data))
+    W = cp + 2 * K + DATA_BLOCKS * K + 3 * K // 2
+    lead = {"burst": cp + 11, "cut": cp // 2, "noise": 0, "zeros": K + cp + 5}[kind]     # window start -> core preamble
+    n = CONTEXT + W + 64
+    gain = 0.5 + rng.random()
+    sigma = gain * np.sqrt(np.mean(np.abs(core) ** 2) / 10 ** (snr_db / 10) / 2)
+    s = sigma * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    core_at = CONTEXT + lead
+    if kind != "noise":
+        b0 = core_at - cp
+        phase = 2 * np.pi * rng.random()
+        rot = gain * np.exp(1j * (phase + 2 * np.pi * cfo / K * np.arange(burst.size)))
+        s[b0:b0 + burst.size] += burst * rot
+    if kind == "zeros":
+        s[CONTEXT:CONTEXT + K] = 0
+    s = s.astype(np.complex64)
+    win = s[CONTEXT:CONTEXT + W].astype(np.complex128)
+    with contextlib.redirect_stdout(io.StringIO()):
+        nm, cfo_est, ic, ac = auto_correlation_sync(win.copy(), K, cp)
+        nc, cfo2, ic2, ac2, napcc, apcc = find_frame_start(win.copy(), core.copy(), K, cp)
+    assert nm == np.argmax(ic2) and cfo2 == cfo_est and np.all(np.isfinite(ac))
+    top = np.sort(ic)[-2:]
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), K=K, cp_len=cp, window_len=W, first=CONTEXT, stream=s, preamble=core,
+                        kind=kind, applied_cfo=cfo, snr_db=snr_db, core_start=(CONTEXT + lead) if kind != "noise" else -1,
+                        ac=ac, ic=ic, nm=nm, cfo=cfo_est, nc=nc, napcc=napcc, apcc=apcc, ic_margin=top[1] - top[0])
+    print("%-24s K=%-4d cp=%-4d W=%-5d nm=%-5d nc=%-5d (core %s) cfo=%+.4f (applied %+.2f) margin %.2e" %
+          (name, K, cp, W, nm, nc, lead if kind != "noise" else "-", cfo_est, cfo, top[1] - top[0]))
+
+
+def main():
+    os.makedirs(OUT, exist_ok=True)
+    for case in CASES:
+        make_case(*case)
+
+
+if __name__ == "__main__":
+    main()
