@@ -3,7 +3,8 @@
 // Their outputs (frame starts, rotations) stay on the device and feed the extractor and the estimated receivers without a host
 // round trip.  The contracts are written out in include/gfdm_hip.h.
 //
-// Synchroniser: the windows of one call lie on a regular grid (first, stride, n_windows), so every argument is checked on the host.
+// Synchroniser: the windows of one call lie on a regular grid (first, stride, n_windows), so every argument is checked on the host, or at
+// the starts of a device array (find_frame_start_at, and the detector's own list), which are clamped into the stream instead.
 // Four launches per find_frame_start, every one a grid of (correlation tiles x windows):
 //   k_sync_ic       |ac| over the tile and its cp_len halo, ic of the tile, first-index argmax of ic     -> key in coarse[w]
 //   k_sync_coarse   one wave per window: ac[nm] again, cfo, metric, sc_rot
@@ -15,6 +16,8 @@
 // of 2K products, every ic its own serial sum of cp_len + 1 magnitudes in ascending order: no running sums (fp32 drift over a long
 // window would move the argmax) and bit-equal values however a window is tiled or batched.  ic is recomputed in k_sync_fine rather
 // than stored: about 1.5x the work of the correlation alone, against an n_windows-sized buffer the caller would have to provide.
+//
+// Detector: the windows' starts found on the device (k_detect_scan, k_detect_offsets, k_detect_scatter; described above them).
 //
 // Extractor: out[b][n] = scale_b s[off_b - backoff + n] (conj(r_b) / |r_b|)^n, samples outside [0, stream_len) read as zero.  The
 // phase of sample n is reduced in fp64 (n angle(r) mod 2 pi) and only then rounded to fp32 for sincos, so the rotation error does
@@ -146,11 +149,24 @@ __device__ float tile_ic(const cf* __restrict__ win, int W, int K, int cp, int P
 }
 
 struct SyncArgs {
-    const cf* samples;       // window w starts at samples[first + w stride]
+    const cf* samples;       // window w starts at samples[first + w stride], or at starts[w] when a start array is given
     int64_t first, stride, nwin;
     int64_t origin;          // stream index of samples[0] (host path: the uploaded span starts inside the caller's stream)
     int W, K, cp, P;
+    const int64_t* starts;   // optional (device): window w starts at clamp(starts[w], 0, last)
+    int64_t nstarts, last;   // entries of starts (windows beyond are empty), stream_len - W
+    int skip_empty;          // the detector's lists: a negative start marks an empty slot (else it is clamped to 0)
 };
+
+// start of window w in samples, or -1 for an empty slot (only with a start array)
+__device__ __forceinline__ int64_t window_start(const SyncArgs& a, int64_t w)
+{
+    if (!a.starts) return a.first + w * a.stride;
+    if (w >= a.nstarts) return -1;
+    const int64_t st = a.starts[w];
+    if (st < 0 && a.skip_empty) return -1;
+    return std::min(std::max(st, (int64_t)0), a.last);
+}
 
 // dynamic LDS: xs [kTile + 2K] (+ q [2K] in the fine stage) complex, then mag [kTile]
 __global__ __launch_bounds__(kTile) void k_sync_ic(SyncArgs a, cf* __restrict__ ac_out, float* __restrict__ ic_out, unsigned long long* __restrict__ key)
@@ -160,8 +176,10 @@ __global__ __launch_bounds__(kTile) void k_sync_ic(SyncArgs a, cf* __restrict__ 
     float* mag = reinterpret_cast<float*>(xs + kTile + 2 * a.K);
     const int i0 = blockIdx.x * kTile, n = i0 + threadIdx.x;
     for (int64_t w = blockIdx.y; w < a.nwin; w += gridDim.y) {
+        const int64_t st = window_start(a, w);
+        if (st < 0) continue;       // empty slot: the key stays 0
         cf acn;
-        const float ic = tile_ic(a.samples + a.first + w * a.stride, a.W, a.K, a.cp, a.P, i0, xs, mag, &acn);
+        const float ic = tile_ic(a.samples + st, a.W, a.K, a.cp, a.P, i0, xs, mag, &acn);
         if (n < a.P) {
             if (ac_out) ac_out[w * a.P + n] = acn;
             if (ic_out) ic_out[w * a.P + n] = ic;
@@ -176,8 +194,15 @@ __global__ __launch_bounds__(64) void k_sync_coarse(SyncArgs a, const unsigned l
 {
     for (int64_t w = blockIdx.x; w < a.nwin; w += gridDim.x) {
         if (threadIdx.x != 0) continue;
+        const int64_t st = window_start(a, w);
+        if (st < 0) {
+            cfo[w] = 0.f;
+            metric[w] = 0.f;
+            sc_rot[w] = czero();
+            continue;
+        }
         const unsigned long long k = key[w];
-        const cf c = ac_at(a.samples + a.first + w * a.stride + key_index(k), a.K);
+        const cf c = ac_at(a.samples + st + key_index(k), a.K);
         const float ang = atan2f(c.y, c.x);
         cfo[w] = ang * (float)(0.5 / M_PI);
         metric[w] = key_value(k);
@@ -199,6 +224,8 @@ __global__ __launch_bounds__(kTile) void k_sync_fine(SyncArgs a, const cf* __res
     const int K2 = 2 * a.K;
     const int i0 = blockIdx.x * kTile, n = i0 + threadIdx.x;
     for (int64_t w = blockIdx.y; w < a.nwin; w += gridDim.y) {
+        const int64_t st = window_start(a, w);
+        if (st < 0) continue;
         const float th = (float)M_PI * cfo[w] / (float)a.K;
         for (int m = threadIdx.x; m < K2; m += kTile) {
             float s, c;
@@ -207,7 +234,7 @@ __global__ __launch_bounds__(kTile) void k_sync_fine(SyncArgs a, const cf* __res
             q[m] = make_float2(p.x * c + p.y * s, p.x * s - p.y * c);
         }
         cf acn;
-        const float ic = tile_ic(a.samples + a.first + w * a.stride, a.W, a.K, a.cp, a.P, i0, xs, mag, &acn);   // syncs after q is written
+        const float ic = tile_ic(a.samples + st, a.W, a.K, a.cp, a.P, i0, xs, mag, &acn);   // syncs after q is written
         float score = 0.f;
         if (n < a.P) {
             float re = 0.f, im = 0.f;
@@ -228,7 +255,13 @@ __global__ void k_sync_finalize(SyncArgs a, int64_t* __restrict__ frame_start, i
 {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= a.nwin) return;
-    const int64_t start = a.origin + a.first + w * a.stride;
+    const int64_t st = window_start(a, w);
+    if (st < 0) {
+        frame_start[w] = -1;
+        coarse[w] = -1;
+        return;
+    }
+    const int64_t start = a.origin + st;
     frame_start[w] = start + key_index((unsigned long long)frame_start[w]);
     coarse[w] = start + key_index((unsigned long long)coarse[w]);
 }
@@ -269,6 +302,185 @@ __global__ __launch_bounds__(kTile) void k_extract(cf* __restrict__ out, const c
             gfdm::dft::st_stream(out, b * burst_len + n, x);
         }
         __syncthreads();
+    }
+}
+
+// ---- detector: every burst of a stream (contract in include/gfdm_hip.h) ----
+// One workgroup scans a tile of per * kTile positions of the whole stream taken as one window, segment by segment (kTile positions,
+// one per lane) from R positions before the tile to R positions after it.  Each segment's ic comes from tile_ic -- the values
+// auto_correlate yields, bit for bit; from a tile's second segment on, with cp <= kTile, the |ac| of the segment before is kept
+// instead of computed again (segment_ic) -- and lives in LDS only while the segment is being compared: its running maxima from both
+// ends (pre, suf) give every lane the maximum over the part of its +-R neighbourhood that falls into the segment in one read (a
+// part strictly inside a segment, which needs R < kTile - 1, is walked).  Per own position a lane keeps one float in LDS -- the
+// maximum to its left until its own segment arrives, its ic from then on -- and one "beaten" bit, so LDS is per * kTile floats
+// whatever R is and nothing is written per position: the stream is read (per kTile + 2 R + cp) / (per kTile) times, and a tile
+// writes its peak count and its peaks in ascending order (at most one per R + 1 positions).
+constexpr int kScanMaxPer = 16;          // positions per lane and tile (one bit each in `beaten`); 32 measured 14 % slower (LDS per tile halves the residency)
+constexpr int kScanTiles = 4096;         // per is chosen so that a long stream has about this many tiles
+
+struct ScanArgs {
+    const cf* samples;
+    int n, K, cp, P;         // stream_len, P = n - 2K positions
+    int R, per, cap;         // min_distance, segments per tile, list entries per tile
+    float thr;
+};
+
+// max of ic over the global positions [a, b] (inside the segment that starts at g)
+__device__ __forceinline__ float seg_range_max(const float* icv, const float* pre, const float* suf, int g, int a, int b)
+{
+    if (a == g) return pre[b - g];
+    if (b == g + kTile - 1) return suf[a - g];
+    float m = icv[a - g];
+    for (int j = a + 1; j <= b; ++j) m = fmaxf(m, icv[j - g]);
+    return m;
+}
+
+size_t scan_lds(int K, int per) { return (size_t)(kTile + 2 * K) * sizeof(cf) + (size_t)(5 + per) * kTile * sizeof(float); }
+
+// tile_ic for the segment at g (>= kTile) of a walk in ascending order with cp <= kTile: magp holds |ac| of the segment before, as
+// tile_ic left it, so only this segment's |ac| is computed (into magc).  The lane's sum runs over the same magnitudes in the same
+// ascending order as tile_ic's: the value is bit-equal.
+__device__ float segment_ic(const cf* __restrict__ win, int W, int K, int cp, int P, int g, cf* xs, const float* magp, float* magc)
+{
+    const int t = threadIdx.x, n = g + t;
+    for (int j = t; j < kTile + 2 * K - 1; j += kTile) xs[j] = (g + j < W) ? win[g + j] : czero();
+    __syncthreads();
+    cf c = czero();
+    if (n < P) c = ac_at(xs + t, K);
+    magc[t] = sqrtf(c.x * c.x + c.y * c.y);
+    __syncthreads();
+    if (n < cp || n >= P) return 0.f;
+    float acc = 0.f;
+    for (int j = n - cp; j < g; ++j) acc += magp[j - g + kTile];
+    for (int j = std::max(g, n - cp); j <= n; ++j) acc += magc[j - g];
+    return acc / (float)(cp + 1);
+}
+
+// dynamic LDS: xs [kTile + 2K] complex, mag [2][kTile], icv, pre, suf [kTile] float, own [per][kTile] float
+__global__ __launch_bounds__(kTile) void k_detect_scan(ScanArgs a, int* __restrict__ counts, int* __restrict__ list)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    cf* xs = reinterpret_cast<cf*>(smem_raw);
+    float* mag = reinterpret_cast<float*>(xs + kTile + 2 * a.K);
+    float* icv = mag + 2 * kTile;
+    float* pre = icv + kTile;
+    float* suf = pre + kTile;
+    float* own = suf + kTile + threadIdx.x;             // own[r * kTile]: this lane's position of segment r; no other lane touches it
+    __shared__ float wmax[kTile / 32];
+    __shared__ int wcnt[kTile / 32];
+    const int t = threadIdx.x, lane = t & (warpSize - 1), wave = t / warpSize, nwave = kTile / warpSize;
+    const int c0 = blockIdx.x * a.per * kTile;
+    const int hs = (a.R + kTile - 1) / kTile;           // halo segments on either side
+    unsigned beaten = 0;                                // bit r: an ic at least as large within R before, or larger within R after
+    for (int r = 0; r < a.per; ++r) own[r * kTile] = -1.f;
+
+    // the neighbourhoods are cut at the stream ends: segments inside [0, P) only
+    const int s_lo = std::max(-hs, -(c0 / kTile)), s_hi = std::min(a.per + hs, (a.P - c0 + kTile - 1) / kTile);
+    for (int s = s_lo; s < s_hi; ++s) {
+        const int g = c0 + s * kTile;
+        float* magc = mag + (s & 1) * kTile;            // this segment's |ac|; the other half holds the segment's before
+        float ic;
+        if (s > s_lo && a.cp <= kTile) {
+            ic = segment_ic(a.samples, a.n, a.K, a.cp, a.P, g, xs, mag + ((s & 1) ^ 1) * kTile, magc);
+        } else {
+            cf acn;
+            ic = tile_ic(a.samples, a.n, a.K, a.cp, a.P, g, xs, magc, &acn);
+        }
+        const float val = (g + t < a.P) ? ic : -1.f;
+        // running maxima from both ends: inside a wave by shuffles, across waves through wmax
+        float p = val, q = val;
+        for (int o = 1; o < warpSize; o <<= 1) {
+            const float x = __shfl_up(p, o), y = __shfl_down(q, o);
+            if (lane >= o) p = fmaxf(p, x);
+            if (lane + o < warpSize) q = fmaxf(q, y);
+        }
+        if (lane == 0) wmax[wave] = q;
+        icv[t] = val;
+        __syncthreads();
+        for (int w = 0; w < nwave; ++w) {
+            const float m = wmax[w];
+            if (w < wave) p = fmaxf(p, m);
+            if (w > wave) q = fmaxf(q, m);
+        }
+        pre[t] = p;
+        suf[t] = q;
+        __syncthreads();
+        for (int r = std::max(0, s - hs); r <= std::min(a.per - 1, s + hs); ++r) {
+            const int n = c0 + r * kTile + t;
+            float* slot = own + r * kTile;
+            if (r >= s) {                                               // positions before n
+                const int lo = std::max(g, n - a.R), hi = std::min(g + kTile - 1, n - 1);
+                float m = *slot;
+                if (lo <= hi) m = fmaxf(m, seg_range_max(icv, pre, suf, g, lo, hi));
+                if (r == s) {                                           // the left side is complete: judge it, keep the own ic from here on
+                    if (m >= val) beaten |= 1u << r;
+                    m = val;
+                }
+                *slot = m;
+            }
+            if (r <= s) {                                               // positions after n
+                const int lo = std::max(g, n + 1), hi = std::min(g + kTile - 1, n + a.R);
+                if (lo <= hi && seg_range_max(icv, pre, suf, g, lo, hi) > *slot) beaten |= 1u << r;
+            }
+        }
+        __syncthreads();                                                // icv, pre, suf are rewritten for the next segment
+    }
+
+    // ordered compaction inside the tile: position order is r-major, lane-minor
+    int base = 0;
+    int* mine = list + (int64_t)blockIdx.x * a.cap;
+    for (int r = 0; r < a.per && c0 + r * kTile < a.P; ++r) {           // (a segment at or past P was never scanned: its slot holds no ic)
+        const bool peak = own[r * kTile] >= a.thr && !((beaten >> r) & 1u);
+        const unsigned long long b = __ballot(peak);
+        if (lane == 0) wcnt[wave] = __popcll(b);
+        __syncthreads();
+        int k = base + __popcll(b & ((1ull << lane) - 1ull));
+        for (int w = 0; w < nwave; ++w) {
+            if (w < wave) k += wcnt[w];
+            base += wcnt[w];
+        }
+        if (peak && k < a.cap) mine[k] = c0 + r * kTile + t;
+        __syncthreads();
+    }
+    if (t == 0) counts[blockIdx.x] = base;
+}
+
+// exclusive scan of the tiles' counts (one workgroup; a tile count is tiny against the scan itself), total -> *count
+__global__ __launch_bounds__(kTile) void k_detect_offsets(const int* __restrict__ counts, int* __restrict__ offs, int ntiles, int64_t* __restrict__ count)
+{
+    __shared__ int wsum[kTile / 32];
+    const int t = threadIdx.x, lane = t & (warpSize - 1), wave = t / warpSize, nwave = kTile / warpSize;
+    int base = 0;
+    for (int i0 = 0; i0 < ntiles; i0 += kTile) {
+        const int i = i0 + t, c = i < ntiles ? counts[i] : 0;
+        int incl = c;
+        for (int o = 1; o < warpSize; o <<= 1) {
+            const int x = __shfl_up(incl, o);
+            if (lane >= o) incl += x;
+        }
+        if (lane == warpSize - 1) wsum[wave] = incl;
+        __syncthreads();
+        int excl = base + incl - c;
+        for (int w = 0; w < nwave; ++w) {
+            if (w < wave) excl += wsum[w];
+            base += wsum[w];
+        }
+        if (i < ntiles) offs[i] = excl;
+        __syncthreads();
+    }
+    if (t == 0) *count = base;
+}
+
+// starts[slot] = clamp(peak - lead, 0, last) for the lowest nslots peaks (the rest of starts was preset to -1)
+__global__ __launch_bounds__(kTile) void k_detect_scatter(const int* __restrict__ counts, const int* __restrict__ offs, const int* __restrict__ list, int cap,
+                                                          int ntiles, int lead, int64_t last, int64_t* __restrict__ starts, int64_t nslots)
+{
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int c = std::min(counts[tile], cap), o = offs[tile];
+        for (int k = threadIdx.x; k < c; k += kTile) {
+            const int64_t slot = (int64_t)o + k;
+            if (slot < nslots) starts[slot] = std::min(std::max((int64_t)list[(int64_t)tile * cap + k] - lead, (int64_t)0), last);
+        }
     }
 }
 
@@ -329,10 +541,21 @@ int check_windows(const gfdm_hip_burst_sync* h, const void* samples, int64_t str
 }
 
 // enqueue the synchroniser; fused (frame_start != NULL) or the auto-correlation stage (ac / ic)
-int sync_enqueue(gfdm_hip_burst_sync* h, const cf* samples, int64_t first, int64_t stride, int64_t n, int64_t origin, int64_t* frame_start, int64_t* coarse,
-                 float* cfo, float* metric, cf* sc_rot, cf* ac, float* ic, hipStream_t s)
+SyncArgs grid_args(const gfdm_hip_burst_sync* h, const cf* samples, int64_t first, int64_t stride, int64_t n, int64_t origin)
 {
-    const SyncArgs a = { samples, first, stride, n, origin, h->W, h->K, h->cp, h->W - 2 * h->K };
+    return SyncArgs{ samples, first, stride, n, origin, h->W, h->K, h->cp, h->W - 2 * h->K, nullptr, 0, 0, 0 };
+}
+
+// windows at starts[w] (device array of nstarts entries; windows w >= nstarts are empty), clamped to [0, stream_len - W]
+SyncArgs list_args(const gfdm_hip_burst_sync* h, const cf* samples, int64_t stream_len, const int64_t* starts, int64_t nstarts, int64_t n, int skip_empty)
+{
+    return SyncArgs{ samples, 0, 0, n, 0, h->W, h->K, h->cp, h->W - 2 * h->K, starts, nstarts, stream_len - h->W, skip_empty };
+}
+
+int sync_enqueue(gfdm_hip_burst_sync* h, const SyncArgs& a, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, cf* sc_rot, cf* ac, float* ic,
+                 hipStream_t s)
+{
+    const int64_t n = a.nwin;
     const dim3 grid((unsigned)((a.P + kTile - 1) / kTile), (unsigned)std::min<int64_t>(n, kMaxGridY));
     if (!frame_start) {
         hipLaunchKernelGGL(k_sync_ic, grid, dim3(kTile), sync_lds(h->K, false), s, a, ac, ic, (unsigned long long*)nullptr);
@@ -373,7 +596,7 @@ int sync_host(gfdm_hip_burst_sync* h, const float* samples, int64_t first, int64
         cf* d_rot = reinterpret_cast<cf*>(d_co + n);
         float* d_cfo = reinterpret_cast<float*>(d_rot + n);
         float* d_met = d_cfo + n;
-        rc = sync_enqueue(h, static_cast<const cf*>(d_in.p), 0, stride, n, first, d_fs, d_co, d_cfo, d_met, d_rot, nullptr, nullptr, h->stream);
+        rc = sync_enqueue(h, grid_args(h, static_cast<const cf*>(d_in.p), 0, stride, n, first), d_fs, d_co, d_cfo, d_met, d_rot, nullptr, nullptr, h->stream);
         if (rc != GFDM_HIP_OK) return rc;
         BURST_TRY(hipMemcpyAsync(frame_start, d_fs, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
         BURST_TRY(hipMemcpyAsync(coarse, d_co, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -383,13 +606,122 @@ int sync_host(gfdm_hip_burst_sync* h, const float* samples, int64_t first, int64
     } else {
         cf* d_ac = reinterpret_cast<cf*>(o);
         float* d_ic = reinterpret_cast<float*>(d_ac + (size_t)n * P);
-        rc = sync_enqueue(h, static_cast<const cf*>(d_in.p), 0, stride, n, first, nullptr, nullptr, nullptr, nullptr, nullptr, d_ac, d_ic, h->stream);
+        rc = sync_enqueue(h, grid_args(h, static_cast<const cf*>(d_in.p), 0, stride, n, first), nullptr, nullptr, nullptr, nullptr, nullptr, d_ac, d_ic, h->stream);
         if (rc != GFDM_HIP_OK) return rc;
         if (ac) BURST_TRY(hipMemcpyAsync(ac, d_ac, (size_t)n * P * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
         if (ic) BURST_TRY(hipMemcpyAsync(ic, d_ic, (size_t)n * P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     }
     BURST_TRY(hipStreamSynchronize(h->stream));
     return GFDM_HIP_OK;
+}
+
+// ---- host side of find_frame_start_at and detect ----
+struct SyncOut { int64_t* frame_start; int64_t* coarse; float* cfo; float* metric; cf* sc_rot; };
+
+// the five per-window outputs of n windows in one device buffer (int64 first: alignment)
+SyncOut carve_out(void* p, int64_t n)
+{
+    SyncOut o;
+    o.frame_start = static_cast<int64_t*>(p);
+    o.coarse = o.frame_start + n;
+    o.sc_rot = reinterpret_cast<cf*>(o.coarse + n);
+    o.cfo = reinterpret_cast<float*>(o.sc_rot + n);
+    o.metric = o.cfo + n;
+    return o;
+}
+size_t out_bytes(int64_t n) { return (size_t)n * (2 * sizeof(int64_t) + 2 * sizeof(float) + sizeof(cf)); }
+
+int fetch_out(const SyncOut& d, int64_t n, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot, hipStream_t s)
+{
+    BURST_TRY(hipMemcpyAsync(frame_start, d.frame_start, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    BURST_TRY(hipMemcpyAsync(coarse, d.coarse, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    BURST_TRY(hipMemcpyAsync(sc_rot, d.sc_rot, (size_t)n * sizeof(cf), hipMemcpyDeviceToHost, s));
+    BURST_TRY(hipMemcpyAsync(cfo, d.cfo, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    BURST_TRY(hipMemcpyAsync(metric, d.metric, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    return GFDM_HIP_OK;
+}
+
+int check_at(const gfdm_hip_burst_sync* h, const void* samples, int64_t stream_len, const void* starts, int64_t n)
+{
+    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
+    if (n < 0) return api_fail(GFDM_HIP_EINVAL, "negative window count");
+    if (stream_len < h->W) return api_fail(GFDM_HIP_EINVAL, "stream_len is shorter than window_len");
+    if (n > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "more than 2^31 windows in one call");
+    if (n > 0 && (!samples || !starts)) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
+    return GFDM_HIP_OK;
+}
+
+constexpr int64_t kMaxDetectLen = (int64_t)1 << 29;      // the scan indexes positions (and positions + R) in 32 bits
+constexpr int64_t kMaxDetectDistance = (int64_t)1 << 16; // a tile walks 2 ceil(R / kTile) halo segments: the scan's cost grows with R
+
+// the detector's argument table (include/gfdm_hip.h); needs no handle, so it is checked before any device is touched
+int detect_check(int K, int cp, int64_t W, int64_t stream_len, float threshold, int64_t R, int64_t lead, int64_t max_bursts)
+{
+    char buf[200];
+    if (K < 2 || K > kMaxK || cp < 0 || W < (int64_t)2 * K + cp + 1) return api_fail(GFDM_HIP_EINVAL, "fft_len, cp_len or window_len outside the synchroniser's range");
+    if (!(threshold > 0.f)) return api_fail(GFDM_HIP_EINVAL, "threshold must be > 0");
+    if (max_bursts < 0) return api_fail(GFDM_HIP_EINVAL, "max_bursts must be >= 0");
+    if (lead < cp || lead > R) {
+        snprintf(buf, sizeof(buf), "lead(%lld) must lie in [cp_len(%d), min_distance(%lld)]", (long long)lead, cp, (long long)R);
+        return api_fail(GFDM_HIP_EINVAL, buf);
+    }
+    if (W - 2 * K - lead - 1 > R) {
+        snprintf(buf, sizeof(buf), "min_distance(%lld) must be at least window_len - 2 fft_len - lead - 1 (%lld)", (long long)R, (long long)(W - 2 * K - lead - 1));
+        return api_fail(GFDM_HIP_EINVAL, buf);
+    }
+    if (R > kMaxDetectDistance) return api_fail(GFDM_HIP_EINVAL, "min_distance above 2^16 (the scan's work grows with it)");
+    if (stream_len < W) return api_fail(GFDM_HIP_EINVAL, "stream_len is shorter than window_len");
+    if (stream_len > kMaxDetectLen) return api_fail(GFDM_HIP_EINVAL, "stream_len above 2^29 (split the capture into overlapping spans)");
+    return GFDM_HIP_OK;
+}
+
+// tiling of the scan and layout of the workspace; depends on the handle and stream_len only (not on min_distance: the smallest
+// one detect accepts, (W - 2K - 1) / 2, bounds the peaks per tile and per stream)
+struct DetectGeom {
+    int per, ntiles, cap;
+    int64_t nstarts;
+    size_t o_offs, o_list, o_starts, bytes;      // counts at 0
+};
+DetectGeom detect_geom(const gfdm_hip_burst_sync* h, int64_t stream_len)
+{
+    DetectGeom g;
+    const int64_t P = stream_len - 2 * h->K, rmin = (h->W - 2 * h->K - 1) / 2;
+    g.per = (int)std::min<int64_t>(kScanMaxPer, std::max<int64_t>(4, (P + (int64_t)kTile * kScanTiles - 1) / ((int64_t)kTile * kScanTiles)));
+    const int64_t tile = (int64_t)g.per * kTile;
+    g.ntiles = (int)((P + tile - 1) / tile);
+    g.cap = (int)(tile / (rmin + 1) + 1);
+    g.nstarts = P / (rmin + 1) + 1;
+    auto up = [](size_t b) { return (b + 15) / 16 * 16; };
+    g.o_offs = up((size_t)g.ntiles * sizeof(int));
+    g.o_list = g.o_offs + up((size_t)g.ntiles * sizeof(int));
+    g.o_starts = g.o_list + up((size_t)g.ntiles * g.cap * sizeof(int));
+    g.bytes = g.o_starts + (size_t)g.nstarts * sizeof(int64_t);
+    return g;
+}
+
+// scan -> ordered compaction -> fine stage over the window starts; count and the five outputs are device pointers
+int detect_enqueue(gfdm_hip_burst_sync* h, int64_t* count, const SyncOut& o, const cf* samples, int64_t stream_len, float threshold, int64_t R, int64_t lead,
+                   int64_t max_bursts, void* workspace, hipStream_t s)
+{
+    const DetectGeom g = detect_geom(h, stream_len);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    int* counts = reinterpret_cast<int*>(ws);
+    int* offs = reinterpret_cast<int*>(ws + g.o_offs);
+    int* list = reinterpret_cast<int*>(ws + g.o_list);
+    int64_t* starts = reinterpret_cast<int64_t*>(ws + g.o_starts);
+    const int P = (int)(stream_len - 2 * h->K);
+    const ScanArgs a = { samples, (int)stream_len, h->K, h->cp, P, (int)std::min<int64_t>(R, P), g.per, g.cap, threshold };
+    hipLaunchKernelGGL(k_detect_scan, dim3((unsigned)g.ntiles), dim3(kTile), scan_lds(h->K, g.per), s, a, counts, list);
+    BURST_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_detect_offsets, dim3(1), dim3(kTile), 0, s, (const int*)counts, offs, g.ntiles, count);
+    BURST_TRY(hipGetLastError());
+    if (max_bursts == 0) return GFDM_HIP_OK;
+    const int64_t nslots = std::min(max_bursts, g.nstarts);
+    BURST_TRY(hipMemsetAsync(starts, 0xFF, (size_t)nslots * sizeof(int64_t), s));          // -1: empty slot
+    hipLaunchKernelGGL(k_detect_scatter, dim3((unsigned)std::min(g.ntiles, 1024)), dim3(kTile), 0, s, (const int*)counts, (const int*)offs, (const int*)list, g.cap,
+                       g.ntiles, (int)lead, stream_len - h->W, starts, nslots);
+    BURST_TRY(hipGetLastError());
+    return sync_enqueue(h, list_args(h, samples, stream_len, starts, nslots, max_bursts, 1), o.frame_start, o.coarse, o.cfo, o.metric, o.sc_rot, nullptr, nullptr, s);
 }
 
 int extract_check(const gfdm_hip_burst_extractor* h, const void* out, const void* samples, int64_t stream_len, const void* offsets, int64_t n)
@@ -471,8 +803,9 @@ int gfdm_hip_burst_sync_find_frame_start_device(gfdm_hip_burst_sync* h, void* fr
     if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
     DeviceGuard guard(h->device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, static_cast<const cf*>(samples), first, stride, n_windows, 0, static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse),
-                        static_cast<float*>(cfo), static_cast<float*>(metric), static_cast<cf*>(sc_rot), nullptr, nullptr, (hipStream_t)stream);
+    return sync_enqueue(h, grid_args(h, static_cast<const cf*>(samples), first, stride, n_windows, 0), static_cast<int64_t*>(frame_start),
+                        static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric), static_cast<cf*>(sc_rot), nullptr, nullptr,
+                        (hipStream_t)stream);
 }
 
 int gfdm_hip_burst_sync_find_frame_start_host(gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
@@ -492,8 +825,8 @@ int gfdm_hip_burst_sync_auto_correlate_device(gfdm_hip_burst_sync* h, void* ac, 
     if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
     DeviceGuard guard(h->device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, static_cast<const cf*>(samples), first, stride, n_windows, 0, nullptr, nullptr, nullptr, nullptr, nullptr, static_cast<cf*>(ac),
-                        static_cast<float*>(ic), (hipStream_t)stream);
+    return sync_enqueue(h, grid_args(h, static_cast<const cf*>(samples), first, stride, n_windows, 0), nullptr, nullptr, nullptr, nullptr, nullptr,
+                        static_cast<cf*>(ac), static_cast<float*>(ic), (hipStream_t)stream);
 }
 
 int gfdm_hip_burst_sync_auto_correlate_host(gfdm_hip_burst_sync* h, float* ac, float* ic, const float* samples, int64_t stream_len, int64_t first,
@@ -503,6 +836,107 @@ int gfdm_hip_burst_sync_auto_correlate_host(gfdm_hip_burst_sync* h, float* ac, f
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
     return sync_host(h, samples, first, stride, n_windows, nullptr, nullptr, nullptr, nullptr, nullptr, ac, ic);
+}
+
+/* windows at arbitrary starts: the regular-grid kernels with a start array (bit-equal results per window) */
+int gfdm_hip_burst_sync_find_frame_start_at_device(gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                                   const void* samples, int64_t stream_len, const void* starts, int64_t n_windows, void* stream)
+{
+    int rc = check_at(h, samples, stream_len, starts, n_windows);
+    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
+    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    return sync_enqueue(h, list_args(h, static_cast<const cf*>(samples), stream_len, static_cast<const int64_t*>(starts), n_windows, n_windows, 0),
+                        static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric),
+                        static_cast<cf*>(sc_rot), nullptr, nullptr, (hipStream_t)stream);
+}
+
+int gfdm_hip_burst_sync_find_frame_start_at_host(gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                                 const float* samples, int64_t stream_len, const int64_t* starts, int64_t n_windows)
+{
+    int rc = check_at(h, samples, stream_len, starts, n_windows);
+    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
+    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const int64_t n = n_windows;
+    DevBuf d_in, d_st, d_out;
+    BURST_TRY(d_in.alloc((size_t)stream_len * sizeof(cf)));
+    BURST_TRY(d_st.alloc((size_t)n * sizeof(int64_t)));
+    BURST_TRY(d_out.alloc(out_bytes(n)));
+    BURST_TRY(hipMemcpyAsync(d_in.p, samples, (size_t)stream_len * sizeof(cf), hipMemcpyHostToDevice, h->stream));
+    BURST_TRY(hipMemcpyAsync(d_st.p, starts, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    const SyncOut o = carve_out(d_out.p, n);
+    rc = sync_enqueue(h, list_args(h, static_cast<const cf*>(d_in.p), stream_len, static_cast<const int64_t*>(d_st.p), n, n, 0), o.frame_start, o.coarse, o.cfo,
+                      o.metric, o.sc_rot, nullptr, nullptr, h->stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    rc = fetch_out(o, n, frame_start, coarse, cfo, metric, sc_rot, h->stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    BURST_TRY(hipStreamSynchronize(h->stream));
+    return GFDM_HIP_OK;
+}
+
+int gfdm_hip_burst_sync_detect_check(int fft_len, int cp_len, int64_t window_len, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead,
+                                     int64_t max_bursts)
+{
+    return detect_check(fft_len, cp_len, window_len, stream_len, threshold, min_distance, lead, max_bursts);
+}
+
+int64_t gfdm_hip_burst_sync_detect_workspace_bytes(const gfdm_hip_burst_sync* h, int64_t stream_len)
+{
+    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
+    if (stream_len < h->W) return api_fail(GFDM_HIP_EINVAL, "stream_len is shorter than window_len");
+    if (stream_len > kMaxDetectLen) return api_fail(GFDM_HIP_EINVAL, "stream_len above 2^29 (split the capture into overlapping spans)");
+    return (int64_t)detect_geom(h, stream_len).bytes;
+}
+
+int gfdm_hip_burst_sync_detect_device(gfdm_hip_burst_sync* h, void* count, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                      const void* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts,
+                                      void* workspace, void* stream)
+{
+    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
+    int rc = detect_check(h->K, h->cp, h->W, stream_len, threshold, min_distance, lead, max_bursts);
+    if (rc != GFDM_HIP_OK) return rc;
+    if (!samples || !count || !workspace) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
+    if (max_bursts > 0 && (!frame_start || !coarse || !cfo || !metric || !sc_rot)) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const SyncOut o = { static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric),
+                        static_cast<cf*>(sc_rot) };
+    return detect_enqueue(h, static_cast<int64_t*>(count), o, static_cast<const cf*>(samples), stream_len, threshold, min_distance, lead, max_bursts, workspace,
+                          (hipStream_t)stream);
+}
+
+int gfdm_hip_burst_sync_detect_host(gfdm_hip_burst_sync* h, int64_t* count, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                    const float* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts)
+{
+    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
+    int rc = detect_check(h->K, h->cp, h->W, stream_len, threshold, min_distance, lead, max_bursts);
+    if (rc != GFDM_HIP_OK) return rc;
+    if (!samples || !count) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
+    if (max_bursts > 0 && (!frame_start || !coarse || !cfo || !metric || !sc_rot)) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const int64_t n = max_bursts;
+    DevBuf d_in, d_ws, d_out, d_count;
+    BURST_TRY(d_in.alloc((size_t)stream_len * sizeof(cf)));
+    BURST_TRY(d_ws.alloc(detect_geom(h, stream_len).bytes));
+    BURST_TRY(d_out.alloc(out_bytes(n)));
+    BURST_TRY(d_count.alloc(sizeof(int64_t)));
+    BURST_TRY(hipMemcpyAsync(d_in.p, samples, (size_t)stream_len * sizeof(cf), hipMemcpyHostToDevice, h->stream));
+    const SyncOut o = carve_out(d_out.p, n);
+    rc = detect_enqueue(h, static_cast<int64_t*>(d_count.p), o, static_cast<const cf*>(d_in.p), stream_len, threshold, min_distance, lead, n, d_ws.p, h->stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    BURST_TRY(hipMemcpyAsync(count, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    if (n > 0) {
+        rc = fetch_out(o, n, frame_start, coarse, cfo, metric, sc_rot, h->stream);
+        if (rc != GFDM_HIP_OK) return rc;
+    }
+    BURST_TRY(hipStreamSynchronize(h->stream));
+    return GFDM_HIP_OK;
 }
 
 int gfdm_hip_burst_extractor_create(gfdm_hip_burst_extractor** out, int burst_len, int tag_backoff, int activate_cfo_correction, int device)

@@ -44,7 +44,7 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64, cp = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p
+    vp, i32, i64, cp, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_float
     sig = {
         "gfdm_hip_strerror": (cp, [i32]),
         "gfdm_hip_last_error": (cp, []),
@@ -177,6 +177,12 @@ def lib():
         "gfdm_hip_burst_sync_find_frame_start_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
         "gfdm_hip_burst_sync_auto_correlate_host": (i32, [vp, vp, vp, vp, i64, i64, i64, i64]),
         "gfdm_hip_burst_sync_auto_correlate_device": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
+        "gfdm_hip_burst_sync_find_frame_start_at_host": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64]),
+        "gfdm_hip_burst_sync_find_frame_start_at_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]),
+        "gfdm_hip_burst_sync_detect_check": (i32, [i32, i32, i64, i64, f32, i64, i64, i64]),
+        "gfdm_hip_burst_sync_detect_workspace_bytes": (i64, [vp, i64]),
+        "gfdm_hip_burst_sync_detect_host": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64]),
+        "gfdm_hip_burst_sync_detect_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64, vp, vp]),
         "gfdm_hip_burst_extractor_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, i32]),
         "gfdm_hip_burst_extractor_destroy": (i32, [vp]),
         "gfdm_hip_burst_extractor_burst_len": (i32, [vp]),
@@ -1021,6 +1027,14 @@ class ChannelEstimator(_Kernel):
         return snr, cnrs
 
 
+def threshold_factor(false_alarm_prob):
+    """pygfdm's calculate_threshold_factor (python/pygfdm/synchronization.py:239-243): sqrt(-(4 / pi) ln p), the detection threshold
+    relative to the noise level for a false-alarm probability p < 1."""
+    if not false_alarm_prob < 1.0:
+        raise ValueError("False alarm probability MUST be smaller 1.0!")
+    return float(np.sqrt(-(4 / np.pi) * np.log(false_alarm_prob)))
+
+
 def _dev_arg(t, dtype, n_elems, what, device):
     """device pointer of a contiguous torch tensor of `dtype` with n_elems elements on `device`"""
     if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
@@ -1081,6 +1095,67 @@ class BurstSync(_Kernel):
              "metric": np.empty(nw, np.float32), "sc_rot": np.empty(nw, np.complex64)}
         _check(L.gfdm_hip_burst_sync_find_frame_start_host(self._h, *[r[k].ctypes.data for k in ("frame_start", "coarse", "cfo", "metric", "sc_rot")],
                                                            a.ctypes.data, n, first, stride, nw))
+        return r
+
+    _OUT = ("frame_start", "coarse", "cfo", "metric", "sc_rot")
+
+    @staticmethod
+    def _outputs(n, device=None):
+        """the five per-window result arrays: torch tensors on `device`, numpy arrays without one"""
+        if device is None:
+            return {"frame_start": np.empty(n, np.int64), "coarse": np.empty(n, np.int64), "cfo": np.empty(n, np.float32),
+                    "metric": np.empty(n, np.float32), "sc_rot": np.empty(n, np.complex64)}
+        import torch
+        return {"frame_start": torch.empty(n, dtype=torch.int64, device=device), "coarse": torch.empty(n, dtype=torch.int64, device=device),
+                "cfo": torch.empty(n, dtype=torch.float32, device=device), "metric": torch.empty(n, dtype=torch.float32, device=device),
+                "sc_rot": torch.empty(n, dtype=torch.complex64, device=device)}
+
+    def find_frame_start_at(self, samples, starts, stream=None):
+        """find_frame_start on the windows samples[st : st + window_len], st = clamp(starts[w], 0, len(samples) - window_len): the same
+        dict, bit-equal per window to find_frame_start(first=st).  starts: int64 (a device tensor when samples is one)."""
+        L = lib()
+        if _is_tensor(samples):
+            import torch
+            n, nw = samples.numel(), starts.numel()
+            r = self._outputs(nw, samples.device)
+            _check(L.gfdm_hip_burst_sync_find_frame_start_at_device(self._h, *[r[k].data_ptr() for k in self._OUT], self._dp(samples, n, "samples"), n,
+                                                                    _dev_arg(starts, torch.int64, nw, "starts", self._dev), nw, self._sp(stream)))
+            return r
+        a = _c64(samples).ravel()
+        st = np.ascontiguousarray(starts, dtype=np.int64).ravel()
+        r = self._outputs(st.size)
+        _check(L.gfdm_hip_burst_sync_find_frame_start_at_host(self._h, *[r[k].ctypes.data for k in self._OUT], a.ctypes.data, a.size, st.ctypes.data, st.size))
+        return r
+
+    def detect(self, samples, threshold, min_distance, lead=None, max_bursts=None, stream=None):
+        """Every burst of a stream (contract in include/gfdm_hip.h): peaks of ic over the whole stream that reach `threshold` and are
+        the first maximum within +-min_distance, in ascending position; each one's window starts `lead` before it.  Returns a dict:
+        count (total peaks found: int on the host path, a one-element int64 tensor on the device path, which does not synchronise) and
+        the five find_frame_start arrays with max_bursts slots, those from min(count, max_bursts) on at frame_start = coarse = -1.
+        Defaults: lead = cp_len + fft_len // 2, max_bursts = ceil(P / (min_distance + 1)), the most peaks P positions can hold."""
+        L = lib()
+        n = samples.numel() if _is_tensor(samples) else np.asarray(samples).size
+        R = int(min_distance)
+        lead = self.cp_len() + self.fft_len() // 2 if lead is None else int(lead)
+        if max_bursts is None:
+            max_bursts = max(0, -(-(n - 2 * self.fft_len()) // (max(R, 0) + 1)))
+        nb = int(max_bursts)
+        _check(L.gfdm_hip_burst_sync_detect_check(self.fft_len(), self.cp_len(), self.window_len(), n, threshold, R, lead, nb))
+        if _is_tensor(samples):
+            import torch
+            d = samples.device
+            r = self._outputs(nb, d)
+            count = torch.empty(1, dtype=torch.int64, device=d)
+            ws = torch.empty(L.gfdm_hip_burst_sync_detect_workspace_bytes(self._h, n), dtype=torch.uint8, device=d)
+            _check(L.gfdm_hip_burst_sync_detect_device(self._h, count.data_ptr(), *[r[k].data_ptr() for k in self._OUT], self._dp(samples, n, "samples"), n,
+                                                       threshold, R, lead, nb, ws.data_ptr(), self._sp(stream)))
+            r["count"] = count
+            return r
+        a = _c64(samples).ravel()
+        r = self._outputs(nb)
+        count = np.zeros(1, np.int64)
+        _check(L.gfdm_hip_burst_sync_detect_host(self._h, count.ctypes.data, *[r[k].ctypes.data for k in self._OUT], a.ctypes.data, n, threshold, R, lead, nb))
+        r["count"] = int(count[0])
         return r
 
     def auto_correlate(self, samples, first=0, stride=None, n_windows=1, stream=None):

@@ -438,6 +438,52 @@ int gfdm_hip_burst_sync_auto_correlate_host(gfdm_hip_burst_sync* s, float* ac, f
 int gfdm_hip_burst_sync_auto_correlate_device(gfdm_hip_burst_sync* s, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
                                               int64_t stride, int64_t n_windows, void* stream);
 
+/* find_frame_start_at: the same five outputs on windows at arbitrary starts.  starts is int64[n_windows] (a device array in the device
+ * flavour); window w is stream[st_w : st_w + W] with st_w = clamp(starts[w], 0, stream_len - W) -- clamped, not refused, because starts
+ * that live on the device cannot be checked on the host.  The kernels are those of the regular-grid call, so a window's results are
+ * bit-equal to find_frame_start(first = st_w, n_windows = 1).  stream_len < W is GFDM_HIP_EINVAL. */
+int gfdm_hip_burst_sync_find_frame_start_at_host(gfdm_hip_burst_sync* s, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                                 const float* samples, int64_t stream_len, const int64_t* starts, int64_t n_windows);
+int gfdm_hip_burst_sync_find_frame_start_at_device(gfdm_hip_burst_sync* s, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                                   const void* samples, int64_t stream_len, const void* starts, int64_t n_windows, void* stream);
+
+/* detect: every burst of a stream, without the caller knowing where they are (the job of the external detector in front of
+ * extract_burst_cc in the reference's flowgraphs; pygfdm's pieces are auto_correlate_signal, abs_integrate and
+ * calculate_threshold_factor, python/pygfdm/synchronization.py:132-151, :239-243).
+ * Definitions: ac[i] and ic[i] as above over the WHOLE stream as one window: P = stream_len - 2K positions, ac = 0 where the energy
+ * is 0, ic[n] = 0 for n < cp_len.  With R = min_distance, position i is a peak when
+ *     ic[i] >= threshold,   ic[j] < ic[i] for every j in [i - R, i),   ic[j] <= ic[i] for every j in (i, i + R]
+ * (ranges cut at the stream ends): non-maximum suppression in which the first index of equal values wins.  The rule is local, so
+ * the result does not depend on how the stream is tiled or batched, and any R + 1 consecutive positions hold at most one peak.
+ * Each peak d gets the window start st = clamp(d - lead, 0, stream_len - W); its five outputs are those of find_frame_start on
+ * stream[st : st + W] (bit-equal to find_frame_start_at on that start).
+ * Arguments, each GFDM_HIP_EINVAL otherwise:  cp_len <= lead <= R;  W - 2K - lead - 1 <= R;  threshold > 0;  max_bursts >= 0;
+ * W <= stream_len <= 2^29 (the scan indexes positions in 32 bits; split a longer capture into spans that overlap by W + 2 R);
+ * R <= 2^16 (every tile of 1024 to 4096 positions also computes ic over R positions on either side of it, so the scan's work is
+ * about 1 + 2 R / tile times that of one pass over the stream: half a burst length is the intended order of magnitude).
+ * Why coarse == d away from a clamped edge: the window's positions are the stream's st .. st + W - 2K - 1, and each ac is a function
+ * of its own 2K samples only, so window ac == stream ac.  The window's ic at local n >= cp_len sums the same cp_len + 1 magnitudes as
+ * the stream's ic at st + n (same order: bit-equal in fp32 too), and is 0 for n < cp_len, where the stream's is >= 0.  The peak sits
+ * at local n = lead >= cp_len, so it is present with its full value; every other window position lies within
+ * [d - lead, d + W - 2K - lead - 1], i.e. within R of d on either side, where the stream's ic is < ic[d] before d and <= ic[d] after
+ * it -- and the window's ic is at most the stream's.  The window's first-index argmax is therefore d.
+ * Output: detections in ascending position.  count (one int64; on the device in the device flavour) is the total number of peaks
+ * found, also when it exceeds max_bursts.  Slots [0, min(count, max_bursts)) hold the lowest-position detections; the slots after
+ * them, up to max_bursts, hold frame_start = coarse = -1, cfo = metric = 0, sc_rot = 0 (the extractor does not rotate those).
+ * The device entry point neither allocates nor synchronises (hipGraph-capturable): its scratch -- per-tile peak counts and lists for
+ * the ordered compaction, and the window starts -- is the caller's `workspace` of detect_workspace_bytes(s, stream_len) bytes
+ * (device memory, 16-byte aligned; its content need not be preserved between calls).  The stream is read once plus a halo of
+ * 2 R + cp_len per tile; ic never exists in HBM and nothing is written per position.
+ * detect_check: the argument table alone, without a handle or a device. */
+int gfdm_hip_burst_sync_detect_check(int fft_len, int cp_len, int64_t window_len, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead,
+                                     int64_t max_bursts);
+int64_t gfdm_hip_burst_sync_detect_workspace_bytes(const gfdm_hip_burst_sync* s, int64_t stream_len);
+int gfdm_hip_burst_sync_detect_host(gfdm_hip_burst_sync* s, int64_t* count, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                    const float* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts);
+int gfdm_hip_burst_sync_detect_device(gfdm_hip_burst_sync* s, void* count, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                      const void* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts,
+                                      void* workspace, void* stream);
+
 /* gfdm_hip_burst_extractor: extract_burst_cc (lib/extract_burst_cc_impl.cc:72-242) for n bursts given by their tag offsets:
  *   out[b][n] = scale_b * s[off_b - tag_backoff + n] * (conj(r_b) / |r_b|)^n,   n < burst_len   (n counted from the burst start)
  * scale NULL = 1; sc_rot (complex r_b) NULL, |r_b| = 0 or CFO correction off = no rotation.  Samples before 0 read as zero (the
