@@ -109,6 +109,12 @@ __device__ __forceinline__ cf ac_at(const cf* x, int K)
         ci1 = fmaf(a1.x, b1.y, fmaf(-a1.y, b1.x, ci1));
         e1 = fmaf(a1.x, a1.x, fmaf(a1.y, a1.y, fmaf(b1.x, b1.x, fmaf(b1.y, b1.y, e1))));
     }
+    if (n < K) {                                                             // odd K: the last n is even, so it extends the even chain
+        const cf a0 = x[n], b0 = x[n + K];
+        cr0 = fmaf(a0.x, b0.x, fmaf(a0.y, b0.y, cr0));
+        ci0 = fmaf(a0.x, b0.y, fmaf(-a0.y, b0.x, ci0));
+        e0 = fmaf(a0.x, a0.x, fmaf(a0.y, a0.y, fmaf(b0.x, b0.x, fmaf(b0.y, b0.y, e0))));
+    }
     const float e = e0 + e1;
     if (!(e > 0.f)) return czero();
     const float g = 2.f / e;

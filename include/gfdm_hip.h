@@ -420,7 +420,14 @@ int gfdm_hip_cyclic_prefixer_remove_device(gfdm_hip_cyclic_prefixer* c, void* ou
  * without a burst has a low one), sc_rot = exp(j angle(ac[nm]) / K) (complex: the per-sample rotation present in the signal, in
  * extract_burst_cc's tag convention).  Every position's sums are computed on their own (no running sums), in fp32.
  * auto_correlate: the first stage alone, ac (complex) and ic (float), W - 2K values each per window (either may be NULL, not both).
- * create: EINVAL for n_preamble != 2 fft_len, fft_len outside [2, 1024], cp_len < 0, window_len < 2 fft_len + cp_len + 1. */
+ * create: EINVAL for n_preamble != 2 fft_len, fft_len outside [2, 1024], cp_len < 0, window_len < 2 fft_len + cp_len + 1.
+ * Tested range (against pygfdm fixtures and a float64 restatement of the above: ac and ic within 1e-5, argmax positions exact):
+ * fft_len 2, 15, 16, 31, 32, 64, 93, 128, 256, 589 and 1024; cp_len 0 to 600, among them 255, 256 and 257 (either side of the kernels'
+ * 256-position tile) and values above 2 fft_len; windows from the smallest, 2 fft_len + cp_len + 1 (one live position), to about
+ * 16 million samples (the stream as one window in the detector's tests); up to 32768 + 37 windows per call (beyond 32768 a workgroup
+ * takes several), for the regular grid and the start array alike; detect with min_distance up to 2100 at cp_len 600.  The
+ * extractor: burst_len 1 to 65536,
+ * up to 32768 + 7 bursts per call. */
 typedef struct gfdm_hip_burst_sync gfdm_hip_burst_sync;
 int gfdm_hip_burst_sync_create(gfdm_hip_burst_sync** out, int fft_len, int cp_len, const float* core_preamble, int n_preamble, int64_t window_len,
                                int device);

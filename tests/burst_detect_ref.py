@@ -74,21 +74,42 @@ def ref_fine(win, preamble, K, cp):
     s2 = win * np.exp(1j * np.pi * cfo / K * np.arange(win.size))
     pcc = np.lib.stride_tricks.sliding_window_view(s2, 2 * K)[:P] @ np.conj(p) / (2 * K)
     nc = int(np.argmax(np.abs(pcc) * ic))
-    return dict(ic=ic, nm=nm, nc=nc, cfo=cfo, metric=ic[nm], sc_rot=np.exp(1j * np.angle(ac[nm]) / K))
+    return dict(ic=ic, nm=nm, nc=nc, cfo=cfo, metric=ic[nm], sc_rot=np.exp(1j * np.angle(ac[nm]) / K), score=np.abs(pcc) * ic)
+
+
+def top_margin(v):
+    """the largest value's lead over the second largest (inf for a single value)"""
+    v = np.asarray(v, float)
+    if v.size < 2:
+        return np.inf
+    top = np.partition(v, v.size - 2)[-2:]
+    return float(top[1] - top[0])
+
+
+def click_burst(K, cp, rng):
+    """[click | prefix (cp) | core (2K) | click] and the core: a unit-amplitude random-phase half-symbol twice, the prefix the core's tail
+    (tiled where cp > 2K), and one sample of power 2K on either side.  Without the clicks the ic maximum leads its neighbours by about
+    1 / (2K (cp + 1)) only -- |ac| leaves its plateau in steps of 1 / 2K --, below what fp32 can be held to at a long prefix; a click
+    entering the 2K window doubles its energy, so the lead is about 0.5 / (cp + 1) whatever K is."""
+    core = np.tile(np.exp(2j * np.pi * rng.random(K)), 2)
+    click = np.sqrt(2 * K) * np.exp(2j * np.pi * rng.random(2))
+    return np.concatenate((click[:1], np.resize(core[::-1], cp)[::-1], core, click[1:])), core
 
 
 def ref_detect(s, preamble, K, cp, W, threshold, R, lead):
-    """dict: ic (global), peaks, starts, and per peak frame_start, coarse (stream indices), cfo, metric, sc_rot, ic_win (the window's ic)"""
+    """dict: ic (global), peaks, starts, and per peak frame_start, coarse (stream indices), cfo, metric, sc_rot, ic_win and score_win
+    (the window's ic and |pcc| ic)"""
     s = np.asarray(s)
     _, ic = ref_ac_ic(s, K, cp)
     peaks = ref_peaks(ic, threshold, R)
     starts = np.clip(peaks - lead, 0, s.size - W)
-    out = dict(ic=ic, peaks=peaks, starts=starts, frame_start=[], coarse=[], cfo=[], metric=[], sc_rot=[], ic_win=[])
+    out = dict(ic=ic, peaks=peaks, starts=starts, frame_start=[], coarse=[], cfo=[], metric=[], sc_rot=[], ic_win=[], score_win=[])
     for st in starts:
         f = ref_fine(s[st:st + W], preamble, K, cp)
         out["frame_start"].append(st + f["nc"])
         out["coarse"].append(st + f["nm"])
         out["ic_win"].append(f["ic"])
+        out["score_win"].append(f["score"])
         for k in ("cfo", "metric", "sc_rot"):
             out[k].append(f[k])
     for k in ("frame_start", "coarse", "cfo", "metric", "sc_rot"):

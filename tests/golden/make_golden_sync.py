@@ -42,6 +42,8 @@ from gfdm_amd.filters import get_frequency_domain_filter                       #
 #   cut:       the window starts inside the burst's cyclic prefix (its CP plateau is cut)
 #   noise:     noise only (frame_start means nothing there; only ac, ic and metric are compared)
 #   zeros:     the window starts with a run of K zeros (shorter than 2K: pygfdm yields no NaN)
+#   tiled:     as burst, but the core preamble is a random-phase half-symbol repeated twice and the prefix the core's tail, tiled
+#              where cp_len > 2K: at K = 64 get_sync_symbol raises for cp_len = 0, 257 and 300 (it accepts an odd K)
 CASES = [
     ("k32_cp32_cfo0", 32, 32, 0.0, 20.0, "burst"),
     ("k32_cp32_cfo045", 32, 32, 0.45, 25.0, "burst"),
@@ -56,6 +58,13 @@ CASES = [
     ("k64_cut_cfop02_20db", 64, 32, 0.2, 20.0, "cut"),
     ("k64_noise", 64, 32, 0.0, 20.0, "noise"),
     ("k64_zeros_cfom02_20db", 64, 32, -0.2, 20.0, "zeros"),
+    # odd fft_len; cp_len 0, one past the 256-position tile of the kernels, and above 2K
+    ("k15_cp7_cfop02_26db", 15, 7, 0.2, 26.0, "burst"),
+    ("k31_cp16_cfom02_20db", 31, 16, -0.2, 20.0, "burst"),
+    ("k93_cp40_cfop02_26db", 93, 40, 0.2, 26.0, "burst"),
+    ("k64_cp0_cfop02_26db", 64, 0, 0.2, 26.0, "tiled"),
+    ("k64_cp257_cfop02_26db", 64, 257, 0.2, 26.0, "tiled"),
+    ("k64_cp300_cfom02_26db", 64, 300, -0.2, 26.0, "tiled"),
 ]
 DATA_BLOCKS = 5          # data samples after the preamble: DATA_BLOCKS * K
 CONTEXT = 37             # stream samples before the window (the window starts at `first`, not at 0)
@@ -63,16 +72,20 @@ CONTEXT = 37             # stream samples before the window (the window starts a
 
 def make_case(name, K, cp, cfo, snr_db, kind):
     rng = np.random.default_rng(sum(map(ord, name)))
-    A = K - K // 4 if K > 32 else 24
-    smap = get_subcarrier_map(K, A, dc_free=True)
-    pn_sym = map_to_waveform_resources(get_random_qpsk(A, int(rng.integers(1 << 30))), A, K, smap)
-    H = get_frequency_domain_filter("rrc", 0.2, 2, K, 2)
-    H = H / np.sqrt(calculate_signal_energy(H) / 2.0)                          # generate_sync_symbol, preamble.py:128-132
-    full, core = get_sync_symbol(pn_sym, H, K, 2, cp, 0)                       # [cp | core (2K)]
+    if kind == "tiled":
+        core = np.tile(np.exp(2j * np.pi * rng.random(K)), 2)
+        full = np.concatenate((np.resize(core[::-1], cp)[::-1], core))        # the last cp samples of ... core core core
+    else:
+        A = K - K // 4 if K > 32 else min(24, K - K // 4)
+        smap = get_subcarrier_map(K, A, dc_free=True)
+        pn_sym = map_to_waveform_resources(get_random_qpsk(A, int(rng.integers(1 << 30))), A, K, smap)
+        H = get_frequency_domain_filter("rrc", 0.2, 2, K, 2)
+        H = H / np.sqrt(calculate_signal_energy(H) / 2.0)                      # generate_sync_symbol, preamble.py:128-132
+        full, core = get_sync_symbol(pn_sym, H, K, 2, cp, 0)                   # [cp | core (2K)]
     data = (rng.standard_normal(DATA_BLOCKS * K) + 1j * rng.standard_normal(DATA_BLOCKS * K)) * np.sqrt(np.mean(np.abs(core) ** 2) / 2)
     burst = np.concatenate((full, data))
     W = cp + 2 * K + DATA_BLOCKS * K + 3 * K // 2
-    lead = {"burst": cp + 11, "cut": cp // 2, "noise": 0, "zeros": K + cp + 5}[kind]     # window start -> core preamble
+    lead = {"burst": cp + 11, "tiled": cp + 11, "cut": cp // 2, "noise": 0, "zeros": K + cp + 5}[kind]     # window start -> core preamble
     n = CONTEXT + W + 64
     gain = 0.5 + rng.random()
     sigma = gain * np.sqrt(np.mean(np.abs(core) ** 2) / 10 ** (snr_db / 10) / 2)

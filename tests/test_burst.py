@@ -1,9 +1,12 @@
 """CPU-side checks of the burst synchroniser and extractor handles (gfdm_hip_burst_sync, gfdm_hip_burst_extractor): the entry points
-are bound, constructor arguments are validated before any device is touched, and without a GPU creation answers ENODEV."""
+are bound, constructor arguments are validated before any device is touched, and without a GPU creation answers ENODEV; and the
+float64 restatement of the synchroniser's contract, the expectation of the GPU tests, against every pygfdm fixture of tests/golden/sync."""
 import numpy as np
 import pytest
 
+from burst_detect_ref import ref_ac_ic, ref_fine
 from conftest import have_gpu
+from test_burst_gpu import load_sync, sync_names
 
 
 def _preamble(K):
@@ -65,3 +68,20 @@ def test_burst_handles_need_a_gpu():
     with pytest.raises(gfdm_amd.GfdmHipError) as e:
         gfdm_amd.BurstExtractor(800, 32, True)
     assert e.value.status == gfdm_amd.capi.ENODEV
+
+
+@pytest.mark.parametrize("name", sync_names())
+def test_restatement_matches_pygfdm(name):
+    """ref_ac_ic / ref_fine (and with them ref_sync, held to the same fixtures on the GPU) are pygfdm's auto_correlation_sync and
+    find_frame_start at every fixture's shape: odd fft_len, cp_len = 0 and cp_len above 2 fft_len among them"""
+    g = load_sync(name)
+    K, cp = g["K"], g["cp_len"]
+    win = g["stream"][g["first"]:g["first"] + g["window_len"]]
+    ac, ic = ref_ac_ic(win, K, cp)
+    assert ac.size == g["ac"].size == g["window_len"] - 2 * K
+    assert np.max(np.abs(ac - g["ac"])) < 1e-12 and np.max(np.abs(ic - g["ic"])) < 1e-12
+    f = ref_fine(win, g["preamble"], K, cp)
+    assert f["nm"] == g["nm"] and f["nc"] == g["nc"] and abs(f["cfo"] - float(g["cfo"])) < 1e-12
+    assert np.max(np.abs(f["score"] - g["napcc"])) < 1e-12
+    if g["kind"] in ("burst", "tiled", "zeros"):
+        assert g["nc"] == g["core_start"] - g["first"]

@@ -1,12 +1,16 @@
 """GPU tests of the burst detector (gfdm_hip_burst_sync_detect) and of find_frame_start_at: against the pygfdm fixtures of
 tests/golden/detect (make_golden_detect.py) and the float64 restatement of the contract (tests/burst_detect_ref.py), against the
 existing regular-grid calls (bit-equal), under a different tiling, with too few and too many output slots, and in front of the
-extractor and the estimated IC receiver with every step on the device."""
+extractor and the estimated IC receiver with every step on the device; and on synthetic streams at odd fft_len, at cp_len of 0 and on
+either side of the 256-position segment (where the scan changes from segment_ic to tile_ic), and with a +-min_distance halo of eight
+segments, against the restatement alone, which tests/test_burst.py holds against pygfdm at such shapes."""
+import functools
+
 import numpy as np
 import pytest
 
 import gfdm_ref as R
-from burst_detect_ref import detect_names, load_detect, ref_detect, ref_peaks
+from burst_detect_ref import click_burst, detect_names, load_detect, nms_maxima, ref_ac_ic, ref_detect, ref_peaks, top_margin
 from conftest import have_gpu
 from gfdm_amd.filters import get_frequency_domain_filter
 
@@ -279,6 +283,101 @@ def test_detect_argument_errors():
     assert L.gfdm_hip_burst_sync_detect_workspace_bytes(sync._h, s.size) > 0
     assert L.gfdm_hip_burst_sync_detect_workspace_bytes(sync._h, W - 1) == gfdm_amd.capi.EINVAL
     assert sync.detect(s[:W], 0.45, W - 2 * K - 64 - 1, 64)["count"] in (0, 1)          # the smallest stream and min_distance
+
+
+# ---- synthetic streams at the shapes the fixtures leave out ----
+# K, cp_len, min_distance, bursts, stream_len.  lead = cp_len + K // 2 (the default) and W = lead + 3 K + cp_len, so W - 2K - lead - 1 = K + cp_len - 1
+EDGE_STREAMS = [
+    (15, 7, 150, 10, 20000), (93, 40, 400, 8, 30000), (64, 0, 300, 9, 24000),
+    (64, 256, 500, 7, 28000), (64, 257, 500, 7, 28001), (64, 300, 500, 6, 27000),      # segment_ic up to cp_len 256, tile_ic per segment above
+    (64, 600, 2100, 8, 40000),                                                          # +-R spans 9 segments either side, the cp halo 3
+]
+EDGE_THRESHOLD = 0.8
+MARGIN = 1e-4
+
+
+@functools.lru_cache(maxsize=None)
+def edge_stream(K, cp, Rd, nb, n):
+    """dict: the stream (noise 26 dB below nb click_bursts of one core, each with its own gain, phase and CFO, more than Rd apart), the
+    core, the planted core starts, lead, W and ref_detect of it"""
+    rng = np.random.default_rng(K * 1000 + cp)
+    burst, core = click_burst(K, cp, rng)
+    lead = cp + K // 2
+    W = lead + 3 * K + cp
+    slot = (n - 2 * W) // nb
+    assert slot > Rd + burst.size + W
+    at = W + slot * np.arange(nb) + rng.integers(0, slot - Rd - burst.size, nb)       # gaps above Rd
+    sigma = np.sqrt(10 ** -2.6 / 2)
+    s = sigma * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    for a in at:
+        # (CFO within +-0.2: towards +-0.3 the fine timing locks to a +-K side peak, in the restatement as in pygfdm -- include/gfdm_hip.h)
+        rot = (0.5 + rng.random()) * np.exp(1j * (2 * np.pi * rng.random() + 2 * np.pi * rng.uniform(-0.2, 0.2) / K * np.arange(burst.size)))
+        s[a:a + burst.size] += burst * rot
+    s = s.astype(np.complex64)
+    s.setflags(write=False)
+    return dict(stream=s, preamble=core, core_starts=at + 1 + cp, lead=lead, window_len=W,
+                ref=ref_detect(s, core, K, cp, W, EDGE_THRESHOLD, Rd, lead))
+
+
+def _assert_reference_is_decided(c, Rd):
+    """on the reference alone: every maximum of the +-Rd rule is more than MARGIN off the threshold, every peak leads its +-Rd
+    neighbourhood by more than MARGIN and is a planted burst, and in every peak's window the ic and |pcc| ic maxima lead by MARGIN"""
+    ref = c["ref"]
+    ic, peaks = ref["ic"], ref["peaks"]
+    maxima = nms_maxima(ic, Rd)
+    assert np.all(np.abs(ic[maxima] - EDGE_THRESHOLD) > MARGIN)
+    assert np.array_equal(peaks, c["core_starts"]) and np.array_equal(ref["frame_start"], c["core_starts"])
+    for i, d in enumerate(peaks):
+        around = np.concatenate((ic[max(0, d - Rd):d], ic[d + 1:d + Rd + 1]))
+        assert ic[d] - around.max() > MARGIN, (d, ic[d] - around.max())
+        assert top_margin(ref["ic_win"][i]) > MARGIN and top_margin(ref["score_win"][i]) > MARGIN, d
+
+
+@pytest.mark.parametrize("K,cp,Rd,nb,n", EDGE_STREAMS)
+def test_edge_stream_peaks_are_the_rule_on_the_librarys_own_ic(K, cp, Rd, nb, n):
+    import gfdm_amd
+    c = edge_stream(K, cp, Rd, nb, n)
+    s, lead, W = c["stream"], c["lead"], c["window_len"]
+    whole = gfdm_amd.BurstSync(K, cp, c["preamble"], n)                              # the stream as one window
+    ac, ic = whole.auto_correlate(s)
+    rac, _ = ref_ac_ic(s, K, cp)
+    e_ac, e_ic = np.max(np.abs(ac[0] - rac)), np.max(np.abs(ic[0] - c["ref"]["ic"]))
+    print("K %d cp %d: ac err %.3e ic err %.3e" % (K, cp, e_ac, e_ic))
+    assert e_ac < 1e-5 and e_ic < 1e-5
+    sync = gfdm_amd.BurstSync(K, cp, c["preamble"], W)
+    for thr in (EDGE_THRESHOLD, 0.5, 0.3):                                           # lower thresholds: noise peaks too
+        r = sync.detect(s, thr, Rd, lead)
+        peaks = ref_peaks(ic[0].astype(np.float64), float(np.float32(thr)), Rd)
+        print("   threshold %.2f: count %d, rule %d" % (thr, r["count"], peaks.size))
+        assert r["count"] == peaks.size and peaks.size >= nb, thr
+        free = np.flatnonzero((peaks >= lead) & (peaks - lead <= n - W))             # coarse == peak is promised away from a clamped window only
+        assert free.size >= peaks.size - 2
+        assert np.array_equal(r["coarse"][free], peaks[free]) and np.array_equal(r["metric"][free], ic[0][peaks[free]]), thr
+        _assert_sentinels(r, peaks.size)
+
+
+@pytest.mark.parametrize("K,cp,Rd,nb,n", EDGE_STREAMS)
+def test_edge_stream_matches_restatement(K, cp, Rd, nb, n):
+    import torch
+    import gfdm_amd
+    c = edge_stream(K, cp, Rd, nb, n)
+    ref = c["ref"]
+    _assert_reference_is_decided(c, Rd)
+    sync = gfdm_amd.BurstSync(K, cp, c["preamble"], c["window_len"])
+    r = sync.detect(c["stream"], EDGE_THRESHOLD, Rd, c["lead"])
+    print("K %d cp %d R %d: count %d (%d) coarse %s" % (K, cp, Rd, r["count"], nb, r["coarse"][:nb]))
+    assert r["count"] == nb
+    _assert_sentinels(r, nb)
+    assert np.array_equal(r["frame_start"][:nb], ref["frame_start"]) and np.array_equal(r["coarse"][:nb], ref["coarse"])
+    e_cfo, e_met = np.max(np.abs(r["cfo"][:nb] - ref["cfo"])), np.max(np.abs(r["metric"][:nb] - ref["metric"]))
+    print("   cfo err %.3e metric err %.3e" % (e_cfo, e_met))
+    assert e_cfo < 1e-4 and e_met < 1e-5
+    rot = r["sc_rot"][:nb]
+    assert np.max(np.abs(np.abs(rot) - 1)) < 1e-5 and np.max(np.abs(np.angle(rot) * K / (2 * np.pi) - r["cfo"][:nb])) < 1e-5
+    d = _to_host(sync.detect(torch.tensor(c["stream"], device="cuda:0"), EDGE_THRESHOLD, Rd, c["lead"]))
+    assert int(d["count"][0]) == nb
+    for k in OUT:
+        assert np.array_equal(d[k], r[k]), k
 
 
 # ---- end to end on the device: detect -> extractor -> estimated IC receiver (the stream of tests/test_burst_gpu.py's chain test) ----

@@ -54,7 +54,7 @@ def ref_sync(s, preamble, K, cp):
     s2 = s * np.exp(1j * np.pi * cfo / K * np.arange(s.size))
     pcc = np.lib.stride_tricks.sliding_window_view(s2, 2 * K)[:P] @ np.conj(p) / (2 * K)
     nc = int(np.argmax(np.abs(pcc) * ic))
-    return dict(ac=ac, ic=ic, nm=nm, cfo=cfo, nc=nc, metric=ic[nm], sc_rot=np.exp(1j * np.angle(ac[nm]) / K))
+    return dict(ac=ac, ic=ic, nm=nm, cfo=cfo, nc=nc, metric=ic[nm], sc_rot=np.exp(1j * np.angle(ac[nm]) / K), score=np.abs(pcc) * ic)
 
 
 def ref_extract(s, offsets, burst_len, backoff, scale=None, sc_rot=None, correct=True):
@@ -121,7 +121,7 @@ def test_find_frame_start_matches_pygfdm(name):
     torch.cuda.synchronize()
     for k in r:
         assert np.array_equal(d[k].cpu().numpy(), r[k]), k
-    if g["kind"] in ("burst", "zeros"):        # (a window that cuts the CP plateau puts pygfdm's nc elsewhere: ic is 0 before cp_len)
+    if g["kind"] in ("burst", "tiled", "zeros"):        # (a window that cuts the CP plateau puts pygfdm's nc elsewhere: ic is 0 before cp_len)
         assert int(r["frame_start"][0]) == g["core_start"]
 
 
