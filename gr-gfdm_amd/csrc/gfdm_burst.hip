@@ -25,6 +25,7 @@
 #include "../../include/gfdm_hip.h"
 #include "gfdm_plan.h"
 #include "gfdm_dft.h"
+#include "gfdm_burstfetch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -285,28 +286,14 @@ __global__ __launch_bounds__(kTile) void k_extract(cf* __restrict__ out, const c
             phi = 0.0;
             if (correct && sc_rot) {
                 const cf r = sc_rot[b];
-                if (r.x != 0.f || r.y != 0.f) {
-                    rotate = 1;
-                    phi = -atan2((double)r.y, (double)r.x);
-                }
+                gfdm::burst_phase_step(r, rotate, phi);
             }
         }
         __syncthreads();
         const int64_t base = offsets[b] - backoff;
         const float g = scale ? scale[b] : 1.f;
-        for (int n = blockIdx.x * kTile + threadIdx.x; n < burst_len; n += gridDim.x * kTile) {
-            const int64_t i = base + n;
-            cf x = (i >= 0 && i < stream_len) ? gfdm::dft::ld_stream(s + i) : czero();
-            x = make_float2(x.x * g, x.y * g);
-            if (rotate) {
-                double ph = phi * (double)n;
-                ph -= 2.0 * M_PI * rint(ph * (0.5 / M_PI));
-                float sn, cs;
-                sincosf((float)ph, &sn, &cs);
-                x = make_float2(x.x * cs - x.y * sn, x.x * sn + x.y * cs);
-            }
-            gfdm::dft::st_stream(out, b * burst_len + n, x);
-        }
+        for (int n = blockIdx.x * kTile + threadIdx.x; n < burst_len; n += gridDim.x * kTile)
+            gfdm::dft::st_stream(out, b * burst_len + n, gfdm::burst_fetch(s, stream_len, base, n, g, rotate, phi));      // gfdm_burstfetch.h
         __syncthreads();
     }
 }

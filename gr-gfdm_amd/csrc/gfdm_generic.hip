@@ -16,6 +16,7 @@
 #include "gfdm_plan.h"
 #include "gfdm_tx.h"
 #include "gfdm_est.h"
+#include "gfdm_burstfetch.h"
 
 namespace gfdm {
 namespace {
@@ -421,18 +422,24 @@ __device__ __forceinline__ cf* col_fft(cf* a, cf* b, const DevicePlan& p)
 
 // estimate_preamble_channel :118-145 -- K-point FFT of both preamble halves, times 0.5 / FFT(known half), summed.
 // a, b: LDS scratch of 2K each; dst: K bins (LDS or global).  Caller syncs afterwards.
-__device__ __forceinline__ void estimate_preamble_bins(const EstPlan& e, const cf* __restrict__ rx, cf* a, cf* b, cf* dst)
+// ld(i): sample i of the received preamble
+template <class Ld>
+__device__ __forceinline__ void estimate_preamble_bins_from(const EstPlan& e, Ld ld, cf* a, cf* b, cf* dst)
 {
     const int K = e.K;
     for (int i = threadIdx.x; i < 2 * K; i += GT) {
         const int h = i >= K, q = i - h * K;
-        a[q * 2 + h] = rx[i];                        // [q][half]: both halves go through one column FFT
+        a[q * 2 + h] = ld(i);                        // [q][half]: both halves go through one column FFT
     }
     __syncthreads();
     DevicePlan p{};
     p.M = 2; p.K = K; p.log2K = e.log2K; p.wK = e.wK;
     const cf* E = col_fft<false>(a, b, p);
     for (int j = threadIdx.x; j < K; j += GT) dst[j] = cfma(E[2 * j], e.inv0[j], cmul(E[2 * j + 1], e.inv1[j]));
+}
+__device__ __forceinline__ void estimate_preamble_bins(const EstPlan& e, const cf* __restrict__ rx, cf* a, cf* b, cf* dst)
+{
+    estimate_preamble_bins_from(e, [&](int i) { return rx[i]; }, a, b, dst);
 }
 
 __device__ __forceinline__ cf decide(cf x, const IcParams& ic)
@@ -641,214 +648,25 @@ __global__ __launch_bounds__(GT) void k_add_frame(DevicePlan p, TxParams tx, con
     tx_store_preamble(tx, blockIdx.x, threadIdx.x, GT);
 }
 
+// BURST: block and preamble gathered from a capture through the burst extractor's fetch (gfdm_burstfetch.h; BurstIo, eq_source
+// EQ_PREAMBLE) -- k_generic_receive_burst; `in` and `f_eq` are unused there
 template <bool GLOBAL, bool MX>
 __global__ __launch_bounds__(GT, MX ? 4 : 8) void k_generic_receive(DevicePlan pg, IcParams ic, EstPlan est, int eq_source, int ntiles, int mode, int s_in_global,
                                                         int tab_off, TileArgs ta, cf* __restrict__ out, const cf* __restrict__ in,
                                                         const cf* __restrict__ f_eq)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const DevicePlan p = stage_tables(pg, smem, tab_off);
-    const auto mx = mx_of<MX>(p, ta, smem);
-    float* red = reinterpret_cast<float*>(smem);
-    cf* t0;
-    if constexpr (GLOBAL) t0 = ta.gtiles + (int64_t)blockIdx.x * ta.tile_elems; else t0 = reinterpret_cast<cf*>(smem + RED_BYTES);
-    const int M = p.M, K = p.K, L = p.L, N = p.N;
-    const int TS = GLOBAL ? N : ta.tile_stride;
-    cf* t1 = t0 + TS;
-    cf* t2 = t1 + TS;                                              // only valid when 3 tiles were requested
-    const int64_t blk = ta.blk0 + blockIdx.x;
-    const cf* x = in + blk * (int64_t)(ic.io.in_stride ? ic.io.in_stride : N) + ic.io.in_offset;   // frame -> block
-    const bool demap = ic.io.demap && mode != RX_FD;
-    cf* o = out + blk * (demap ? ic.io.nout : N);
-    const cf* eq = (eq_source == EQ_VECTOR) ? f_eq + blk * N : nullptr;
-    cf* filt = t0 + (size_t)ntiles * TS + K;                      // EQ_PREAMBLE: smoothed channel estimate, behind the tiles
-    if (eq_source == EQ_PREAMBLE) {                                // channel estimator in front, the tiles are its scratch
-        cf* bins = t0 + (size_t)ntiles * TS;
-        estimate_preamble_bins(est, f_eq + blk * (est.pre_stride ? est.pre_stride : 2 * K), t0, t1, bins);
-        __syncthreads();
-        for (int i = threadIdx.x; i < est.n_est; i += GT) filt[i] = est_filter_bin(bins, i, est);
-        __syncthreads();
-    }
+    constexpr bool BURST = false;
+    const BurstIo bio{};                                  // (never read)
+#include "gfdm_generic_receive_body.h"
+}
 
-    GFDM_GSTAMP(0);
-    stream_in(t1, x, N);
-    __syncthreads();
-    GFDM_GSTAMP(1);
-    // A[q][m] = W_N^{q m} * sum_p x[K p + q] W_M^{p m}
-    // (matrix-core form without a scratch of its own: the operands go to the free tile t0, the result replaces the samples in t1)
-    cf* A0 = mx.in_place() ? t1 : t0;
-    cf* A1 = mx.in_place() ? t0 : t1;
-    paired_dft<false>(mx.at(t0, K), K, M, p.wM, [&](int q, int pp) { return t1[K * pp + q]; },       // outputs m and M - m from one pass (DftPair)
-                      [&](int q, int m, const DftPair& acc) {
-                          const int m2 = (m == 0) ? 0 : M - m;
-                          A0[q * M + m] = cmul(acc.with_root(), p.wN[q * m]);
-                          if (m2 != m) A0[q * M + m2] = cmul(acc.with_conj(), p.wN[q * m2]);
-                      });
-    __syncthreads();
-    GFDM_GSTAMP(2);
-    cf* X = col_fft<false>(A0, A1, p);                             // X[j][m] = FFT_N(x)[M j + m]       :304-305
-    cf* U = (X == A0) ? A1 : A0;
-    GFDM_GSTAMP(3);
-    if (eq) {                                                      // one-tap equaliser                 :315-316
-        stream_in(X, eq, N, [&](cf e, int idx) { return cdiv(X[idx], e); });
-        __syncthreads();
-    } else if (eq_source == EQ_PREAMBLE) {                         // same, the estimate interpolated on the fly
-        for (int idx = threadIdx.x; idx < N; idx += GT) X[idx] = cdiv(X[idx], est_frame_bin<0>(filt, idx, est));
-        __syncthreads();
-    }
-    // S[k][m] = sum_i taps[((i + L/2) % L) M + m] * X[((k + i + K - L/2) % K) M + m]                    :165-192
-    cf* Sdst = (mode == RX_FD) ? o : U;
-    if (L <= TAPS_IN_REGS) {
-        for_columns(M, [&](int m, int k0, int ks) {
-            cf tp[TAPS_IN_REGS];
-#pragma unroll
-            for (int i = 0; i < TAPS_IN_REGS; ++i) tp[i] = (i < L) ? p.taps[((i + L / 2) % L) * M + m] : make_float2(0.f, 0.f);
-            int r0 = ((k0 - L / 2) % K + K) % K;                    // row (k + i - L/2) mod K, tap part (i + L/2) mod L
-            const int rs = ks % K;
-            for (int k = k0; k < K; k += ks) {
-                cf acc = make_float2(0.f, 0.f);
-                int row = r0;
-#pragma unroll
-                for (int i = 0; i < TAPS_IN_REGS; ++i) {
-                    if (i < L) {
-                        acc = cfma(tp[i], X[row * M + m], acc);
-                        if (++row == K) row = 0;
-                    }
-                }
-                Sdst[k * M + m] = acc;
-                r0 += rs;
-                if (r0 >= K) r0 -= K;
-            }
-        });
-    } else {
-        DivStep fx(threadIdx.x, GT, M);
-        for (int idx = threadIdx.x; idx < N; idx += GT, fx.next()) {
-            const int k = fx.q, m = fx.r;
-            cf acc = make_float2(0.f, 0.f);
-            int row = k - L / 2, part = L / 2;
-            if (row < 0) row += K;
-            for (int i = 0; i < L; ++i) {
-                acc = cfma(p.taps[part * M + m], X[row * M + m], acc);
-                if (++row == K) row = 0;
-                if (++part == L) part = 0;
-            }
-            Sdst[idx] = acc;
-        }
-    }
-    if (mode == RX_FD) return;
-    __syncthreads();
-    GFDM_GSTAMP(4);
-    const float invM = 1.f / (float)M;
-    if (mode == RX_DEMOD || ic.ic_iter <= 0) {
-        if (!demap) {
-            row_dft<true>(mx.at(X, K), o, U, K, M, M, 1, p.wM, invM);      // d = IFFT_M(S_k) / M                :211-225
-            GFDM_GSTAMP(5);
-        } else {
-            cf* d = mx.in_place() ? U : X;                              // (X holds the operands then)
-            row_dft<true>(mx.at(X, K), d, U, K, M, M, 1, p.wM, invM);
-            __syncthreads();
-            emit_demapped(o, d, ic.io, K, M);
-        }
-        return;
-    }
-    // One cancellation round of the reference is  d_new = IDFT_M(S - ic (.) DFT_M(nb)) / M  with nb = dec_{k-1} + dec_{k+1}
-    // (receiver_kernel_cc.cc:274-299 + :211-225).  Both transforms are linear, so  d_new = d0 - g (*) nb  with d0 = IDFT_M(S) / M
-    // and the M-tap circular kernel g = IDFT_M(ic) / M (p.icg): one table-driven pass per round instead of two, S is not needed
-    // again (a rotation of S by the phase compensation is the same rotation of d0).
-    cf* D = mx.in_place() ? t2 : X;                                // (in place: X takes the operands of every transform from here on)
-    row_dft<true>(mx.at(X, K), D, U, K, M, M, 1, p.wM, invM);
-    __syncthreads();
-    if constexpr (MX) {
-        // With the transforms on the matrix cores the rounds keep the reference's own form, S' = S - ic (.) DFT_M(nb), d = IDFT_M(S') / M: two constant-
-        // matrix products per round instead of the O(M^2) convolution on the vector ALU.  S stays in its tile, S' goes to the third one (or the output block).
-        cf* S = U;
-        cf* V = mx.in_place() ? D : s_in_global ? o : t2;             // (in place: S' replaces the decisions once all of them are operands)
-        const auto mxs = mx.at(X, K);
-        for (int j = 0; j < ic.ic_iter; ++j) {
-            if (ic.do_phase_compensation > 0 && j == 0) {
-                const cf rot = phase_rotation(D, ic, red, M);
-                for (int idx = threadIdx.x; idx < N; idx += GT) S[idx] = cmul(S[idx], rot);     // adv:63-70: the rotation of S persists
-                __syncthreads();
-            }
-            {
-                DivStep dx(threadIdx.x, GT, M);
-                for (int idx = threadIdx.x; idx < N; idx += GT, dx.next())
-                    D[idx] = ic.active[dx.q] ? decide(D[idx], ic) : make_float2(0.f, 0.f);
-            }
-            __syncthreads();
-            cancel_rows(mxs, V, D, S, p);
-            __syncthreads();
-            const bool last = (j == ic.ic_iter - 1);
-            row_dft<true>(mxs, (last && !demap) ? o : D, V, K, M, M, 1, p.wM, invM);
-            __syncthreads();
-            if (last && demap) emit_demapped(o, D, ic.io, K, M);
-        }
-        return;
-    }
-    cf* D0 = U;
-    cf* V = t2;
-    if (s_in_global) {                                            // third tile does not fit: d0 lives in the output block
-        D0 = o;
-        V = U;
-    }
-    for (int idx = threadIdx.x; idx < N; idx += GT) D0[idx] = D[idx];
-    __syncthreads();
-    for (int j = 0; j < ic.ic_iter; ++j) {                        // perform_ic_iterations            adv:56-76
-        if (ic.do_phase_compensation > 0 && j == 0) {
-            const cf rot = phase_rotation(D, ic, red, M);
-            for (int idx = threadIdx.x; idx < N; idx += GT) D0[idx] = cmul(D0[idx], rot);   // rotating S rotates d0; persists  adv:63-70
-            __syncthreads();
-        }
-        {
-            DivStep dx(threadIdx.x, GT, M);
-            for (int idx = threadIdx.x; idx < N; idx += GT, dx.next())   // map_symbols_to_constellation_points  adv:109-123
-                D[idx] = ic.active[dx.q] ? decide(D[idx], ic) : make_float2(0.f, 0.f);
-        }
-        __syncthreads();
-        {                                                         // nb = dec_{k-1} + dec_{k+1} (wraps mod K)  rx:279-284
-            DivStep nx(threadIdx.x, GT, M);
-            for (int idx = threadIdx.x; idx < N; idx += GT, nx.next()) {
-                const int k = nx.q, pp = nx.r;
-                V[idx] = cadd(D[(k == 0 ? K - 1 : k - 1) * M + pp], D[(k == K - 1 ? 0 : k + 1) * M + pp]);
-            }
-        }
-        __syncthreads();
-        const bool last = (j == ic.ic_iter - 1);
-        cf* dst = (last && !demap) ? o : D;                        // the decisions are spent: the new symbols replace them
-        DivStep cx(threadIdx.x, GT, M);
-        for (int idx = threadIdx.x; idx < N; idx += GT, cx.next()) {
-            const int pp = cx.r;
-            const cf* nb = V + cx.q * M;
-            cf acc = D0[idx];
-            if (p.ic_real_sym) {                                   // g real and even: g_r (nb[p - r] + nb[p + r])
-                const float g0 = p.icg[0].x;
-                acc = make_float2(acc.x - g0 * nb[pp].x, acc.y - g0 * nb[pp].y);
-                int lo = pp, hi = pp;
-                const int H = (M - 1) / 2;
-                for (int r = 1; r <= H; ++r) {
-                    if (--lo < 0) lo = M - 1;
-                    if (++hi == M) hi = 0;
-                    const float g = p.icg[r].x;
-                    acc = make_float2(acc.x - g * (nb[lo].x + nb[hi].x), acc.y - g * (nb[lo].y + nb[hi].y));
-                }
-                if ((M & 1) == 0) {                                // the middle tap of an even length
-                    if (--lo < 0) lo = M - 1;
-                    const float g = p.icg[M / 2].x;
-                    acc = make_float2(acc.x - g * nb[lo].x, acc.y - g * nb[lo].y);
-                }
-            } else {
-                int src = pp;                                     // (pp - r) mod M
-                for (int r = 0; r < M; ++r) {
-                    const cf g = p.icg[r], x = nb[src];
-                    acc = make_float2(acc.x - g.x * x.x + g.y * x.y, acc.y - g.x * x.y - g.y * x.x);
-                    if (--src < 0) src = M - 1;
-                }
-            }
-            dst[idx] = acc;
-        }
-        __syncthreads();
-        if (last && demap) emit_demapped(o, D, ic.io, K, M);
-    }
+template <bool GLOBAL, bool MX>
+__global__ __launch_bounds__(GT, MX ? 4 : 8) void k_generic_receive_burst(DevicePlan pg, IcParams ic, EstPlan est, int eq_source, int ntiles, int mode, int s_in_global,
+                                                        int tab_off, TileArgs ta, cf* __restrict__ out, const cf* __restrict__ in,
+                                                        const cf* __restrict__ f_eq, BurstIo bio)
+{
+    constexpr bool BURST = true;
+#include "gfdm_generic_receive_body.h"
 }
 
 template <bool GLOBAL, bool MX>
@@ -1135,6 +953,14 @@ hipError_t launch_generic_receive(const DevicePlan& p, const IcParams& ic, const
             // (the rounds of the matrix-core form keep S, the decisions and the operands in three LDS tiles)
             const MxAlias al = s_in_global ? MxAlias{ false, p.N } : mx_alias(p, ntiles, RED_BYTES + extra + 16 + table_bytes(p));
             const size_t tab = (generic_lds_bytes(al.tile_stride, ntiles) + extra + 15) & ~(size_t)15, lds = tab + table_bytes(p);
+            if (const BurstIo* bio = burst_io(est)) {
+                auto kern = al.on ? k_generic_receive_burst<false, true> : k_generic_receive_burst<false, false>;
+                hipError_t e = allow_lds(kern, lds);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(GT), lds, s, p, ic, *est, eq_source, ntiles, mode, s_in_global, (int)tab,
+                                   TileArgs{ nullptr, 0, 0, 0, 0, al.on ? 1 : 0, al.tile_stride }, out, in, f_eq, *bio);
+                return hipGetLastError();
+            }
             auto kern = al.on ? k_generic_receive<false, true> : k_generic_receive<false, false>;
             hipError_t e = allow_lds(kern, lds);
             if (e != hipSuccess) return e;
@@ -1150,11 +976,15 @@ hipError_t launch_generic_receive(const DevicePlan& p, const IcParams& ic, const
     if (e != hipSuccess) return e;
     const size_t tab = (RED_BYTES + 15) & ~(size_t)15;
     const MxLds mx = mx_lds(p, tab + table_bytes(p));
+    const BurstIo* bio = burst_io(est);
     auto kern = mx.rtc ? k_generic_receive<true, true> : k_generic_receive<true, false>;
-    if ((e = allow_lds(kern, mx.total)) != hipSuccess) return e;
+    auto kern_burst = mx.rtc ? k_generic_receive_burst<true, true> : k_generic_receive_burst<true, false>;
+    if ((e = bio ? allow_lds(kern_burst, mx.total) : allow_lds(kern, mx.total)) != hipSuccess) return e;
     for (int64_t b0 = 0; b0 < nblocks && e == hipSuccess; b0 += sc.chunk) {
         const int64_t n = std::min(sc.chunk, nblocks - b0);
-        hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(GT), mx.total, s, p, ic, est ? *est : kNoEst, eq_source, ntiles,
+        if (bio) hipLaunchKernelGGL(kern_burst, dim3((unsigned)n), dim3(GT), mx.total, s, p, ic, *est, eq_source, ntiles, mode, 0, (int)tab,
+                                    TileArgs{ sc.base, tile_elems, b0, mx.off, mx.rtc, 0, p.N }, out, in, f_eq, *bio);
+        else hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(GT), mx.total, s, p, ic, est ? *est : kNoEst, eq_source, ntiles,
                            mode, 0, (int)tab, TileArgs{ sc.base, tile_elems, b0, mx.off, mx.rtc, 0, p.N }, out, in, f_eq);
         e = hipGetLastError();
     }

@@ -81,6 +81,11 @@ struct Plan {
     // the preamble-equalised receive kernels of a run-time instantiated shape, built in the background after set_channel_estimator when they
     // are neither cached nor quick to compile: 0 compiling (estimated calls run on the generic family meanwhile), 1 ready, -1 failed (they stay there)
     std::shared_ptr<std::atomic<int>> jit_pre_pending;
+    // the gather-load receive kernels (JIT_PART_RX_BURST) of a run-time instantiated shape, the kernels of demodulate_bursts: requested by
+    // set_channel_estimator, or by the first such call of a handle that switched to the tuned kernels later.  Only demodulate_bursts reads this
+    // state; while the part is not there (0 compiling, -1 failed) that call runs on the generic family
+    bool jit_burst_ready = false;
+    std::shared_ptr<std::atomic<int>> jit_burst_pending;
 
     // a *_host call cuts its batch into chunks, one launch each: the family (and the preamble-equalised kernels' availability) it starts
     // with is the one all of its chunks run on, so that a background instantiation finishing meanwhile cannot change the rounding inside
@@ -448,7 +453,20 @@ hipError_t rx_launch(Plan& pl, const gfdm::IcParams& ic, int mode, cf* out, cons
     const int family = pl.current_family();
     if (family == gfdm::FAMILY_ROWLANE) return gfdm::launch_rowlane_receive(pl.dp, ic, est, pl.d_twT, mode, out, in, f_eq, nblocks, s);
     bool tuned = family == gfdm::FAMILY_ROWLANE_JIT;
-    if (tuned && est && pl.pinned_pre >= 0) tuned = pl.pinned_pre == 1;
+    if (tuned && gfdm::burst_io(est)) {
+        // demodulate_bursts: its own part, its own state (never compiled inside the call: the device entry point is graph-capturable)
+        if (!pl.jit_burst_ready) {
+            if (!pl.jit_burst_pending) {
+                pl.jit_burst_pending = std::make_shared<std::atomic<int>>(0);
+                gfdm::jit_prepare_async(pl.dp.M, pl.dp.K, pl.dp.L, 1u << gfdm::JIT_PART_RX_BURST, pl.device, pl.jit_burst_pending);
+            } else if (pl.jit_burst_pending->load(std::memory_order_acquire) == 1) {
+                pl.jit_burst_ready = true;
+                pl.jit_burst_pending.reset();
+            }
+        }
+        tuned = pl.jit_burst_ready;
+    }
+    else if (tuned && est && pl.pinned_pre >= 0) tuned = pl.pinned_pre == 1;
     else if (tuned && est && pl.jit_pre_pending) {
         const int st = pl.jit_pre_pending->load(std::memory_order_acquire);
         if (st == 1) pl.jit_pre_pending.reset(); else tuned = false;       // still compiling (or failed): this estimated call runs on the generic family
@@ -619,6 +637,7 @@ int gfdm_hip_set_dft_matrix_cores(int mode)
 int gfdm_hip_jit_build_for_testing(int timeslots, int subcarriers, int overlap, int part)
 {
     std::string why;
+    if (part > gfdm::JIT_PART_EST) return fail(GFDM_HIP_EINVAL, "part must be 0 .. 4 (the later parts build through gfdm_hip_precompile)");
     if (gfdm::jit_build_only(timeslots, subcarriers, overlap, part, why)) return GFDM_HIP_OK;
     return fail(GFDM_HIP_EINVAL, why.c_str());
 }
@@ -1498,6 +1517,19 @@ int est_attach(Plan& pl, const gfdm_hip_channel_estimator*& slot, const gfdm_hip
             pl.jit_pre_pending = std::make_shared<std::atomic<int>>(0);
             gfdm::jit_prepare_async(M, K, L, 1u << gfdm::JIT_PART_RX_PREAMBLE, pl.device, pl.jit_pre_pending);
         }
+        // ... and the kernels of demodulate_bursts (JIT_PART_RX_BURST), under a state of their own that only that call consults: whatever
+        // happens to this part -- still compiling, failed -- the *_estimated_* calls launch what they always launched, and attaching succeeds
+        if (!pl.jit_burst_ready && !pl.jit_burst_pending) {
+            if (mode == 1 || M <= 16 || gfdm::jit_cached(M, K, L, gfdm::JIT_PART_RX_BURST) || !gfdm::generic_supports(M, K, false)) {
+                std::string why;
+                DeviceGuard guard(pl.device);
+                if (gfdm::jit_prepare(M, K, L, 1u << gfdm::JIT_PART_RX_BURST, why)) pl.jit_burst_ready = true;
+                else pl.jit_burst_pending = std::make_shared<std::atomic<int>>(-1);      // failed: demodulate_bursts stays on the generic family
+            } else {
+                pl.jit_burst_pending = std::make_shared<std::atomic<int>>(0);
+                gfdm::jit_prepare_async(M, K, L, 1u << gfdm::JIT_PART_RX_BURST, pl.device, pl.jit_burst_pending);
+            }
+        }
     }
     slot = c;
     return GFDM_HIP_OK;
@@ -1633,6 +1665,129 @@ int gfdm_hip_advanced_receiver_work_estimated_host(gfdm_hip_advanced_receiver* a
     return est_call_host(a->plan, io, ep, out, in, rx_preamble, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, void* s) {
         return gfdm_hip_advanced_receiver_work_estimated_device(a, o, i, e, preamble_stride, noutput_size, nb, s);
     });
+}
+
+}  // extern "C"
+
+// ---- receivers that read their bursts straight from the capture: the burst extractor as the load stage of the estimating receivers ----
+
+namespace {
+
+// arguments of one demodulate_bursts call -> RxIo and estimator plan + BurstIo of the launch (the contract is in include/gfdm_hip.h)
+int bursts_call_io(const FrameIo& f, const Plan& pl, const gfdm_hip_channel_estimator* c, int64_t stream_len, int backoff, int preamble_offset,
+                   int noutput_size, int64_t n_bursts, gfdm::RxIo& io, gfdm::BurstEstPlan& ep)
+{
+    if (!f.configured) return fail(GFDM_HIP_EINVAL, "configure_frames has not been called on this handle");
+    if (!c) return fail(GFDM_HIP_EINVAL, "set_channel_estimator has not been called on this handle");
+    if (preamble_offset < 0 || (int64_t)preamble_offset + 2 * pl.dp.K > f.io.in_stride)
+        return fail(GFDM_HIP_EINVAL, "preamble_offset must be >= 0 and preamble_offset + 2 * fft_len <= frame_len");
+    if (backoff < 0) return fail(GFDM_HIP_EINVAL, "backoff must be >= 0");
+    if (stream_len < 0) return fail(GFDM_HIP_EINVAL, "stream_len must be >= 0");
+    if (n_bursts < 0) return fail(GFDM_HIP_EINVAL, "n_bursts must be >= 0");
+    int rc = frame_io_for_call(f, pl, noutput_size, io);
+    if (rc != GFDM_HIP_OK) return rc;
+    ep.est = c->ep;
+    ep.est.pre_stride = gfdm::EST_GATHER;          // marks the BurstIo behind the EstPlan (gfdm_plan.h, burst_io)
+    ep.io = gfdm::BurstIo{};
+    ep.io.backoff = backoff;
+    ep.io.pre = preamble_offset;
+    ep.io.cap_len = stream_len;
+    return GFDM_HIP_OK;
+}
+
+int bursts_device(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, gfdm::IcParams ic, int mode, void* out, const void* samples,
+                  int64_t stream_len, const void* offsets, const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
+                  int noutput_size, int64_t n_bursts, void* stream)
+{
+    gfdm::BurstEstPlan ep;
+    int rc = bursts_call_io(f, pl, c, stream_len, backoff, preamble_offset, noutput_size, n_bursts, ic.io, ep);
+    if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
+    if (!out || !offsets || (!samples && stream_len > 0)) return fail(GFDM_HIP_EINVAL, "NULL buffer");
+    if (n_bursts > 0x7fffffff) return fail(GFDM_HIP_EINVAL, "more than 2^31 - 1 bursts per call");
+    ep.io.cap = static_cast<const cf*>(samples);
+    ep.io.off = static_cast<const int64_t*>(offsets);
+    ep.io.rot = cfo_correction ? static_cast<const cf*>(sc_rot) : nullptr;
+    ep.io.count = static_cast<const int64_t*>(count);
+    DeviceGuard guard(pl.device);
+    if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    return status_of(rx_launch(pl, ic, mode, static_cast<cf*>(out), nullptr, nullptr, n_bursts, static_cast<hipStream_t>(stream), &ep.est));
+}
+
+struct DevMem {
+    void* p = nullptr;
+    ~DevMem() { if (p) (void)hipFree(p); }
+};
+
+// convenience, not a pipeline: capture and arrays to the device, ONE launch, result back (the handle's private stream)
+int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, const gfdm::IcParams& ic, int mode, float* out, const float* samples,
+                int64_t stream_len, const int64_t* offsets, const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction,
+                int noutput_size, int64_t n_bursts)
+{
+    gfdm::RxIo io{};
+    gfdm::BurstEstPlan ep;
+    int rc = bursts_call_io(f, pl, c, stream_len, backoff, preamble_offset, noutput_size, n_bursts, io, ep);
+    if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
+    if (!out || !offsets || (!samples && stream_len > 0)) return fail(GFDM_HIP_EINVAL, "NULL buffer");
+    DeviceGuard guard(pl.device);
+    if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const size_t n = (size_t)n_bursts, out_bytes = n * (size_t)io.nout * sizeof(cf);
+    DevMem d_s, d_args, d_out;
+    HIP_TRY(hipMalloc(&d_s.p, std::max<size_t>((size_t)stream_len * sizeof(cf), sizeof(cf))));
+    HIP_TRY(hipMalloc(&d_args.p, (n + 1) * sizeof(int64_t) + n * sizeof(cf)));
+    HIP_TRY(hipMalloc(&d_out.p, out_bytes));
+    int64_t* d_off = static_cast<int64_t*>(d_args.p);
+    int64_t* d_cnt = d_off + n;
+    cf* d_rot = reinterpret_cast<cf*>(d_cnt + 1);
+    if (stream_len) HIP_TRY(hipMemcpyAsync(d_s.p, samples, (size_t)stream_len * sizeof(cf), hipMemcpyHostToDevice, pl.stream));
+    HIP_TRY(hipMemcpyAsync(d_off, offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, pl.stream));
+    if (count) HIP_TRY(hipMemcpyAsync(d_cnt, count, sizeof(int64_t), hipMemcpyHostToDevice, pl.stream));
+    if (sc_rot) HIP_TRY(hipMemcpyAsync(d_rot, sc_rot, n * sizeof(cf), hipMemcpyHostToDevice, pl.stream));
+    rc = bursts_device(pl, f, c, ic, mode, d_out.p, d_s.p, stream_len, d_off, sc_rot ? d_rot : nullptr, count ? d_cnt : nullptr, backoff, preamble_offset,
+                       cfo_correction, noutput_size, n_bursts, pl.stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, pl.stream));
+    HIP_TRY(hipStreamSynchronize(pl.stream));
+    return GFDM_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gfdm_hip_receiver_demodulate_bursts_device(gfdm_hip_receiver* r, void* out, const void* samples, int64_t stream_len, const void* offsets,
+                                               const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
+                                               int noutput_size, int64_t n_bursts, void* stream)
+{
+    if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    return bursts_device(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+                         cfo_correction, noutput_size, n_bursts, stream);
+}
+
+int gfdm_hip_receiver_demodulate_bursts_host(gfdm_hip_receiver* r, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
+                                             const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction,
+                                             int noutput_size, int64_t n_bursts)
+{
+    if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    return bursts_host(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+                       cfo_correction, noutput_size, n_bursts);
+}
+
+int gfdm_hip_advanced_receiver_work_bursts_device(gfdm_hip_advanced_receiver* a, void* out, const void* samples, int64_t stream_len, const void* offsets,
+                                                  const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
+                                                  int noutput_size, int64_t n_bursts, void* stream)
+{
+    if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    return bursts_device(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+                         cfo_correction, noutput_size, n_bursts, stream);
+}
+
+int gfdm_hip_advanced_receiver_work_bursts_host(gfdm_hip_advanced_receiver* a, float* out, const float* samples, int64_t stream_len,
+                                                const int64_t* offsets, const float* sc_rot, const int64_t* count, int backoff, int preamble_offset,
+                                                int cfo_correction, int noutput_size, int64_t n_bursts)
+{
+    if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    return bursts_host(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+                       cfo_correction, noutput_size, n_bursts);
 }
 
 }  // extern "C"

@@ -121,8 +121,10 @@ hipError_t launch_rowlane_receive(const DevicePlan& p, const IcParams& ic, const
 #include <vector>
 namespace gfdm {
 void rader_host_table(int M, std::vector<cf>& tab);          // empty when the timeslot count has no Rader kernels
+// parts of a shape (one hiprtc program each): a handle prepares the ones its kind launches, the others load at first use
+enum { JIT_PART_RX = 0, JIT_PART_RX_IC = 1, JIT_PART_RX_PREAMBLE = 2, JIT_PART_MOD = 3, JIT_PART_EST = 4, JIT_PART_RX_BURST = 5, JIT_NUM_PARTS = 6 };
 struct JitCache {
-    std::atomic<const void*> part[5];
+    std::atomic<const void*> part[JIT_NUM_PARTS];
     JitCache() { for (auto& p : part) p.store(nullptr); }
 };
 hipError_t jit_launch_modulate(JitCache* cache, const DevicePlan& p, const TxParams& tx, const cf* twT, cf* out, const cf* in, int64_t nblocks, hipStream_t s);
@@ -138,8 +140,6 @@ void jit_quiesce();
 int api_fail(int code, const std::string& msg);
 int api_fail_hip(hipError_t e, const char* what);
 bool jit_eligible(int M, int K, int L);
-// parts of a shape (one hiprtc program each): a handle prepares the ones its kind launches, the others load at first use
-enum { JIT_PART_RX = 0, JIT_PART_RX_IC = 1, JIT_PART_RX_PREAMBLE = 2, JIT_PART_MOD = 3, JIT_PART_EST = 4, JIT_NUM_PARTS = 5 };
 bool jit_prepare(int M, int K, int L, unsigned parts, std::string& err);      // parts: bit p = part p
 bool jit_prepare_estimate(int M, int K, std::string& err);
 bool jit_build_only(int M, int K, int L, int part, std::string& err);
@@ -160,11 +160,36 @@ struct EstPlan {
     int pre_stride;       // receivers with EQ_PREAMBLE: samples between the preambles of successive blocks (0 = packed, 2K)
 };
 
+// Receivers that read their bursts straight from a capture (demodulate_bursts, contract in include/gfdm_hip.h): the burst extractor as
+// the load stage (gfdm_burstfetch.h).  Sample n of burst b is cap[off[b] - backoff + n] (zero outside [0, cap_len)) times
+// (conj(r_b) / |r_b|)^n; the block starts at n = RxIo::in_offset, the preamble at n = pre.
+// These kernels are instantiations of their own (EQ_BURST; k_generic_receive_burst) that take BurstIo as one more, LAST kernel argument:
+// the argument layout of every other kernel -- and with it its code and its registers -- stays what it was (grown by these fields, EstPlan
+// moved the arguments behind it and hipcc merged their scalar loads differently).  On the host a launch carries it behind its EstPlan
+// (BurstEstPlan, marked by pre_stride == EST_GATHER), so the launchers keep their signatures; without it a launch is what it always was.
+struct BurstIo {
+    const cf* cap;            // the capture
+    int64_t cap_len;
+    const int64_t* off;       // [nblocks] burst offsets
+    const cf* rot;            // [nblocks] r_b, nullptr = no rotation
+    const int64_t* count;     // nullptr or one value: bursts from clamp(*count, 0, nblocks) on read nothing and yield zeros
+    int backoff, pre;
+};
+constexpr int EST_GATHER = -1;    // EstPlan::pre_stride of a BurstEstPlan (no other launch has a negative stride)
+struct BurstEstPlan { EstPlan est; BurstIo io; };
+#ifndef __HIPCC_RTC__
+inline const BurstIo* burst_io(const EstPlan* est)
+{
+    return (est && est->pre_stride == EST_GATHER) ? &reinterpret_cast<const BurstEstPlan*>(est)->io : nullptr;
+}
+#endif
+
 // how a receiver launch gets its one-tap equaliser
 enum EqSource {
     EQ_NONE = 0,
     EQ_VECTOR = 1,        // f_eq: N bins per block (generic_work_equalize)
-    EQ_PREAMBLE = 2       // f_eq points at the received preambles; the kernel runs the channel estimator itself
+    EQ_PREAMBLE = 2,      // f_eq points at the received preambles; the kernel runs the channel estimator itself
+    EQ_BURST = 3          // EQ_PREAMBLE with block and preamble gathered from a capture (BurstIo): separate instantiations of the row-lane kernels
 };
 
 // interference-cancellation rounds of k_row_receive (gfdm_rowlane_impl.h): vector ALU, vector ALU with a real even IC kernel, matrix cores

@@ -13,7 +13,7 @@ typedef const void* const* KernelList;        // the kernels of one part of a sh
 #define GFDM_ROWLANE_PART(K_, M_, L_, P_) rowlane_##K_##_##M_##_##L_##_p##P_
 #define X(K_, M_, L_)                                                                                                                  \
     extern const KernelList GFDM_ROWLANE_PART(K_, M_, L_, 0), GFDM_ROWLANE_PART(K_, M_, L_, 1), GFDM_ROWLANE_PART(K_, M_, L_, 2),       \
-        GFDM_ROWLANE_PART(K_, M_, L_, 3), GFDM_ROWLANE_PART(K_, M_, L_, 4);
+        GFDM_ROWLANE_PART(K_, M_, L_, 3), GFDM_ROWLANE_PART(K_, M_, L_, 4), GFDM_ROWLANE_PART(K_, M_, L_, 5);
 GFDM_ROW_SHAPES(X)
 #undef X
 
@@ -26,7 +26,7 @@ KernelList compiled_part(int K, int M, int L, int part)
     if (K == K_ && M == M_ && (L < 0 || L == L_))                                                                                      \
         return std::array<KernelList, JIT_NUM_PARTS>{ GFDM_ROWLANE_PART(K_, M_, L_, 0), GFDM_ROWLANE_PART(K_, M_, L_, 1),              \
                                                       GFDM_ROWLANE_PART(K_, M_, L_, 2), GFDM_ROWLANE_PART(K_, M_, L_, 3),              \
-                                                      GFDM_ROWLANE_PART(K_, M_, L_, 4) }[part];
+                                                      GFDM_ROWLANE_PART(K_, M_, L_, 4), GFDM_ROWLANE_PART(K_, M_, L_, 5) }[part];
     GFDM_ROW_SHAPES(X)
 #undef X
     return nullptr;
@@ -75,7 +75,10 @@ hipError_t launch_rowlane_receive(const DevicePlan& p, const IcParams& ic, const
     DevicePlan a_p = p;
     IcParams a_ic = ic;
     EstPlan a_est = est ? *est : kNoEst;
-    void* args[] = { &a_p, &a_ic, &a_est, &twT, &out, &in, &f_eq, &nblocks };
+    BurstIo a_bio = burst_io(est) ? *burst_io(est) : BurstIo{};
+    void* args8[] = { &a_p, &a_ic, &a_est, &twT, &out, &in, &f_eq, &nblocks };
+    void* args9[] = { &a_p, &a_ic, &a_est, &twT, &out, &in, &f_eq, &nblocks, &a_bio };      // k_row_receive_burst: BurstIo is its last argument
+    void** args = burst_io(est) ? args9 : args8;
     return launch(compiled_part(p.K, p.M, p.L, c.v.part), c, p.K, p.M, nblocks, s, args);
 }
 

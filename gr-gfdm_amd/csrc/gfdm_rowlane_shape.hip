@@ -22,6 +22,7 @@ template <int I> const void* kernel()
     constexpr rowvar::Variant v = kPart.v[I];
     if constexpr (PART == JIT_PART_MOD) return reinterpret_cast<const void*>(k_row_modulate<K, M, L, v.tx>);
     else if constexpr (PART == JIT_PART_EST) return reinterpret_cast<const void*>(k_row_estimate<K, M>);
+    else if constexpr (PART == JIT_PART_RX_BURST) return reinterpret_cast<const void*>(k_row_receive_burst<K, M, L, v.mode, v.ick>);
     else return reinterpret_cast<const void*>(k_row_receive<K, M, L, v.mode, v.eq, v.ick>);
 }
 

@@ -11,6 +11,7 @@ namespace rowvar {
 
 // One kernel of a part (JIT_PART_*, gfdm_plan.h):
 //   JIT_PART_RX, JIT_PART_RX_IC, JIT_PART_RX_PREAMBLE   k_row_receive<K, M, L, mode, eq, ick>
+//   JIT_PART_RX_BURST                                   k_row_receive_burst<K, M, L, mode, ick>
 //   JIT_PART_MOD                                        k_row_modulate<K, M, L, tx>
 //   JIT_PART_EST                                        k_row_estimate<K, M>
 struct Variant { int part, mode, eq, ick, tx; };
@@ -43,6 +44,11 @@ constexpr PartVariants part_variants(int K, int M, int part)
         t.add(RX_IC, EQ_PREAMBLE, ICK_GENERAL); t.add(RX_IC, EQ_PREAMBLE, ICK_REALSYM);
         if (mx) t.add(RX_IC, EQ_PREAMBLE, ICK_MFMA);
         break;
+    case JIT_PART_RX_BURST:        // the same with block and preamble gathered from a capture (BurstIo)
+        t.add(RX_FD, EQ_BURST, ICK_GENERAL); t.add(RX_DEMOD, EQ_BURST, ICK_GENERAL);
+        t.add(RX_IC, EQ_BURST, ICK_GENERAL); t.add(RX_IC, EQ_BURST, ICK_REALSYM);
+        if (mx) t.add(RX_IC, EQ_BURST, ICK_MFMA);
+        break;
     case JIT_PART_MOD:             // plain, behind the resource mapper, framed (TxParams)
         for (int tx = 0; tx < 3; ++tx) t.add(0, EQ_NONE, ICK_GENERAL, tx);
         break;
@@ -70,8 +76,9 @@ inline Choice select_receive(const DevicePlan& p, const IcParams& ic, const EstP
 {
     const bool rounds = (mode == RX_IC && ic.ic_iter > 0);
     const int ick = !rounds ? ICK_GENERAL : (ic_mfma_applies(p, ic) && rowgeom::ic_mfma(p.K, p.M)) ? ICK_MFMA : p.ic_real_sym ? ICK_REALSYM : ICK_GENERAL;
-    return find(p.K, p.M, Variant{ est ? JIT_PART_RX_PREAMBLE : rounds ? JIT_PART_RX_IC : JIT_PART_RX, mode == RX_FD ? RX_FD : rounds ? RX_IC : RX_DEMOD,
-                                   est ? EQ_PREAMBLE : f_eq ? EQ_VECTOR : EQ_NONE, ick, 0 });
+    const bool gather = burst_io(est) != nullptr;
+    return find(p.K, p.M, Variant{ gather ? JIT_PART_RX_BURST : est ? JIT_PART_RX_PREAMBLE : rounds ? JIT_PART_RX_IC : JIT_PART_RX,
+                                   mode == RX_FD ? RX_FD : rounds ? RX_IC : RX_DEMOD, gather ? EQ_BURST : est ? EQ_PREAMBLE : f_eq ? EQ_VECTOR : EQ_NONE, ick, 0 });
 }
 
 inline Choice select_modulate(const DevicePlan& p, const TxParams& tx)
@@ -85,7 +92,7 @@ struct Geometry { unsigned grid, block; size_t lds; };       // lds: dynamic LDS
 
 constexpr Geometry geometry(int K, int M, const Variant& v, int64_t nblocks)
 {
-    const bool pre = (v.eq == EQ_PREAMBLE);
+    const bool pre = (v.eq == EQ_PREAMBLE || v.eq == EQ_BURST);
     size_t lds = rowgeom::lds_bytes(K, pre ? M + 2 : M);                // EQ_PREAMBLE: two more tile columns for the preamble halves
     if (pre || v.part == JIT_PART_EST) lds += rowgeom::est_bytes(K);    // the estimate behind the tiles
     if (v.ick == ICK_MFMA) lds += rowgeom::ic_mfma_edge_bytes(K);       // behind everything else: the wavefronts' edge rows of the IcMfma rounds

@@ -167,6 +167,10 @@ def lib():
         "gfdm_hip_receiver_demodulate_estimated_device": (i32, [vp, vp, vp, vp, i32, i32, i64, vp]),
         "gfdm_hip_advanced_receiver_work_estimated_host": (i32, [vp, vp, vp, vp, i32, i32, i64]),
         "gfdm_hip_advanced_receiver_work_estimated_device": (i32, [vp, vp, vp, vp, i32, i32, i64, vp]),
+        "gfdm_hip_receiver_demodulate_bursts_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64]),
+        "gfdm_hip_receiver_demodulate_bursts_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
+        "gfdm_hip_advanced_receiver_work_bursts_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64]),
+        "gfdm_hip_advanced_receiver_work_bursts_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
         "gfdm_hip_burst_sync_create": (i32, [ctypes.POINTER(vp), i32, i32, vp, i32, i64, i32]),
         "gfdm_hip_burst_sync_destroy": (i32, [vp]),
         "gfdm_hip_burst_sync_fft_len": (i32, [vp]),
@@ -275,7 +279,8 @@ def set_jit(mode):
 
 def precompile(timeslots, subcarriers, overlap, parts=0):
     """gfdm_hip_precompile: compile the tuned kernels of a shape into the disk cache without creating a handle (no GPU needed).
-    parts: bit mask (receive 1, receive + IC 2, preamble-equalised receive 4, modulate 8, estimator 16), 0 = all."""
+    parts: bit mask (receive 1, receive + IC 2, preamble-equalised receive 4, modulate 8, estimator 16, preamble-equalised receive
+    straight from a capture -- demodulate_bursts -- 32), 0 = all."""
     _check(lib().gfdm_hip_precompile(int(timeslots), int(subcarriers), int(overlap), int(parts)))
 
 
@@ -483,6 +488,43 @@ class _Kernel:
         _check(getattr(L, self._estimated_prefix + "_host")(self._h, res.ctypes.data, a.ctypes.data, pre.ctypes.data, int(preamble_stride), nout_arg, nb))
         return res
 
+    def demodulate_bursts(self, samples, offsets, sc_rot=None, count=None, backoff=0, preamble_offset=0, cfo_correction=True, noutput_size=None,
+                          out=None, stream=None):
+        """The bursts at `offsets` of the capture `samples`, demodulated straight from it: BurstExtractor.extract (offset - backoff, zero
+        outside the capture, CFO rotation by sc_rot) as the load stage of demodulate_estimated, preamble at preamble_offset of each burst.
+        Needs configure_frames and set_channel_estimator.  count (one int64, e.g. detect's): rows from count on are zeros.
+        r = sync.detect(...) feeds it as demodulate_bursts(samples, r["frame_start"], r["sc_rot"], r["count"], ...).
+        Torch device tensors run the device entry point (no allocation beyond `out`, no synchronisation), numpy arrays the host one."""
+        L = lib()
+        if getattr(self, "_estimator", None) is None:
+            raise ValueError("set_channel_estimator has not been called on this handle")
+        nout_arg = -1 if noutput_size is None else int(noutput_size)
+        _, nout, _ = self._layout(True, nout_arg)
+        args = (int(backoff), int(preamble_offset), int(bool(cfo_correction)), nout_arg)
+        if _is_tensor(samples):
+            import torch
+            n = offsets.numel()
+            out = torch.empty(n, nout, dtype=torch.complex64, device=samples.device) if out is None else out
+            rp = None if sc_rot is None else _dev_arg(sc_rot, torch.complex64, n, "sc_rot", self._dev)
+            cp = None if count is None else _dev_arg(count, torch.int64, 1, "count", self._dev)
+            _check(getattr(L, self._bursts_prefix + "_device")(self._h, self._dp(out, n * nout, "out"), self._dp(samples, samples.numel(), "samples"),
+                                                              samples.numel(), _dev_arg(offsets, torch.int64, n, "offsets", self._dev), rp, cp, *args, n,
+                                                              self._sp(stream)))
+            return out
+        a = _c64(samples).ravel()
+        off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+        n = off.size
+        rot = None if sc_rot is None else _c64(sc_rot).ravel()
+        if rot is not None and rot.size != n:
+            raise RuntimeError("sc_rot has %d elements, expected %d" % (rot.size, n))
+        cnt = None if count is None else np.ascontiguousarray(count, dtype=np.int64).ravel()
+        if cnt is not None and cnt.size != 1:
+            raise RuntimeError("count has %d elements, expected 1" % cnt.size)
+        res = np.empty((n, nout), np.complex64)
+        _check(getattr(L, self._bursts_prefix + "_host")(self._h, res.ctypes.data, a.ctypes.data, a.size, off.ctypes.data,
+                                                        None if rot is None else rot.ctypes.data, None if cnt is None else cnt.ctypes.data, *args, n))
+        return res
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h and _lib is not None and self._destroy:
@@ -574,6 +616,7 @@ class Demodulator(_Kernel):
     _configure_frames = "gfdm_hip_receiver_configure_frames"
     _io_layout = "gfdm_hip_receiver_io_layout"
     _estimated_prefix = "gfdm_hip_receiver_demodulate_estimated"
+    _bursts_prefix = "gfdm_hip_receiver_demodulate_bursts"
     _set_estimator = "gfdm_hip_receiver_set_channel_estimator"
 
     def __init__(self, timeslots, subcarriers, overlap, taps, device=0):
@@ -650,6 +693,7 @@ class AdvancedReceiver(_Kernel):
     _configure_frames = "gfdm_hip_advanced_receiver_configure_frames"
     _io_layout = "gfdm_hip_advanced_receiver_io_layout"
     _estimated_prefix = "gfdm_hip_advanced_receiver_work_estimated"
+    _bursts_prefix = "gfdm_hip_advanced_receiver_work_bursts"
     _set_estimator = "gfdm_hip_advanced_receiver_set_channel_estimator"
 
     def __init__(self, timeslots, subcarriers, overlap, taps, subcarrier_map, ic_iter, constellation_points,

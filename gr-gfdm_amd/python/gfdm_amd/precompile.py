@@ -1,6 +1,6 @@
 """Fill the code-object cache of the run-time instantiated kernels ahead of time (deployment step; no GPU needed):
 
-    python -m gfdm_amd.precompile <timeslots> <subcarriers> <overlap> [--parts rx,ic,pre,mod,est] [more shapes: M K L ...]
+    python -m gfdm_amd.precompile <timeslots> <subcarriers> <overlap> [--parts rx,ic,pre,mod,est,burst] [more shapes: M K L ...]
 
 Shapes that are compiled into the library need nothing and are reported as such; shapes only the generic family serves are refused.
 See gfdm_hip_precompile / gfdm_hip_set_jit in include/gfdm_hip.h.
@@ -10,7 +10,7 @@ import time
 
 from . import capi
 
-PARTS = {"rx": 1, "ic": 2, "pre": 4, "mod": 8, "est": 16}
+PARTS = {"rx": 1, "ic": 2, "pre": 4, "mod": 8, "est": 16, "burst": 32}
 
 
 def main(argv=None):

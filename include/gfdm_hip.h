@@ -87,7 +87,7 @@ int gfdm_hip_force_generic_family_for_testing(int enable);
 int gfdm_hip_set_jit(int mode);
 /* Deployment step: compile the tuned kernels of a shape into the disk cache WITHOUT creating a handle (no GPU needed), so that the first
  * flowgraph using the shape starts with them.  parts: bit 0 receive, 1 receive + IC, 2 preamble-equalised receive, 3 modulate,
- * 4 estimator (0 = all).  Returns GFDM_HIP_OK also for shapes that are compiled into the library; GFDM_HIP_EUNSUPPORTED for shapes only
+ * 4 estimator, 5 preamble-equalised receive straight from a capture (demodulate_bursts) (0 = all).  Returns GFDM_HIP_OK also for shapes that are compiled into the library; GFDM_HIP_EUNSUPPORTED for shapes only
  * the generic family serves.  Command line: python -m gfdm_amd.precompile <timeslots> <subcarriers> <overlap> [...]. */
 int gfdm_hip_precompile(int timeslots, int subcarriers, int overlap, unsigned parts);
 /* Stops the background builds of gfdm_hip_set_jit modes 2 / 3: what is still queued is dropped (those handles stay on the generic kernels), the
@@ -115,7 +115,8 @@ int gfdm_hip_set_ic_matrix_cores(int mode);
  * (csrc/gfdm_rader.hip; kernel_name "generic_rader"); frames / demapper and the self-estimating receivers of that shape stay on the generic
  * kernels.  Modes 0 and 2 keep the dense forms for that shape too (A/B, tests). */
 int gfdm_hip_set_dft_matrix_cores(int mode);
-/* TEST HOOK: compile (or find in the disk cache) part 0..4 (receive, receive + IC, preamble-equalised receive, modulate, estimator) of
+/* TEST HOOK: compile (or find in the disk cache) part 0..4 (receive, receive + IC, preamble-equalised receive, modulate, estimator; the
+ * sixth part, the receive kernels of demodulate_bursts, builds through gfdm_hip_precompile, bit 5) of
  * the row-lane kernels for a shape through hiprtc WITHOUT loading it --
  * needs no GPU, so the CPU-side tests can check that the embedded kernel sources build. */
 int gfdm_hip_jit_build_for_testing(int timeslots, int subcarriers, int overlap, int part);
@@ -359,6 +360,44 @@ int gfdm_hip_advanced_receiver_work_estimated_host(gfdm_hip_advanced_receiver* a
                                                    int preamble_stride, int noutput_size, int64_t nblocks);
 int gfdm_hip_advanced_receiver_work_estimated_device(gfdm_hip_advanced_receiver* a, void* out, const void* in, const void* rx_preamble,
                                                      int preamble_stride, int noutput_size, int64_t nblocks, void* stream);
+
+/* ---- receivers that read detected bursts straight from the capture ----
+ * The chain  burst_extractor -> *_estimated_*  in ONE kernel: the extractor's fetch (offset per burst, zero outside the stream, per-sample
+ * CFO rotation) is the receiver kernel's load stage, so the extracted burst buffer never exists in memory.  The handle needs a frame
+ * layout (frame_len, cp_len) from configure_frames and an attached channel estimator.  For burst b < n_bursts define the virtual burst
+ *     e_b[n] = s[off_b - backoff + n] * rho_b^n          0 <= n < frame_len      (n counted from the burst start, as the extractor below)
+ *     s[i]   = 0 for i < 0 or i >= stream_len            (the extractor's rule, including its extension past the end)
+ *     rho_b  = conj(r_b) / |r_b|;  rho_b = 1 when sc_rot is NULL, r_b == 0 or cfo_correction == 0
+ * The result for burst b is what the *_estimated_* call above returns for in = e_b and rx_preamble = e_b + preamble_offset: the same
+ * demapping, noutput_size, IC iterations, decision rule and phase compensation; per burst the buffer sizes are those of
+ * *_io_layout(estimated = 1, noutput_size).  Only the samples the kernel needs are read: n in [cp_len, cp_len + block_size) and
+ * n in [preamble_offset, preamble_offset + 2 fft_len).  Both paths fetch through one device function; their results differ by the
+ * compiler's contraction of the rotation only (tested: within 1e-5 relative).
+ * There is no `scale` argument: the preamble equaliser divides any per-burst gain out.
+ * count: NULL, or one int64 (the detector's `count` output).  live = count ? clamp(*count, 0, n_bursts) : n_bursts; output rows
+ * b >= live are written as zeros and their workgroups read nothing from the capture -- the detector's spare slots (frame_start = -1)
+ * are exactly those rows, so detect(max_bursts = n) followed by this call is a fixed-shape chain.
+ * *_device: samples, offsets (int64[n_bursts]), sc_rot (complex[n_bursts] or NULL) and count are device arrays -- the synchroniser's and
+ * the detector's outputs as they are; the call neither allocates nor synchronises and is hipGraph-capturable.  (A receiver on run-time
+ * instantiated kernels requests this call's kernels in set_channel_estimator -- at once when they are cached or quick to build, otherwise
+ * on the background pool -- under a state of their own: until they are there, or if they fail to build, THIS call runs on the generic
+ * kernel family, same results; what the *_estimated_* calls launch, and whether set_channel_estimator succeeds, does not depend on them.)
+ * *_host: a convenience, not a pipeline: copies the capture and the arrays to the device, makes one launch and copies the result back.
+ * GFDM_HIP_EINVAL (message in gfdm_hip_last_error()): no configure_frames; no estimator attached; preamble_offset < 0 or
+ * preamble_offset + 2 fft_len > frame_len; backoff < 0; stream_len < 0; n_bursts < 0; noutput_size as the *_estimated_* calls refuse it.
+ * n_bursts == 0 returns GFDM_HIP_OK without a launch. */
+int gfdm_hip_receiver_demodulate_bursts_device(gfdm_hip_receiver* r, void* out, const void* samples, int64_t stream_len, const void* offsets,
+                                               const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
+                                               int noutput_size, int64_t n_bursts, void* stream);
+int gfdm_hip_receiver_demodulate_bursts_host(gfdm_hip_receiver* r, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
+                                             const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction,
+                                             int noutput_size, int64_t n_bursts);
+int gfdm_hip_advanced_receiver_work_bursts_device(gfdm_hip_advanced_receiver* a, void* out, const void* samples, int64_t stream_len, const void* offsets,
+                                                  const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
+                                                  int noutput_size, int64_t n_bursts, void* stream);
+int gfdm_hip_advanced_receiver_work_bursts_host(gfdm_hip_advanced_receiver* a, float* out, const float* samples, int64_t stream_len,
+                                                const int64_t* offsets, const float* sc_rot, const int64_t* count, int backoff, int preamble_offset,
+                                                int cfo_correction, int noutput_size, int64_t n_bursts);
 
 /* ---- resource_mapper_kernel_cc (include/gfdm/resource_mapper_kernel_cc.h:38-60, lib/resource_mapper_kernel_cc.cc) -----------------
  * The stand-alone form of the mapper / demapper that the transmitter and the *_frames_* receivers above have fused into their
