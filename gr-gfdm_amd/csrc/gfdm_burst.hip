@@ -96,8 +96,16 @@ __device__ void block_argmax(unsigned long long key, unsigned long long* dst)
     if (threadIdx.x == 0) atomicMax(dst, best);
 }
 
-// ac at the position whose 2K samples start at x:  2 sum_{n<K} conj(x[n]) x[n+K] / sum_{n<2K} |x[n]|^2, 0 where the energy is 0
-__device__ __forceinline__ cf ac_at(const cf* x, int K)
+// an sc16 capture read as complex samples (ac_at straight from global memory)
+struct Sc16View {
+    const gfdm::sc16_io* p;
+    __device__ __forceinline__ cf operator[](int n) const { return gfdm::sc16_to_cf(p[n]); }
+};
+
+// ac at the position whose 2K samples start at x:  2 sum_{n<K} conj(x[n]) x[n+K] / sum_{n<2K} |x[n]|^2, 0 where the energy is 0.
+// X: const cf* or Sc16View -- the sums are the same instructions in the same order on the same fp32 values.
+template <class X>
+__device__ __forceinline__ cf ac_at(X x, int K)
 {
     float cr0 = 0.f, ci0 = 0.f, e0 = 0.f, cr1 = 0.f, ci1 = 0.f, e1 = 0.f;   // two chains: even / odd n
     int n = 0;
@@ -127,7 +135,7 @@ __device__ __forceinline__ cf ac_at(const cf* x, int K)
 // |ac| is computed segment by segment (kTile positions each) from i0 - cp (rounded down to a whole segment) up to the tile itself, so
 // LDS holds kTile + 2K samples whatever cp is.  On return xs[0 .. kTile + 2K - 1) holds the window's samples from i0 on (zero past W)
 // -- the fine stage correlates straight out of it -- and *ac_n the lane's own ac.
-__device__ float tile_ic(const cf* __restrict__ win, int W, int K, int cp, int P, int i0, cf* xs, float* mag, cf* ac_n)
+__device__ float tile_ic(const void* __restrict__ win, int fmt, int W, int K, int cp, int P, int i0, cf* xs, float* mag, cf* ac_n)
 {
     const int t = threadIdx.x, n = i0 + t;
     const int lo = std::max(0, i0 - cp), hi = std::min(P, i0 + kTile);
@@ -137,12 +145,12 @@ __device__ float tile_ic(const cf* __restrict__ win, int W, int K, int cp, int P
     for (int seg = i0 - (i0 - lo + kTile - 1) / kTile * kTile; seg <= i0; seg += kTile) {
         for (int j = t; j < span; j += kTile) {
             const int g = seg + j;
-            xs[j] = (g >= 0 && g < W) ? win[g] : czero();
+            xs[j] = (g >= 0 && g < W) ? gfdm::capture_load(win, g, fmt) : czero();
         }
         __syncthreads();
         const int m = seg + t;
         cf c = czero();
-        if (m >= lo && m < hi) c = ac_at(xs + t, K);
+        if (m >= lo && m < hi) c = ac_at((const cf*)(xs + t), K);
         mag[t] = sqrtf(c.x * c.x + c.y * c.y);
         if (seg == i0) *ac_n = c;
         __syncthreads();
@@ -156,7 +164,8 @@ __device__ float tile_ic(const cf* __restrict__ win, int W, int K, int cp, int P
 }
 
 struct SyncArgs {
-    const cf* samples;       // window w starts at samples[first + w stride], or at starts[w] when a start array is given
+    const void* samples;     // window w starts at sample first + w stride, or at starts[w] when a start array is given
+    int fmt;                 // gfdm::SampleFormat of samples
     int64_t first, stride, nwin;
     int64_t origin;          // stream index of samples[0] (host path: the uploaded span starts inside the caller's stream)
     int W, K, cp, P;
@@ -186,7 +195,7 @@ __global__ __launch_bounds__(kTile) void k_sync_ic(SyncArgs a, cf* __restrict__ 
         const int64_t st = window_start(a, w);
         if (st < 0) continue;       // empty slot: the key stays 0
         cf acn;
-        const float ic = tile_ic(a.samples + st, a.W, a.K, a.cp, a.P, i0, xs, mag, &acn);
+        const float ic = tile_ic(gfdm::capture_at(a.samples, st, a.fmt), a.fmt, a.W, a.K, a.cp, a.P, i0, xs, mag, &acn);
         if (n < a.P) {
             if (ac_out) ac_out[w * a.P + n] = acn;
             if (ic_out) ic_out[w * a.P + n] = ic;
@@ -209,7 +218,8 @@ __global__ __launch_bounds__(64) void k_sync_coarse(SyncArgs a, const unsigned l
             continue;
         }
         const unsigned long long k = key[w];
-        const cf c = ac_at(a.samples + st + key_index(k), a.K);
+        const void* x = gfdm::capture_at(a.samples, st + key_index(k), a.fmt);
+        const cf c = a.fmt == gfdm::SAMPLES_SC16 ? ac_at(Sc16View{ static_cast<const gfdm::sc16_io*>(x) }, a.K) : ac_at(static_cast<const cf*>(x), a.K);
         const float ang = atan2f(c.y, c.x);
         cfo[w] = ang * (float)(0.5 / M_PI);
         metric[w] = key_value(k);
@@ -241,7 +251,7 @@ __global__ __launch_bounds__(kTile) void k_sync_fine(SyncArgs a, const cf* __res
             q[m] = make_float2(p.x * c + p.y * s, p.x * s - p.y * c);
         }
         cf acn;
-        const float ic = tile_ic(a.samples + st, a.W, a.K, a.cp, a.P, i0, xs, mag, &acn);   // syncs after q is written
+        const float ic = tile_ic(gfdm::capture_at(a.samples, st, a.fmt), a.fmt, a.W, a.K, a.cp, a.P, i0, xs, mag, &acn);   // syncs after q is written
         float score = 0.f;
         if (n < a.P) {
             float re = 0.f, im = 0.f;
@@ -274,7 +284,7 @@ __global__ void k_sync_finalize(SyncArgs a, int64_t* __restrict__ frame_start, i
 }
 
 // out[b][n] = scale_b s[off_b - backoff + n] rot_b^n; one burst per blockIdx.y, samples strided over blockIdx.x
-__global__ __launch_bounds__(kTile) void k_extract(cf* __restrict__ out, const cf* __restrict__ s, int64_t stream_len, const int64_t* __restrict__ offsets,
+__global__ __launch_bounds__(kTile) void k_extract(cf* __restrict__ out, const void* __restrict__ s, int fmt, int64_t stream_len, const int64_t* __restrict__ offsets,
                                                    const float* __restrict__ scale, const cf* __restrict__ sc_rot, int correct, int burst_len, int backoff,
                                                    int64_t nbursts)
 {
@@ -293,7 +303,7 @@ __global__ __launch_bounds__(kTile) void k_extract(cf* __restrict__ out, const c
         const int64_t base = offsets[b] - backoff;
         const float g = scale ? scale[b] : 1.f;
         for (int n = blockIdx.x * kTile + threadIdx.x; n < burst_len; n += gridDim.x * kTile)
-            gfdm::dft::st_stream(out, b * burst_len + n, gfdm::burst_fetch(s, stream_len, base, n, g, rotate, phi));      // gfdm_burstfetch.h
+            gfdm::dft::st_stream(out, b * burst_len + n, gfdm::burst_fetch(s, fmt, stream_len, base, n, g, rotate, phi));      // gfdm_burstfetch.h
         __syncthreads();
     }
 }
@@ -312,7 +322,8 @@ constexpr int kScanMaxPer = 16;          // positions per lane and tile (one bit
 constexpr int kScanTiles = 4096;         // per is chosen so that a long stream has about this many tiles
 
 struct ScanArgs {
-    const cf* samples;
+    const void* samples;
+    int fmt;                 // gfdm::SampleFormat of samples
     int n, K, cp, P;         // stream_len, P = n - 2K positions
     int R, per, cap;         // min_distance, segments per tile, list entries per tile
     float thr;
@@ -333,13 +344,13 @@ size_t scan_lds(int K, int per) { return (size_t)(kTile + 2 * K) * sizeof(cf) + 
 // tile_ic for the segment at g (>= kTile) of a walk in ascending order with cp <= kTile: magp holds |ac| of the segment before, as
 // tile_ic left it, so only this segment's |ac| is computed (into magc).  The lane's sum runs over the same magnitudes in the same
 // ascending order as tile_ic's: the value is bit-equal.
-__device__ float segment_ic(const cf* __restrict__ win, int W, int K, int cp, int P, int g, cf* xs, const float* magp, float* magc)
+__device__ float segment_ic(const void* __restrict__ win, int fmt, int W, int K, int cp, int P, int g, cf* xs, const float* magp, float* magc)
 {
     const int t = threadIdx.x, n = g + t;
-    for (int j = t; j < kTile + 2 * K - 1; j += kTile) xs[j] = (g + j < W) ? win[g + j] : czero();
+    for (int j = t; j < kTile + 2 * K - 1; j += kTile) xs[j] = (g + j < W) ? gfdm::capture_load(win, g + j, fmt) : czero();
     __syncthreads();
     cf c = czero();
-    if (n < P) c = ac_at(xs + t, K);
+    if (n < P) c = ac_at((const cf*)(xs + t), K);
     magc[t] = sqrtf(c.x * c.x + c.y * c.y);
     __syncthreads();
     if (n < cp || n >= P) return 0.f;
@@ -374,10 +385,10 @@ __global__ __launch_bounds__(kTile) void k_detect_scan(ScanArgs a, int* __restri
         float* magc = mag + (s & 1) * kTile;            // this segment's |ac|; the other half holds the segment's before
         float ic;
         if (s > s_lo && a.cp <= kTile) {
-            ic = segment_ic(a.samples, a.n, a.K, a.cp, a.P, g, xs, mag + ((s & 1) ^ 1) * kTile, magc);
+            ic = segment_ic(a.samples, a.fmt, a.n, a.K, a.cp, a.P, g, xs, mag + ((s & 1) ^ 1) * kTile, magc);
         } else {
             cf acn;
-            ic = tile_ic(a.samples, a.n, a.K, a.cp, a.P, g, xs, magc, &acn);
+            ic = tile_ic(a.samples, a.fmt, a.n, a.K, a.cp, a.P, g, xs, magc, &acn);
         }
         const float val = (g + t < a.P) ? ic : -1.f;
         // running maxima from both ends: inside a wave by shuffles, across waves through wmax
@@ -464,10 +475,14 @@ __global__ __launch_bounds__(kTile) void k_detect_offsets(const int* __restrict_
     if (t == 0) *count = base;
 }
 
-// starts[slot] = clamp(peak - lead, 0, last) for the lowest nslots peaks (the rest of starts was preset to -1)
+// starts[slot] = clamp(peak - lead, 0, last) for the lowest nslots peaks, -1 (empty) for the slots from *count on.  The empty slots are
+// written here and not by a byte-pattern memset in front: as a node of a captured graph that memset left them positive from the second
+// replay on (measured: they then ran as windows at `last`), where a store does what it says on every replay.
 __global__ __launch_bounds__(kTile) void k_detect_scatter(const int* __restrict__ counts, const int* __restrict__ offs, const int* __restrict__ list, int cap,
-                                                          int ntiles, int lead, int64_t last, int64_t* __restrict__ starts, int64_t nslots)
+                                                          int ntiles, int lead, int64_t last, int64_t* __restrict__ starts, int64_t nslots,
+                                                          const int64_t* __restrict__ count)
 {
+    for (int64_t slot = *count + (int64_t)blockIdx.x * kTile + threadIdx.x; slot < nslots; slot += (int64_t)gridDim.x * kTile) starts[slot] = -1;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int c = std::min(counts[tile], cap), o = offs[tile];
         for (int k = threadIdx.x; k < c; k += kTile) {
@@ -478,6 +493,9 @@ __global__ __launch_bounds__(kTile) void k_detect_scatter(const int* __restrict_
 }
 
 size_t sync_lds(int K, bool fine) { return (size_t)(kTile + 2 * K + (fine ? 2 * K : 0)) * sizeof(cf) + kTile * sizeof(float); }
+
+// bytes of one sample of a capture: the host flavours upload it in the caller's format
+size_t sample_bytes(int fmt) { return fmt == gfdm::SAMPLES_SC16 ? sizeof(gfdm::sc16_io) : sizeof(cf); }
 
 // a device buffer that lives for one host call
 struct DevBuf {
@@ -534,15 +552,15 @@ int check_windows(const gfdm_hip_burst_sync* h, const void* samples, int64_t str
 }
 
 // enqueue the synchroniser; fused (frame_start != NULL) or the auto-correlation stage (ac / ic)
-SyncArgs grid_args(const gfdm_hip_burst_sync* h, const cf* samples, int64_t first, int64_t stride, int64_t n, int64_t origin)
+SyncArgs grid_args(const gfdm_hip_burst_sync* h, const void* samples, int fmt, int64_t first, int64_t stride, int64_t n, int64_t origin)
 {
-    return SyncArgs{ samples, first, stride, n, origin, h->W, h->K, h->cp, h->W - 2 * h->K, nullptr, 0, 0, 0 };
+    return SyncArgs{ samples, fmt, first, stride, n, origin, h->W, h->K, h->cp, h->W - 2 * h->K, nullptr, 0, 0, 0 };
 }
 
 // windows at starts[w] (device array of nstarts entries; windows w >= nstarts are empty), clamped to [0, stream_len - W]
-SyncArgs list_args(const gfdm_hip_burst_sync* h, const cf* samples, int64_t stream_len, const int64_t* starts, int64_t nstarts, int64_t n, int skip_empty)
+SyncArgs list_args(const gfdm_hip_burst_sync* h, const void* samples, int fmt, int64_t stream_len, const int64_t* starts, int64_t nstarts, int64_t n, int skip_empty)
 {
-    return SyncArgs{ samples, 0, 0, n, 0, h->W, h->K, h->cp, h->W - 2 * h->K, starts, nstarts, stream_len - h->W, skip_empty };
+    return SyncArgs{ samples, fmt, 0, 0, n, 0, h->W, h->K, h->cp, h->W - 2 * h->K, starts, nstarts, stream_len - h->W, skip_empty };
 }
 
 int sync_enqueue(gfdm_hip_burst_sync* h, const SyncArgs& a, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, cf* sc_rot, cf* ac, float* ic,
@@ -569,18 +587,19 @@ int sync_enqueue(gfdm_hip_burst_sync* h, const SyncArgs& a, int64_t* frame_start
 }
 
 // host path of the synchroniser: the span the windows cover goes up, the results come back
-int sync_host(gfdm_hip_burst_sync* h, const float* samples, int64_t first, int64_t stride, int64_t n, int64_t* frame_start, int64_t* coarse, float* cfo,
+int sync_host(gfdm_hip_burst_sync* h, const void* samples, int fmt, int64_t first, int64_t stride, int64_t n, int64_t* frame_start, int64_t* coarse, float* cfo,
               float* metric, float* sc_rot, float* ac, float* ic)
 {
     DeviceGuard guard(h->device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const int64_t span = (n - 1) * stride + h->W, P = h->W - 2 * h->K;
     DevBuf d_in, d_out;
-    BURST_TRY(d_in.alloc((size_t)span * sizeof(cf)));
+    const size_t sb = sample_bytes(fmt);
+    BURST_TRY(d_in.alloc((size_t)span * sb));
     const size_t n_res = (size_t)n * (2 * sizeof(int64_t) + 2 * sizeof(float) + sizeof(cf));
     const size_t n_stage = (size_t)n * P * (sizeof(cf) + sizeof(float));
     BURST_TRY(d_out.alloc(frame_start ? n_res : n_stage));
-    BURST_TRY(hipMemcpyAsync(d_in.p, samples + 2 * first, (size_t)span * sizeof(cf), hipMemcpyHostToDevice, h->stream));
+    BURST_TRY(hipMemcpyAsync(d_in.p, static_cast<const unsigned char*>(samples) + (size_t)first * sb, (size_t)span * sb, hipMemcpyHostToDevice, h->stream));
     unsigned char* o = static_cast<unsigned char*>(d_out.p);
     int rc;
     if (frame_start) {
@@ -589,7 +608,7 @@ int sync_host(gfdm_hip_burst_sync* h, const float* samples, int64_t first, int64
         cf* d_rot = reinterpret_cast<cf*>(d_co + n);
         float* d_cfo = reinterpret_cast<float*>(d_rot + n);
         float* d_met = d_cfo + n;
-        rc = sync_enqueue(h, grid_args(h, static_cast<const cf*>(d_in.p), 0, stride, n, first), d_fs, d_co, d_cfo, d_met, d_rot, nullptr, nullptr, h->stream);
+        rc = sync_enqueue(h, grid_args(h, d_in.p, fmt, 0, stride, n, first), d_fs, d_co, d_cfo, d_met, d_rot, nullptr, nullptr, h->stream);
         if (rc != GFDM_HIP_OK) return rc;
         BURST_TRY(hipMemcpyAsync(frame_start, d_fs, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
         BURST_TRY(hipMemcpyAsync(coarse, d_co, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -599,7 +618,7 @@ int sync_host(gfdm_hip_burst_sync* h, const float* samples, int64_t first, int64
     } else {
         cf* d_ac = reinterpret_cast<cf*>(o);
         float* d_ic = reinterpret_cast<float*>(d_ac + (size_t)n * P);
-        rc = sync_enqueue(h, grid_args(h, static_cast<const cf*>(d_in.p), 0, stride, n, first), nullptr, nullptr, nullptr, nullptr, nullptr, d_ac, d_ic, h->stream);
+        rc = sync_enqueue(h, grid_args(h, d_in.p, fmt, 0, stride, n, first), nullptr, nullptr, nullptr, nullptr, nullptr, d_ac, d_ic, h->stream);
         if (rc != GFDM_HIP_OK) return rc;
         if (ac) BURST_TRY(hipMemcpyAsync(ac, d_ac, (size_t)n * P * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
         if (ic) BURST_TRY(hipMemcpyAsync(ic, d_ic, (size_t)n * P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -693,7 +712,7 @@ DetectGeom detect_geom(const gfdm_hip_burst_sync* h, int64_t stream_len)
 }
 
 // scan -> ordered compaction -> fine stage over the window starts; count and the five outputs are device pointers
-int detect_enqueue(gfdm_hip_burst_sync* h, int64_t* count, const SyncOut& o, const cf* samples, int64_t stream_len, float threshold, int64_t R, int64_t lead,
+int detect_enqueue(gfdm_hip_burst_sync* h, int64_t* count, const SyncOut& o, const void* samples, int fmt, int64_t stream_len, float threshold, int64_t R, int64_t lead,
                    int64_t max_bursts, void* workspace, hipStream_t s)
 {
     const DetectGeom g = detect_geom(h, stream_len);
@@ -703,18 +722,17 @@ int detect_enqueue(gfdm_hip_burst_sync* h, int64_t* count, const SyncOut& o, con
     int* list = reinterpret_cast<int*>(ws + g.o_list);
     int64_t* starts = reinterpret_cast<int64_t*>(ws + g.o_starts);
     const int P = (int)(stream_len - 2 * h->K);
-    const ScanArgs a = { samples, (int)stream_len, h->K, h->cp, P, (int)std::min<int64_t>(R, P), g.per, g.cap, threshold };
+    const ScanArgs a = { samples, fmt, (int)stream_len, h->K, h->cp, P, (int)std::min<int64_t>(R, P), g.per, g.cap, threshold };
     hipLaunchKernelGGL(k_detect_scan, dim3((unsigned)g.ntiles), dim3(kTile), scan_lds(h->K, g.per), s, a, counts, list);
     BURST_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_detect_offsets, dim3(1), dim3(kTile), 0, s, (const int*)counts, offs, g.ntiles, count);
     BURST_TRY(hipGetLastError());
     if (max_bursts == 0) return GFDM_HIP_OK;
     const int64_t nslots = std::min(max_bursts, g.nstarts);
-    BURST_TRY(hipMemsetAsync(starts, 0xFF, (size_t)nslots * sizeof(int64_t), s));          // -1: empty slot
     hipLaunchKernelGGL(k_detect_scatter, dim3((unsigned)std::min(g.ntiles, 1024)), dim3(kTile), 0, s, (const int*)counts, (const int*)offs, (const int*)list, g.cap,
-                       g.ntiles, (int)lead, stream_len - h->W, starts, nslots);
+                       g.ntiles, (int)lead, stream_len - h->W, starts, nslots, (const int64_t*)count);
     BURST_TRY(hipGetLastError());
-    return sync_enqueue(h, list_args(h, samples, stream_len, starts, nslots, max_bursts, 1), o.frame_start, o.coarse, o.cfo, o.metric, o.sc_rot, nullptr, nullptr, s);
+    return sync_enqueue(h, list_args(h, samples, fmt, stream_len, starts, nslots, max_bursts, 1), o.frame_start, o.coarse, o.cfo, o.metric, o.sc_rot, nullptr, nullptr, s);
 }
 
 int extract_check(const gfdm_hip_burst_extractor* h, const void* out, const void* samples, int64_t stream_len, const void* offsets, int64_t n)
@@ -725,12 +743,186 @@ int extract_check(const gfdm_hip_burst_extractor* h, const void* out, const void
     return GFDM_HIP_OK;
 }
 
-int extract_enqueue(gfdm_hip_burst_extractor* h, cf* out, const cf* samples, int64_t stream_len, const int64_t* offsets, const float* scale, const cf* sc_rot,
+int extract_enqueue(gfdm_hip_burst_extractor* h, cf* out, const void* samples, int fmt, int64_t stream_len, const int64_t* offsets, const float* scale, const cf* sc_rot,
                     int64_t n, hipStream_t s)
 {
     const dim3 grid((unsigned)std::min((h->burst_len + kTile - 1) / kTile, 64), (unsigned)std::min<int64_t>(n, kMaxGridY));
-    hipLaunchKernelGGL(k_extract, grid, dim3(kTile), 0, s, out, samples, stream_len, offsets, scale, sc_rot, h->correct, h->burst_len, h->backoff, n);
+    hipLaunchKernelGGL(k_extract, grid, dim3(kTile), 0, s, out, samples, fmt, stream_len, offsets, scale, sc_rot, h->correct, h->burst_len, h->backoff, n);
     BURST_TRY(hipGetLastError());
+    return GFDM_HIP_OK;
+}
+
+}  // namespace
+
+// ---- the entry points that read a capture, once for both sample formats (fmt: gfdm::SampleFormat; `samples` is complex64 or interleaved
+// int16 accordingly, stream_len counts samples).  The public calls and their *_sc16_* twins at the end of the file are thin wrappers.
+namespace {
+
+int sync_find_frame_start_device(int fmt, gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                                const void* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows, void* stream)
+{
+    int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
+    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
+    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    return sync_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), static_cast<int64_t*>(frame_start),
+                        static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric), static_cast<cf*>(sc_rot), nullptr, nullptr,
+                        (hipStream_t)stream);
+}
+
+int sync_find_frame_start_host(int fmt, gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                              const void* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows)
+{
+    int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
+    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
+    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    return sync_host(h, samples, fmt, first, stride, n_windows, frame_start, coarse, cfo, metric, sc_rot, nullptr, nullptr);
+}
+
+int sync_auto_correlate_device(int fmt, gfdm_hip_burst_sync* h, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
+                                              int64_t stride, int64_t n_windows, void* stream)
+{
+    int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
+    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
+    if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    return sync_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), nullptr, nullptr, nullptr, nullptr, nullptr,
+                        static_cast<cf*>(ac), static_cast<float*>(ic), (hipStream_t)stream);
+}
+
+int sync_auto_correlate_host(int fmt, gfdm_hip_burst_sync* h, float* ac, float* ic, const void* samples, int64_t stream_len, int64_t first,
+                                            int64_t stride, int64_t n_windows)
+{
+    int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
+    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
+    if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
+    return sync_host(h, samples, fmt, first, stride, n_windows, nullptr, nullptr, nullptr, nullptr, nullptr, ac, ic);
+}
+
+/* windows at arbitrary starts: the regular-grid kernels with a start array (bit-equal results per window) */
+int sync_find_frame_start_at_device(int fmt, gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                                   const void* samples, int64_t stream_len, const void* starts, int64_t n_windows, void* stream)
+{
+    int rc = check_at(h, samples, stream_len, starts, n_windows);
+    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
+    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    return sync_enqueue(h, list_args(h, samples, fmt, stream_len, static_cast<const int64_t*>(starts), n_windows, n_windows, 0),
+                        static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric),
+                        static_cast<cf*>(sc_rot), nullptr, nullptr, (hipStream_t)stream);
+}
+
+int sync_find_frame_start_at_host(int fmt, gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                                 const void* samples, int64_t stream_len, const int64_t* starts, int64_t n_windows)
+{
+    int rc = check_at(h, samples, stream_len, starts, n_windows);
+    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
+    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const int64_t n = n_windows;
+    DevBuf d_in, d_st, d_out;
+    BURST_TRY(d_in.alloc((size_t)stream_len * sample_bytes(fmt)));
+    BURST_TRY(d_st.alloc((size_t)n * sizeof(int64_t)));
+    BURST_TRY(d_out.alloc(out_bytes(n)));
+    BURST_TRY(hipMemcpyAsync(d_in.p, samples, (size_t)stream_len * sample_bytes(fmt), hipMemcpyHostToDevice, h->stream));
+    BURST_TRY(hipMemcpyAsync(d_st.p, starts, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    const SyncOut o = carve_out(d_out.p, n);
+    rc = sync_enqueue(h, list_args(h, d_in.p, fmt, stream_len, static_cast<const int64_t*>(d_st.p), n, n, 0), o.frame_start, o.coarse, o.cfo,
+                      o.metric, o.sc_rot, nullptr, nullptr, h->stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    rc = fetch_out(o, n, frame_start, coarse, cfo, metric, sc_rot, h->stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    BURST_TRY(hipStreamSynchronize(h->stream));
+    return GFDM_HIP_OK;
+}
+
+int sync_detect_device(int fmt, gfdm_hip_burst_sync* h, void* count, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                      const void* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts,
+                                      void* workspace, void* stream)
+{
+    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
+    int rc = detect_check(h->K, h->cp, h->W, stream_len, threshold, min_distance, lead, max_bursts);
+    if (rc != GFDM_HIP_OK) return rc;
+    if (!samples || !count || !workspace) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
+    if (max_bursts > 0 && (!frame_start || !coarse || !cfo || !metric || !sc_rot)) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const SyncOut o = { static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric),
+                        static_cast<cf*>(sc_rot) };
+    return detect_enqueue(h, static_cast<int64_t*>(count), o, samples, fmt, stream_len, threshold, min_distance, lead, max_bursts, workspace,
+                          (hipStream_t)stream);
+}
+
+int sync_detect_host(int fmt, gfdm_hip_burst_sync* h, int64_t* count, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                    const void* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts)
+{
+    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
+    int rc = detect_check(h->K, h->cp, h->W, stream_len, threshold, min_distance, lead, max_bursts);
+    if (rc != GFDM_HIP_OK) return rc;
+    if (!samples || !count) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
+    if (max_bursts > 0 && (!frame_start || !coarse || !cfo || !metric || !sc_rot)) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const int64_t n = max_bursts;
+    DevBuf d_in, d_ws, d_out, d_count;
+    BURST_TRY(d_in.alloc((size_t)stream_len * sample_bytes(fmt)));
+    BURST_TRY(d_ws.alloc(detect_geom(h, stream_len).bytes));
+    BURST_TRY(d_out.alloc(out_bytes(n)));
+    BURST_TRY(d_count.alloc(sizeof(int64_t)));
+    BURST_TRY(hipMemcpyAsync(d_in.p, samples, (size_t)stream_len * sample_bytes(fmt), hipMemcpyHostToDevice, h->stream));
+    const SyncOut o = carve_out(d_out.p, n);
+    rc = detect_enqueue(h, static_cast<int64_t*>(d_count.p), o, d_in.p, fmt, stream_len, threshold, min_distance, lead, n, d_ws.p, h->stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    BURST_TRY(hipMemcpyAsync(count, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    if (n > 0) {
+        rc = fetch_out(o, n, frame_start, coarse, cfo, metric, sc_rot, h->stream);
+        if (rc != GFDM_HIP_OK) return rc;
+    }
+    BURST_TRY(hipStreamSynchronize(h->stream));
+    return GFDM_HIP_OK;
+}
+
+int extractor_extract_device(int fmt, gfdm_hip_burst_extractor* h, void* out, const void* samples, int64_t stream_len, const void* offsets,
+                                            const void* scale, const void* sc_rot, int64_t n_bursts, void* stream)
+{
+    int rc = extract_check(h, out, samples, stream_len, offsets, n_bursts);
+    if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    return extract_enqueue(h, static_cast<cf*>(out), samples, fmt, stream_len, static_cast<const int64_t*>(offsets),
+                           static_cast<const float*>(scale), static_cast<const cf*>(sc_rot), n_bursts, (hipStream_t)stream);
+}
+
+int extractor_extract_host(int fmt, gfdm_hip_burst_extractor* h, float* out, const void* samples, int64_t stream_len, const int64_t* offsets,
+                                          const float* scale, const float* sc_rot, int64_t n_bursts)
+{
+    int rc = extract_check(h, out, samples, stream_len, offsets, n_bursts);
+    if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const size_t n = (size_t)n_bursts, L = (size_t)h->burst_len;
+    DevBuf d_s, d_args, d_out;
+    BURST_TRY(d_s.alloc((size_t)stream_len * sample_bytes(fmt)));
+    BURST_TRY(d_args.alloc(n * (sizeof(int64_t) + sizeof(float) + sizeof(cf))));
+    BURST_TRY(d_out.alloc(n * L * sizeof(cf)));
+    int64_t* d_off = static_cast<int64_t*>(d_args.p);
+    cf* d_rot = reinterpret_cast<cf*>(d_off + n);
+    float* d_scale = reinterpret_cast<float*>(d_rot + n);
+    if (stream_len) BURST_TRY(hipMemcpyAsync(d_s.p, samples, (size_t)stream_len * sample_bytes(fmt), hipMemcpyHostToDevice, h->stream));
+    BURST_TRY(hipMemcpyAsync(d_off, offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    if (sc_rot) BURST_TRY(hipMemcpyAsync(d_rot, sc_rot, n * sizeof(cf), hipMemcpyHostToDevice, h->stream));
+    if (scale) BURST_TRY(hipMemcpyAsync(d_scale, scale, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    rc = extract_enqueue(h, static_cast<cf*>(d_out.p), d_s.p, fmt, stream_len, d_off, scale ? d_scale : nullptr, sc_rot ? d_rot : nullptr,
+                         n_bursts, h->stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    BURST_TRY(hipMemcpyAsync(out, d_out.p, n * L * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
+    BURST_TRY(hipStreamSynchronize(h->stream));
     return GFDM_HIP_OK;
 }
 
@@ -788,88 +980,6 @@ int gfdm_hip_burst_sync_cp_len(const gfdm_hip_burst_sync* h) { return h ? h->cp 
 int64_t gfdm_hip_burst_sync_window_len(const gfdm_hip_burst_sync* h) { return h ? h->W : GFDM_HIP_EINVAL; }
 int64_t gfdm_hip_burst_sync_corr_len(const gfdm_hip_burst_sync* h) { return h ? h->W - 2 * h->K : GFDM_HIP_EINVAL; }
 
-int gfdm_hip_burst_sync_find_frame_start_device(gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
-                                                const void* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows, void* stream)
-{
-    int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
-    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, grid_args(h, static_cast<const cf*>(samples), first, stride, n_windows, 0), static_cast<int64_t*>(frame_start),
-                        static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric), static_cast<cf*>(sc_rot), nullptr, nullptr,
-                        (hipStream_t)stream);
-}
-
-int gfdm_hip_burst_sync_find_frame_start_host(gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
-                                              const float* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows)
-{
-    int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
-    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    return sync_host(h, samples, first, stride, n_windows, frame_start, coarse, cfo, metric, sc_rot, nullptr, nullptr);
-}
-
-int gfdm_hip_burst_sync_auto_correlate_device(gfdm_hip_burst_sync* h, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
-                                              int64_t stride, int64_t n_windows, void* stream)
-{
-    int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
-    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, grid_args(h, static_cast<const cf*>(samples), first, stride, n_windows, 0), nullptr, nullptr, nullptr, nullptr, nullptr,
-                        static_cast<cf*>(ac), static_cast<float*>(ic), (hipStream_t)stream);
-}
-
-int gfdm_hip_burst_sync_auto_correlate_host(gfdm_hip_burst_sync* h, float* ac, float* ic, const float* samples, int64_t stream_len, int64_t first,
-                                            int64_t stride, int64_t n_windows)
-{
-    int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
-    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
-    return sync_host(h, samples, first, stride, n_windows, nullptr, nullptr, nullptr, nullptr, nullptr, ac, ic);
-}
-
-/* windows at arbitrary starts: the regular-grid kernels with a start array (bit-equal results per window) */
-int gfdm_hip_burst_sync_find_frame_start_at_device(gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
-                                                   const void* samples, int64_t stream_len, const void* starts, int64_t n_windows, void* stream)
-{
-    int rc = check_at(h, samples, stream_len, starts, n_windows);
-    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, list_args(h, static_cast<const cf*>(samples), stream_len, static_cast<const int64_t*>(starts), n_windows, n_windows, 0),
-                        static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric),
-                        static_cast<cf*>(sc_rot), nullptr, nullptr, (hipStream_t)stream);
-}
-
-int gfdm_hip_burst_sync_find_frame_start_at_host(gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
-                                                 const float* samples, int64_t stream_len, const int64_t* starts, int64_t n_windows)
-{
-    int rc = check_at(h, samples, stream_len, starts, n_windows);
-    if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const int64_t n = n_windows;
-    DevBuf d_in, d_st, d_out;
-    BURST_TRY(d_in.alloc((size_t)stream_len * sizeof(cf)));
-    BURST_TRY(d_st.alloc((size_t)n * sizeof(int64_t)));
-    BURST_TRY(d_out.alloc(out_bytes(n)));
-    BURST_TRY(hipMemcpyAsync(d_in.p, samples, (size_t)stream_len * sizeof(cf), hipMemcpyHostToDevice, h->stream));
-    BURST_TRY(hipMemcpyAsync(d_st.p, starts, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    const SyncOut o = carve_out(d_out.p, n);
-    rc = sync_enqueue(h, list_args(h, static_cast<const cf*>(d_in.p), stream_len, static_cast<const int64_t*>(d_st.p), n, n, 0), o.frame_start, o.coarse, o.cfo,
-                      o.metric, o.sc_rot, nullptr, nullptr, h->stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    rc = fetch_out(o, n, frame_start, coarse, cfo, metric, sc_rot, h->stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    BURST_TRY(hipStreamSynchronize(h->stream));
-    return GFDM_HIP_OK;
-}
-
 int gfdm_hip_burst_sync_detect_check(int fft_len, int cp_len, int64_t window_len, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead,
                                      int64_t max_bursts)
 {
@@ -882,54 +992,6 @@ int64_t gfdm_hip_burst_sync_detect_workspace_bytes(const gfdm_hip_burst_sync* h,
     if (stream_len < h->W) return api_fail(GFDM_HIP_EINVAL, "stream_len is shorter than window_len");
     if (stream_len > kMaxDetectLen) return api_fail(GFDM_HIP_EINVAL, "stream_len above 2^29 (split the capture into overlapping spans)");
     return (int64_t)detect_geom(h, stream_len).bytes;
-}
-
-int gfdm_hip_burst_sync_detect_device(gfdm_hip_burst_sync* h, void* count, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
-                                      const void* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts,
-                                      void* workspace, void* stream)
-{
-    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
-    int rc = detect_check(h->K, h->cp, h->W, stream_len, threshold, min_distance, lead, max_bursts);
-    if (rc != GFDM_HIP_OK) return rc;
-    if (!samples || !count || !workspace) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
-    if (max_bursts > 0 && (!frame_start || !coarse || !cfo || !metric || !sc_rot)) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const SyncOut o = { static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric),
-                        static_cast<cf*>(sc_rot) };
-    return detect_enqueue(h, static_cast<int64_t*>(count), o, static_cast<const cf*>(samples), stream_len, threshold, min_distance, lead, max_bursts, workspace,
-                          (hipStream_t)stream);
-}
-
-int gfdm_hip_burst_sync_detect_host(gfdm_hip_burst_sync* h, int64_t* count, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
-                                    const float* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts)
-{
-    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
-    int rc = detect_check(h->K, h->cp, h->W, stream_len, threshold, min_distance, lead, max_bursts);
-    if (rc != GFDM_HIP_OK) return rc;
-    if (!samples || !count) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
-    if (max_bursts > 0 && (!frame_start || !coarse || !cfo || !metric || !sc_rot)) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const int64_t n = max_bursts;
-    DevBuf d_in, d_ws, d_out, d_count;
-    BURST_TRY(d_in.alloc((size_t)stream_len * sizeof(cf)));
-    BURST_TRY(d_ws.alloc(detect_geom(h, stream_len).bytes));
-    BURST_TRY(d_out.alloc(out_bytes(n)));
-    BURST_TRY(d_count.alloc(sizeof(int64_t)));
-    BURST_TRY(hipMemcpyAsync(d_in.p, samples, (size_t)stream_len * sizeof(cf), hipMemcpyHostToDevice, h->stream));
-    const SyncOut o = carve_out(d_out.p, n);
-    rc = detect_enqueue(h, static_cast<int64_t*>(d_count.p), o, static_cast<const cf*>(d_in.p), stream_len, threshold, min_distance, lead, n, d_ws.p, h->stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    BURST_TRY(hipMemcpyAsync(count, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    if (n > 0) {
-        rc = fetch_out(o, n, frame_start, coarse, cfo, metric, sc_rot, h->stream);
-        if (rc != GFDM_HIP_OK) return rc;
-    }
-    BURST_TRY(hipStreamSynchronize(h->stream));
-    return GFDM_HIP_OK;
 }
 
 int gfdm_hip_burst_extractor_create(gfdm_hip_burst_extractor** out, int burst_len, int tag_backoff, int activate_cfo_correction, int device)
@@ -966,42 +1028,106 @@ int gfdm_hip_burst_extractor_set_cfo_correction(gfdm_hip_burst_extractor* h, int
     return GFDM_HIP_OK;
 }
 
-int gfdm_hip_burst_extractor_extract_device(gfdm_hip_burst_extractor* h, void* out, const void* samples, int64_t stream_len, const void* offsets,
-                                            const void* scale, const void* sc_rot, int64_t n_bursts, void* stream)
+/* the calls that read a capture and their sc16 twins (include/gfdm_hip.h) */
+int gfdm_hip_burst_sync_find_frame_start_device(gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+    const void* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows, void* stream)
 {
-    int rc = extract_check(h, out, samples, stream_len, offsets, n_bursts);
-    if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return extract_enqueue(h, static_cast<cf*>(out), static_cast<const cf*>(samples), stream_len, static_cast<const int64_t*>(offsets),
-                           static_cast<const float*>(scale), static_cast<const cf*>(sc_rot), n_bursts, (hipStream_t)stream);
+    return sync_find_frame_start_device(gfdm::SAMPLES_CF32, h, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, first, stride, n_windows, stream);
 }
-
-int gfdm_hip_burst_extractor_extract_host(gfdm_hip_burst_extractor* h, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
-                                          const float* scale, const float* sc_rot, int64_t n_bursts)
+int gfdm_hip_burst_sync_find_frame_start_sc16_device(gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+    const void* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows, void* stream)
 {
-    int rc = extract_check(h, out, samples, stream_len, offsets, n_bursts);
-    if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t n = (size_t)n_bursts, L = (size_t)h->burst_len;
-    DevBuf d_s, d_args, d_out;
-    BURST_TRY(d_s.alloc((size_t)stream_len * sizeof(cf)));
-    BURST_TRY(d_args.alloc(n * (sizeof(int64_t) + sizeof(float) + sizeof(cf))));
-    BURST_TRY(d_out.alloc(n * L * sizeof(cf)));
-    int64_t* d_off = static_cast<int64_t*>(d_args.p);
-    cf* d_rot = reinterpret_cast<cf*>(d_off + n);
-    float* d_scale = reinterpret_cast<float*>(d_rot + n);
-    if (stream_len) BURST_TRY(hipMemcpyAsync(d_s.p, samples, (size_t)stream_len * sizeof(cf), hipMemcpyHostToDevice, h->stream));
-    BURST_TRY(hipMemcpyAsync(d_off, offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    if (sc_rot) BURST_TRY(hipMemcpyAsync(d_rot, sc_rot, n * sizeof(cf), hipMemcpyHostToDevice, h->stream));
-    if (scale) BURST_TRY(hipMemcpyAsync(d_scale, scale, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    rc = extract_enqueue(h, static_cast<cf*>(d_out.p), static_cast<const cf*>(d_s.p), stream_len, d_off, scale ? d_scale : nullptr, sc_rot ? d_rot : nullptr,
-                         n_bursts, h->stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    BURST_TRY(hipMemcpyAsync(out, d_out.p, n * L * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
-    BURST_TRY(hipStreamSynchronize(h->stream));
-    return GFDM_HIP_OK;
+    return sync_find_frame_start_device(gfdm::SAMPLES_SC16, h, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, first, stride, n_windows, stream);
+}
+int gfdm_hip_burst_sync_find_frame_start_host(gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+    const float* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows)
+{
+    return sync_find_frame_start_host(gfdm::SAMPLES_CF32, h, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, first, stride, n_windows);
+}
+int gfdm_hip_burst_sync_find_frame_start_sc16_host(gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+    const int16_t* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows)
+{
+    return sync_find_frame_start_host(gfdm::SAMPLES_SC16, h, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, first, stride, n_windows);
+}
+int gfdm_hip_burst_sync_auto_correlate_device(gfdm_hip_burst_sync* h, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
+    int64_t stride, int64_t n_windows, void* stream)
+{
+    return sync_auto_correlate_device(gfdm::SAMPLES_CF32, h, ac, ic, samples, stream_len, first, stride, n_windows, stream);
+}
+int gfdm_hip_burst_sync_auto_correlate_sc16_device(gfdm_hip_burst_sync* h, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
+    int64_t stride, int64_t n_windows, void* stream)
+{
+    return sync_auto_correlate_device(gfdm::SAMPLES_SC16, h, ac, ic, samples, stream_len, first, stride, n_windows, stream);
+}
+int gfdm_hip_burst_sync_auto_correlate_host(gfdm_hip_burst_sync* h, float* ac, float* ic, const float* samples, int64_t stream_len, int64_t first,
+    int64_t stride, int64_t n_windows)
+{
+    return sync_auto_correlate_host(gfdm::SAMPLES_CF32, h, ac, ic, samples, stream_len, first, stride, n_windows);
+}
+int gfdm_hip_burst_sync_auto_correlate_sc16_host(gfdm_hip_burst_sync* h, float* ac, float* ic, const int16_t* samples, int64_t stream_len, int64_t first,
+    int64_t stride, int64_t n_windows)
+{
+    return sync_auto_correlate_host(gfdm::SAMPLES_SC16, h, ac, ic, samples, stream_len, first, stride, n_windows);
+}
+int gfdm_hip_burst_sync_find_frame_start_at_device(gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+    const void* samples, int64_t stream_len, const void* starts, int64_t n_windows, void* stream)
+{
+    return sync_find_frame_start_at_device(gfdm::SAMPLES_CF32, h, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, starts, n_windows, stream);
+}
+int gfdm_hip_burst_sync_find_frame_start_at_sc16_device(gfdm_hip_burst_sync* h, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+    const void* samples, int64_t stream_len, const void* starts, int64_t n_windows, void* stream)
+{
+    return sync_find_frame_start_at_device(gfdm::SAMPLES_SC16, h, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, starts, n_windows, stream);
+}
+int gfdm_hip_burst_sync_find_frame_start_at_host(gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+    const float* samples, int64_t stream_len, const int64_t* starts, int64_t n_windows)
+{
+    return sync_find_frame_start_at_host(gfdm::SAMPLES_CF32, h, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, starts, n_windows);
+}
+int gfdm_hip_burst_sync_find_frame_start_at_sc16_host(gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+    const int16_t* samples, int64_t stream_len, const int64_t* starts, int64_t n_windows)
+{
+    return sync_find_frame_start_at_host(gfdm::SAMPLES_SC16, h, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, starts, n_windows);
+}
+int gfdm_hip_burst_sync_detect_device(gfdm_hip_burst_sync* h, void* count, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+    const void* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts, void* workspace, void* stream)
+{
+    return sync_detect_device(gfdm::SAMPLES_CF32, h, count, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, threshold, min_distance, lead, max_bursts, workspace, stream);
+}
+int gfdm_hip_burst_sync_detect_sc16_device(gfdm_hip_burst_sync* h, void* count, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+    const void* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts, void* workspace, void* stream)
+{
+    return sync_detect_device(gfdm::SAMPLES_SC16, h, count, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, threshold, min_distance, lead, max_bursts, workspace, stream);
+}
+int gfdm_hip_burst_sync_detect_host(gfdm_hip_burst_sync* h, int64_t* count, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+    const float* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts)
+{
+    return sync_detect_host(gfdm::SAMPLES_CF32, h, count, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, threshold, min_distance, lead, max_bursts);
+}
+int gfdm_hip_burst_sync_detect_sc16_host(gfdm_hip_burst_sync* h, int64_t* count, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric,
+    float* sc_rot, const int16_t* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts)
+{
+    return sync_detect_host(gfdm::SAMPLES_SC16, h, count, frame_start, coarse, cfo, metric, sc_rot, samples, stream_len, threshold, min_distance, lead, max_bursts);
+}
+int gfdm_hip_burst_extractor_extract_device(gfdm_hip_burst_extractor* h, void* out, const void* samples, int64_t stream_len, const void* offsets,
+    const void* scale, const void* sc_rot, int64_t n_bursts, void* stream)
+{
+    return extractor_extract_device(gfdm::SAMPLES_CF32, h, out, samples, stream_len, offsets, scale, sc_rot, n_bursts, stream);
+}
+int gfdm_hip_burst_extractor_extract_sc16_device(gfdm_hip_burst_extractor* h, void* out, const void* samples, int64_t stream_len, const void* offsets,
+    const void* scale, const void* sc_rot, int64_t n_bursts, void* stream)
+{
+    return extractor_extract_device(gfdm::SAMPLES_SC16, h, out, samples, stream_len, offsets, scale, sc_rot, n_bursts, stream);
+}
+int gfdm_hip_burst_extractor_extract_host(gfdm_hip_burst_extractor* h, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
+    const float* scale, const float* sc_rot, int64_t n_bursts)
+{
+    return extractor_extract_host(gfdm::SAMPLES_CF32, h, out, samples, stream_len, offsets, scale, sc_rot, n_bursts);
+}
+int gfdm_hip_burst_extractor_extract_sc16_host(gfdm_hip_burst_extractor* h, float* out, const int16_t* samples, int64_t stream_len, const int64_t* offsets,
+    const float* scale, const float* sc_rot, int64_t n_bursts)
+{
+    return extractor_extract_host(gfdm::SAMPLES_SC16, h, out, samples, stream_len, offsets, scale, sc_rot, n_bursts);
 }
 
 }  // extern "C"

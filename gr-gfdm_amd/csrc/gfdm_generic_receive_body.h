@@ -34,7 +34,7 @@
     if (eq_source == EQ_PREAMBLE) {                                // channel estimator in front, the tiles are its scratch
         cf* bins = t0 + (size_t)ntiles * TS;
         if constexpr (BURST)
-            estimate_preamble_bins_from(est, [&](int i) { return burst_fetch(bio.cap, bio.cap_len, cap_base, bio.pre + i, 1.f, cap_rotate, cap_phi); }, t0, t1, bins);
+            estimate_preamble_bins_from(est, [&](int i) { return burst_fetch(bio.cap, bio.fmt, bio.cap_len, cap_base, bio.pre + i, 1.f, cap_rotate, cap_phi); }, t0, t1, bins);
         else
         estimate_preamble_bins(est, f_eq + blk * (est.pre_stride ? est.pre_stride : 2 * K), t0, t1, bins);
         __syncthreads();
@@ -44,7 +44,7 @@
 
     GFDM_GSTAMP(0);
     if constexpr (BURST) {
-        for (int idx = threadIdx.x; idx < N; idx += GT) t1[idx] = burst_fetch(bio.cap, bio.cap_len, cap_base, ic.io.in_offset + idx, 1.f, cap_rotate, cap_phi);
+        for (int idx = threadIdx.x; idx < N; idx += GT) t1[idx] = burst_fetch(bio.cap, bio.fmt, bio.cap_len, cap_base, ic.io.in_offset + idx, 1.f, cap_rotate, cap_phi);
     } else {
         stream_in(t1, x, N);
     }

@@ -1695,7 +1695,7 @@ int bursts_call_io(const FrameIo& f, const Plan& pl, const gfdm_hip_channel_esti
     return GFDM_HIP_OK;
 }
 
-int bursts_device(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, gfdm::IcParams ic, int mode, void* out, const void* samples,
+int bursts_device(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, gfdm::IcParams ic, int mode, void* out, const void* samples, int fmt,
                   int64_t stream_len, const void* offsets, const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
                   int noutput_size, int64_t n_bursts, void* stream)
 {
@@ -1704,7 +1704,8 @@ int bursts_device(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* 
     if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
     if (!out || !offsets || (!samples && stream_len > 0)) return fail(GFDM_HIP_EINVAL, "NULL buffer");
     if (n_bursts > 0x7fffffff) return fail(GFDM_HIP_EINVAL, "more than 2^31 - 1 bursts per call");
-    ep.io.cap = static_cast<const cf*>(samples);
+    ep.io.cap = samples;
+    ep.io.fmt = fmt;
     ep.io.off = static_cast<const int64_t*>(offsets);
     ep.io.rot = cfo_correction ? static_cast<const cf*>(sc_rot) : nullptr;
     ep.io.count = static_cast<const int64_t*>(count);
@@ -1718,8 +1719,9 @@ struct DevMem {
     ~DevMem() { if (p) (void)hipFree(p); }
 };
 
-// convenience, not a pipeline: capture and arrays to the device, ONE launch, result back (the handle's private stream)
-int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, const gfdm::IcParams& ic, int mode, float* out, const float* samples,
+// convenience, not a pipeline: capture (in the caller's format: an sc16 capture goes up as int16) and arrays to the device, ONE launch,
+// result back (the handle's private stream)
+int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, const gfdm::IcParams& ic, int mode, float* out, const void* samples, int fmt,
                 int64_t stream_len, const int64_t* offsets, const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction,
                 int noutput_size, int64_t n_bursts)
 {
@@ -1732,17 +1734,18 @@ int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c,
     if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const size_t n = (size_t)n_bursts, out_bytes = n * (size_t)io.nout * sizeof(cf);
     DevMem d_s, d_args, d_out;
-    HIP_TRY(hipMalloc(&d_s.p, std::max<size_t>((size_t)stream_len * sizeof(cf), sizeof(cf))));
+    const size_t sb = fmt == gfdm::SAMPLES_SC16 ? 2 * sizeof(int16_t) : sizeof(cf);
+    HIP_TRY(hipMalloc(&d_s.p, std::max<size_t>((size_t)stream_len * sb, sizeof(cf))));
     HIP_TRY(hipMalloc(&d_args.p, (n + 1) * sizeof(int64_t) + n * sizeof(cf)));
     HIP_TRY(hipMalloc(&d_out.p, out_bytes));
     int64_t* d_off = static_cast<int64_t*>(d_args.p);
     int64_t* d_cnt = d_off + n;
     cf* d_rot = reinterpret_cast<cf*>(d_cnt + 1);
-    if (stream_len) HIP_TRY(hipMemcpyAsync(d_s.p, samples, (size_t)stream_len * sizeof(cf), hipMemcpyHostToDevice, pl.stream));
+    if (stream_len) HIP_TRY(hipMemcpyAsync(d_s.p, samples, (size_t)stream_len * sb, hipMemcpyHostToDevice, pl.stream));
     HIP_TRY(hipMemcpyAsync(d_off, offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, pl.stream));
     if (count) HIP_TRY(hipMemcpyAsync(d_cnt, count, sizeof(int64_t), hipMemcpyHostToDevice, pl.stream));
     if (sc_rot) HIP_TRY(hipMemcpyAsync(d_rot, sc_rot, n * sizeof(cf), hipMemcpyHostToDevice, pl.stream));
-    rc = bursts_device(pl, f, c, ic, mode, d_out.p, d_s.p, stream_len, d_off, sc_rot ? d_rot : nullptr, count ? d_cnt : nullptr, backoff, preamble_offset,
+    rc = bursts_device(pl, f, c, ic, mode, d_out.p, d_s.p, fmt, stream_len, d_off, sc_rot ? d_rot : nullptr, count ? d_cnt : nullptr, backoff, preamble_offset,
                        cfo_correction, noutput_size, n_bursts, pl.stream);
     if (rc != GFDM_HIP_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, pl.stream));
@@ -1754,39 +1757,68 @@ int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c,
 
 extern "C" {
 
+/* the four calls and their sc16 twins (include/gfdm_hip.h): thin wrappers over bursts_device / bursts_host, which take the sample format */
 int gfdm_hip_receiver_demodulate_bursts_device(gfdm_hip_receiver* r, void* out, const void* samples, int64_t stream_len, const void* offsets,
-                                               const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
-                                               int noutput_size, int64_t n_bursts, void* stream)
+    const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_device(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+    return bursts_device(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
                          cfo_correction, noutput_size, n_bursts, stream);
 }
 
 int gfdm_hip_receiver_demodulate_bursts_host(gfdm_hip_receiver* r, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
-                                             const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction,
-                                             int noutput_size, int64_t n_bursts)
+    const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_host(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+    return bursts_host(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
                        cfo_correction, noutput_size, n_bursts);
 }
 
 int gfdm_hip_advanced_receiver_work_bursts_device(gfdm_hip_advanced_receiver* a, void* out, const void* samples, int64_t stream_len, const void* offsets,
-                                                  const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
-                                                  int noutput_size, int64_t n_bursts, void* stream)
+    const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_device(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+    return bursts_device(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
                          cfo_correction, noutput_size, n_bursts, stream);
 }
 
-int gfdm_hip_advanced_receiver_work_bursts_host(gfdm_hip_advanced_receiver* a, float* out, const float* samples, int64_t stream_len,
-                                                const int64_t* offsets, const float* sc_rot, const int64_t* count, int backoff, int preamble_offset,
-                                                int cfo_correction, int noutput_size, int64_t n_bursts)
+int gfdm_hip_advanced_receiver_work_bursts_host(gfdm_hip_advanced_receiver* a, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
+    const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_host(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+    return bursts_host(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+                       cfo_correction, noutput_size, n_bursts);
+}
+
+int gfdm_hip_receiver_demodulate_bursts_sc16_device(gfdm_hip_receiver* r, void* out, const void* samples, int64_t stream_len, const void* offsets,
+    const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
+{
+    if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    return bursts_device(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+                         cfo_correction, noutput_size, n_bursts, stream);
+}
+
+int gfdm_hip_receiver_demodulate_bursts_sc16_host(gfdm_hip_receiver* r, float* out, const int16_t* samples, int64_t stream_len, const int64_t* offsets,
+    const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
+{
+    if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    return bursts_host(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+                       cfo_correction, noutput_size, n_bursts);
+}
+
+int gfdm_hip_advanced_receiver_work_bursts_sc16_device(gfdm_hip_advanced_receiver* a, void* out, const void* samples, int64_t stream_len, const void* offsets,
+    const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
+{
+    if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    return bursts_device(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
+                         cfo_correction, noutput_size, n_bursts, stream);
+}
+
+int gfdm_hip_advanced_receiver_work_bursts_sc16_host(gfdm_hip_advanced_receiver* a, float* out, const int16_t* samples, int64_t stream_len, const int64_t* offsets,
+    const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
+{
+    if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    return bursts_host(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
                        cfo_correction, noutput_size, n_bursts);
 }
 

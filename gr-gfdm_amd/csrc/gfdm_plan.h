@@ -167,13 +167,15 @@ struct EstPlan {
 // the argument layout of every other kernel -- and with it its code and its registers -- stays what it was (grown by these fields, EstPlan
 // moved the arguments behind it and hipcc merged their scalar loads differently).  On the host a launch carries it behind its EstPlan
 // (BurstEstPlan, marked by pre_stride == EST_GATHER), so the launchers keep their signatures; without it a launch is what it always was.
+enum SampleFormat { SAMPLES_CF32 = 0, SAMPLES_SC16 = 1 };      // complex64 | interleaved int16 I, Q (gfdm_burstfetch.h)
 struct BurstIo {
-    const cf* cap;            // the capture
+    const void* cap;          // the capture
     int64_t cap_len;
     const int64_t* off;       // [nblocks] burst offsets
     const cf* rot;            // [nblocks] r_b, nullptr = no rotation
     const int64_t* count;     // nullptr or one value: bursts from clamp(*count, 0, nblocks) on read nothing and yield zeros
     int backoff, pre;
+    int fmt;                  // SampleFormat of cap, uniform over the launch
 };
 constexpr int EST_GATHER = -1;    // EstPlan::pre_stride of a BurstEstPlan (no other launch has a negative stride)
 struct BurstEstPlan { EstPlan est; BurstIo io; };

@@ -69,9 +69,9 @@
     cf pre0, pre1, inv0, inv1;
     if constexpr (BURST) {
         const int n0 = ic.io.in_offset + q, np = bio.pre + q;
-        static_for<0, M>([&](auto pi) { constexpr int pp = decltype(pi)::value; v[pp] = burst_fetch(bio.cap, cap_len, cap_base, n0 + K * pp, 1.f, cap_rotate, cap_phi); });
-        pre0 = burst_fetch(bio.cap, cap_len, cap_base, np, 1.f, cap_rotate, cap_phi);
-        pre1 = burst_fetch(bio.cap, cap_len, cap_base, np + K, 1.f, cap_rotate, cap_phi);
+        static_for<0, M>([&](auto pi) { constexpr int pp = decltype(pi)::value; v[pp] = burst_fetch(bio.cap, bio.fmt, cap_len, cap_base, n0 + K * pp, 1.f, cap_rotate, cap_phi); });
+        pre0 = burst_fetch(bio.cap, bio.fmt, cap_len, cap_base, np, 1.f, cap_rotate, cap_phi);
+        pre1 = burst_fetch(bio.cap, bio.fmt, cap_len, cap_base, np + K, 1.f, cap_rotate, cap_phi);
         inv0 = est.inv0[q];
         inv1 = est.inv1[q];
     } else if constexpr (EQ == EQ_PREAMBLE) {

@@ -195,6 +195,21 @@ def lib():
         "gfdm_hip_burst_extractor_get_cfo_correction": (i32, [vp]),
         "gfdm_hip_burst_extractor_extract_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i64]),
         "gfdm_hip_burst_extractor_extract_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i64, vp]),
+        # the sc16 twins: the same signatures, `samples` interleaved int16 I/Q
+        "gfdm_hip_receiver_demodulate_bursts_sc16_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64]),
+        "gfdm_hip_receiver_demodulate_bursts_sc16_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
+        "gfdm_hip_advanced_receiver_work_bursts_sc16_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64]),
+        "gfdm_hip_advanced_receiver_work_bursts_sc16_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
+        "gfdm_hip_burst_sync_find_frame_start_sc16_host": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64]),
+        "gfdm_hip_burst_sync_find_frame_start_sc16_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
+        "gfdm_hip_burst_sync_auto_correlate_sc16_host": (i32, [vp, vp, vp, vp, i64, i64, i64, i64]),
+        "gfdm_hip_burst_sync_auto_correlate_sc16_device": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
+        "gfdm_hip_burst_sync_find_frame_start_at_sc16_host": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64]),
+        "gfdm_hip_burst_sync_find_frame_start_at_sc16_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]),
+        "gfdm_hip_burst_sync_detect_sc16_host": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64]),
+        "gfdm_hip_burst_sync_detect_sc16_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64, vp, vp]),
+        "gfdm_hip_burst_extractor_extract_sc16_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i64]),
+        "gfdm_hip_burst_extractor_extract_sc16_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == the library does not export a declared symbol
@@ -239,6 +254,73 @@ def _dev_ptr(t, n_elems, what, device=None):
     if t.numel() != n_elems:
         raise RuntimeError("%s has %d elements, expected %d" % (what, t.numel(), n_elems))
     return t.data_ptr()
+
+
+def to_sc16(signal, peak=0.9 * 2048):
+    """pygfdm's convert_to_sc16 (python/pygfdm/converter.py): the signal scaled so that its largest |re| or |im| equals `peak` (default: 0.9 of
+    a 12-bit ADC's full scale), then truncated toward zero.  Returns int16 of shape (n, 2): columns I, Q.  The input is left as it is."""
+    x = np.asarray(signal, dtype=np.complex128).ravel()
+    if not 0 < peak <= np.iinfo(np.int16).max:
+        raise ValueError("peak must lie in (0, 32767]")
+    iq = np.stack((x.real, x.imag), axis=1)
+    top = float(np.max(np.abs(iq))) if iq.size else 0.0
+    if top > 0.0:
+        iq = iq * (peak / top)
+    return np.trunc(iq).astype(np.int16)
+
+
+def from_sc16(iq):
+    """pygfdm's convert_from_sc16: int16 I/Q of shape (n, 2) or flat (2n,) -> complex64 (float)I + j (float)Q, unscaled (exact)."""
+    a = np.asarray(iq)
+    if a.dtype != np.int16:
+        raise TypeError("from_sc16 takes int16 I/Q values, not %s" % a.dtype)
+    a = _sc16_pairs(a.shape, "iq", a.reshape)
+    out = np.empty(a.shape[0], np.complex64)
+    out.real = a[:, 0]
+    out.imag = a[:, 1]
+    return out
+
+
+def _sc16_pairs(shape, what, reshape=None):
+    """number of samples of an sc16 array of `shape` -- (n, 2) or flat (2n,) -- or, with `reshape`, the array as (n, 2)"""
+    shape = tuple(shape)
+    if len(shape) == 2 and shape[1] == 2:
+        n = shape[0]
+    elif len(shape) == 1:
+        if shape[0] % 2:
+            raise ValueError("%s: a flat sc16 array holds I, Q pairs, its length(%d) is odd" % (what, shape[0]))
+        n = shape[0] // 2
+    else:
+        raise ValueError("%s: an sc16 array has shape (n, 2) or (2n,), not %s" % (what, shape))
+    return n if reshape is None else reshape(n, 2)
+
+
+def _capture(samples, device, what="samples"):
+    """A capture argument -> (pointer, n_samples, name infix, keep-alive): complex64 (anything _c64 takes on the host path, a contiguous
+    complex64 tensor on the device path: infix "") or sc16 (a contiguous int16 array / tensor of shape (n, 2) or (2n,): infix "_sc16",
+    passed on as it is, never widened).  Any other integer dtype is a TypeError.  Checks come before anything touches the device."""
+    if _is_tensor(samples):
+        import torch
+        if samples.dtype == torch.int16:
+            n = _sc16_pairs(samples.shape, what)
+            if not samples.is_cuda or not samples.is_contiguous():
+                raise TypeError("%s must be a contiguous int16 CUDA/HIP tensor" % what)
+            if samples.device.index != device:
+                raise RuntimeError("%s lives on GPU %d, the kernel handle on GPU %d" % (what, samples.device.index, device))
+            return samples.data_ptr(), n, "_sc16", samples
+        if not (samples.dtype.is_floating_point or samples.dtype.is_complex):
+            raise TypeError("%s: integer captures must be int16 (sc16), not %s" % (what, samples.dtype))
+        return _dev_ptr(samples, samples.numel(), what, device), samples.numel(), "", samples
+    a = np.asarray(samples)
+    if a.dtype == np.int16:
+        n = _sc16_pairs(a.shape, what)
+        if not a.flags.c_contiguous:
+            raise TypeError("%s must be a C-contiguous int16 array" % what)
+        return a.ctypes.data, n, "_sc16", a
+    if np.issubdtype(a.dtype, np.integer):
+        raise TypeError("%s: integer captures must be int16 (sc16), not %s" % (what, a.dtype))
+    a = _c64(a).ravel()
+    return a.ctypes.data, a.size, "", a
 
 
 def _stream_ptr(stream, device=None):
@@ -494,7 +576,9 @@ class _Kernel:
         outside the capture, CFO rotation by sc_rot) as the load stage of demodulate_estimated, preamble at preamble_offset of each burst.
         Needs configure_frames and set_channel_estimator.  count (one int64, e.g. detect's): rows from count on are zeros.
         r = sync.detect(...) feeds it as demodulate_bursts(samples, r["frame_start"], r["sc_rot"], r["count"], ...).
-        Torch device tensors run the device entry point (no allocation beyond `out`, no synchronisation), numpy arrays the host one."""
+        Torch device tensors run the device entry point (no allocation beyond `out`, no synchronisation), numpy arrays the host one.
+        An int16 capture, shape (n, 2) or (2n,), is read as sc16 (the *_sc16_* entry points): bit-equal to the call on from_sc16(samples)."""
+        sptr, slen, fmt, _keep = _capture(samples, self._dev)
         L = lib()
         if getattr(self, "_estimator", None) is None:
             raise ValueError("set_channel_estimator has not been called on this handle")
@@ -507,11 +591,10 @@ class _Kernel:
             out = torch.empty(n, nout, dtype=torch.complex64, device=samples.device) if out is None else out
             rp = None if sc_rot is None else _dev_arg(sc_rot, torch.complex64, n, "sc_rot", self._dev)
             cp = None if count is None else _dev_arg(count, torch.int64, 1, "count", self._dev)
-            _check(getattr(L, self._bursts_prefix + "_device")(self._h, self._dp(out, n * nout, "out"), self._dp(samples, samples.numel(), "samples"),
-                                                              samples.numel(), _dev_arg(offsets, torch.int64, n, "offsets", self._dev), rp, cp, *args, n,
-                                                              self._sp(stream)))
+            _check(getattr(L, self._bursts_prefix + fmt + "_device")(self._h, self._dp(out, n * nout, "out"), sptr, slen,
+                                                                    _dev_arg(offsets, torch.int64, n, "offsets", self._dev), rp, cp, *args, n,
+                                                                    self._sp(stream)))
             return out
-        a = _c64(samples).ravel()
         off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
         n = off.size
         rot = None if sc_rot is None else _c64(sc_rot).ravel()
@@ -521,8 +604,8 @@ class _Kernel:
         if cnt is not None and cnt.size != 1:
             raise RuntimeError("count has %d elements, expected 1" % cnt.size)
         res = np.empty((n, nout), np.complex64)
-        _check(getattr(L, self._bursts_prefix + "_host")(self._h, res.ctypes.data, a.ctypes.data, a.size, off.ctypes.data,
-                                                        None if rot is None else rot.ctypes.data, None if cnt is None else cnt.ctypes.data, *args, n))
+        _check(getattr(L, self._bursts_prefix + fmt + "_host")(self._h, res.ctypes.data, sptr, slen, off.ctypes.data,
+                                                              None if rot is None else rot.ctypes.data, None if cnt is None else cnt.ctypes.data, *args, n))
         return res
 
     def __del__(self):
@@ -1093,7 +1176,9 @@ def _dev_arg(t, dtype, n_elems, what, device):
 class BurstSync(_Kernel):
     """Preamble timing / CFO synchronisation: pygfdm's find_frame_start (python/pygfdm/synchronization.py:154-263) on every window
     stream[first + b * stride : ... + window_len] of a capture buffer (contract in include/gfdm_hip.h).  numpy samples -> numpy results
-    (host path), a torch complex64 device tensor -> torch results on its device (device path, current stream unless given)."""
+    (host path), a torch complex64 device tensor -> torch results on its device (device path, current stream unless given).  Every call that
+    takes `samples` also takes an sc16 capture -- int16 I/Q of shape (n, 2) or (2n,), numpy or torch -- and reads it as it is (the *_sc16_*
+    entry points): bit-equal to the call on from_sc16(samples)."""
     _destroy = "gfdm_hip_burst_sync_destroy"
 
     def __init__(self, fft_len, cp_len, core_preamble, window_len, device=0):
@@ -1116,29 +1201,22 @@ class BurstSync(_Kernel):
         """ac / ic values per window: window_len - 2 fft_len"""
         return lib().gfdm_hip_burst_sync_corr_len(self._h)
 
-    def _grid(self, samples, first, stride, n_windows):
-        n = samples.numel() if _is_tensor(samples) else np.asarray(samples).size
-        return n, int(first), self.window_len() if stride is None else int(stride), int(n_windows)
+    def _grid(self, first, stride, n_windows):
+        return int(first), self.window_len() if stride is None else int(stride), int(n_windows)
 
     def find_frame_start(self, samples, first=0, stride=None, n_windows=1, stream=None):
         """dict of per-window arrays: frame_start, coarse (stream indices, int64), cfo, metric (float32), sc_rot (complex64).
         stride defaults to window_len (windows back to back)."""
+        sptr, n, fmt, _keep = _capture(samples, self._dev)
         L = lib()
-        n, first, stride, nw = self._grid(samples, first, stride, n_windows)
+        first, stride, nw = self._grid(first, stride, n_windows)
         if _is_tensor(samples):
-            import torch
-            d = samples.device
-            r = {"frame_start": torch.empty(nw, dtype=torch.int64, device=d), "coarse": torch.empty(nw, dtype=torch.int64, device=d),
-                 "cfo": torch.empty(nw, dtype=torch.float32, device=d), "metric": torch.empty(nw, dtype=torch.float32, device=d),
-                 "sc_rot": torch.empty(nw, dtype=torch.complex64, device=d)}
-            _check(L.gfdm_hip_burst_sync_find_frame_start_device(self._h, *[r[k].data_ptr() for k in ("frame_start", "coarse", "cfo", "metric", "sc_rot")],
-                                                                 self._dp(samples, n, "samples"), n, first, stride, nw, self._sp(stream)))
+            r = self._outputs(nw, samples.device)
+            _check(getattr(L, "gfdm_hip_burst_sync_find_frame_start%s_device" % fmt)(self._h, *[r[k].data_ptr() for k in self._OUT], sptr, n, first, stride, nw,
+                                                                                    self._sp(stream)))
             return r
-        a = _c64(samples).ravel()
-        r = {"frame_start": np.empty(nw, np.int64), "coarse": np.empty(nw, np.int64), "cfo": np.empty(nw, np.float32),
-             "metric": np.empty(nw, np.float32), "sc_rot": np.empty(nw, np.complex64)}
-        _check(L.gfdm_hip_burst_sync_find_frame_start_host(self._h, *[r[k].ctypes.data for k in ("frame_start", "coarse", "cfo", "metric", "sc_rot")],
-                                                           a.ctypes.data, n, first, stride, nw))
+        r = self._outputs(nw)
+        _check(getattr(L, "gfdm_hip_burst_sync_find_frame_start%s_host" % fmt)(self._h, *[r[k].ctypes.data for k in self._OUT], sptr, n, first, stride, nw))
         return r
 
     _OUT = ("frame_start", "coarse", "cfo", "metric", "sc_rot")
@@ -1157,18 +1235,20 @@ class BurstSync(_Kernel):
     def find_frame_start_at(self, samples, starts, stream=None):
         """find_frame_start on the windows samples[st : st + window_len], st = clamp(starts[w], 0, len(samples) - window_len): the same
         dict, bit-equal per window to find_frame_start(first=st).  starts: int64 (a device tensor when samples is one)."""
+        sptr, n, fmt, _keep = _capture(samples, self._dev)
         L = lib()
         if _is_tensor(samples):
             import torch
-            n, nw = samples.numel(), starts.numel()
+            nw = starts.numel()
             r = self._outputs(nw, samples.device)
-            _check(L.gfdm_hip_burst_sync_find_frame_start_at_device(self._h, *[r[k].data_ptr() for k in self._OUT], self._dp(samples, n, "samples"), n,
-                                                                    _dev_arg(starts, torch.int64, nw, "starts", self._dev), nw, self._sp(stream)))
+            _check(getattr(L, "gfdm_hip_burst_sync_find_frame_start_at%s_device" % fmt)(self._h, *[r[k].data_ptr() for k in self._OUT], sptr, n,
+                                                                                       _dev_arg(starts, torch.int64, nw, "starts", self._dev), nw,
+                                                                                       self._sp(stream)))
             return r
-        a = _c64(samples).ravel()
         st = np.ascontiguousarray(starts, dtype=np.int64).ravel()
         r = self._outputs(st.size)
-        _check(L.gfdm_hip_burst_sync_find_frame_start_at_host(self._h, *[r[k].ctypes.data for k in self._OUT], a.ctypes.data, a.size, st.ctypes.data, st.size))
+        _check(getattr(L, "gfdm_hip_burst_sync_find_frame_start_at%s_host" % fmt)(self._h, *[r[k].ctypes.data for k in self._OUT], sptr, n, st.ctypes.data,
+                                                                                 st.size))
         return r
 
     def detect(self, samples, threshold, min_distance, lead=None, max_bursts=None, stream=None):
@@ -1177,8 +1257,8 @@ class BurstSync(_Kernel):
         count (total peaks found: int on the host path, a one-element int64 tensor on the device path, which does not synchronise) and
         the five find_frame_start arrays with max_bursts slots, those from min(count, max_bursts) on at frame_start = coarse = -1.
         Defaults: lead = cp_len + fft_len // 2, max_bursts = ceil(P / (min_distance + 1)), the most peaks P positions can hold."""
+        sptr, n, fmt, _keep = _capture(samples, self._dev)
         L = lib()
-        n = samples.numel() if _is_tensor(samples) else np.asarray(samples).size
         R = int(min_distance)
         lead = self.cp_len() + self.fft_len() // 2 if lead is None else int(lead)
         if max_bursts is None:
@@ -1191,33 +1271,33 @@ class BurstSync(_Kernel):
             r = self._outputs(nb, d)
             count = torch.empty(1, dtype=torch.int64, device=d)
             ws = torch.empty(L.gfdm_hip_burst_sync_detect_workspace_bytes(self._h, n), dtype=torch.uint8, device=d)
-            _check(L.gfdm_hip_burst_sync_detect_device(self._h, count.data_ptr(), *[r[k].data_ptr() for k in self._OUT], self._dp(samples, n, "samples"), n,
-                                                       threshold, R, lead, nb, ws.data_ptr(), self._sp(stream)))
+            _check(getattr(L, "gfdm_hip_burst_sync_detect%s_device" % fmt)(self._h, count.data_ptr(), *[r[k].data_ptr() for k in self._OUT], sptr, n,
+                                                                          threshold, R, lead, nb, ws.data_ptr(), self._sp(stream)))
             r["count"] = count
             return r
-        a = _c64(samples).ravel()
         r = self._outputs(nb)
         count = np.zeros(1, np.int64)
-        _check(L.gfdm_hip_burst_sync_detect_host(self._h, count.ctypes.data, *[r[k].ctypes.data for k in self._OUT], a.ctypes.data, n, threshold, R, lead, nb))
+        _check(getattr(L, "gfdm_hip_burst_sync_detect%s_host" % fmt)(self._h, count.ctypes.data, *[r[k].ctypes.data for k in self._OUT], sptr, n, threshold, R,
+                                                                    lead, nb))
         r["count"] = int(count[0])
         return r
 
     def auto_correlate(self, samples, first=0, stride=None, n_windows=1, stream=None):
         """(ac, ic): [n_windows][corr_len] complex64 / float32 (pygfdm's auto_correlate_signal and abs_integrate)."""
+        sptr, n, fmt, _keep = _capture(samples, self._dev)
         L = lib()
-        n, first, stride, nw = self._grid(samples, first, stride, n_windows)
+        first, stride, nw = self._grid(first, stride, n_windows)
         P = self.corr_len()
         if _is_tensor(samples):
             import torch
             ac = torch.empty(nw, P, dtype=torch.complex64, device=samples.device)
             ic = torch.empty(nw, P, dtype=torch.float32, device=samples.device)
-            _check(L.gfdm_hip_burst_sync_auto_correlate_device(self._h, ac.data_ptr(), ic.data_ptr(), self._dp(samples, n, "samples"), n, first, stride, nw,
-                                                               self._sp(stream)))
+            _check(getattr(L, "gfdm_hip_burst_sync_auto_correlate%s_device" % fmt)(self._h, ac.data_ptr(), ic.data_ptr(), sptr, n, first, stride, nw,
+                                                                                  self._sp(stream)))
             return ac, ic
-        a = _c64(samples).ravel()
         ac = np.empty((nw, P), np.complex64)
         ic = np.empty((nw, P), np.float32)
-        _check(L.gfdm_hip_burst_sync_auto_correlate_host(self._h, ac.ctypes.data, ic.ctypes.data, a.ctypes.data, n, first, stride, nw))
+        _check(getattr(L, "gfdm_hip_burst_sync_auto_correlate%s_host" % fmt)(self._h, ac.ctypes.data, ic.ctypes.data, sptr, n, first, stride, nw))
         return ac, ic
 
 
@@ -1248,7 +1328,9 @@ class BurstExtractor(_Kernel):
         return bool(lib().gfdm_hip_burst_extractor_get_cfo_correction(self._h))
 
     def extract(self, samples, offsets, scale=None, sc_rot=None, stream=None):
-        """[n][burst_len] bursts; offsets are tag positions in `samples` (the extractor subtracts tag_backoff)."""
+        """[n][burst_len] bursts; offsets are tag positions in `samples` (the extractor subtracts tag_backoff).  An int16 capture, shape (n, 2)
+        or (2n,), is read as sc16, unscaled: scale = 1 / 32768 gives unit full scale."""
+        sptr, slen, fmt, _keep = _capture(samples, self._dev)
         L = lib()
         B = self.burst_len()
         if _is_tensor(samples):
@@ -1257,10 +1339,10 @@ class BurstExtractor(_Kernel):
             out = torch.empty(n, B, dtype=torch.complex64, device=samples.device)
             sp = None if scale is None else _dev_arg(scale, torch.float32, n, "scale", self._dev)
             rp = None if sc_rot is None else _dev_arg(sc_rot, torch.complex64, n, "sc_rot", self._dev)
-            _check(L.gfdm_hip_burst_extractor_extract_device(self._h, out.data_ptr(), self._dp(samples, samples.numel(), "samples"), samples.numel(),
-                                                             _dev_arg(offsets, torch.int64, n, "offsets", self._dev), sp, rp, n, self._sp(stream)))
+            _check(getattr(L, "gfdm_hip_burst_extractor_extract%s_device" % fmt)(self._h, out.data_ptr(), sptr, slen,
+                                                                                _dev_arg(offsets, torch.int64, n, "offsets", self._dev), sp, rp, n,
+                                                                                self._sp(stream)))
             return out
-        a = _c64(samples).ravel()
         off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
         n = off.size
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32).ravel()
@@ -1269,6 +1351,6 @@ class BurstExtractor(_Kernel):
             if v is not None and v.size != n:
                 raise RuntimeError("%s has %d elements, expected %d" % (what, v.size, n))
         out = np.empty((n, B), np.complex64)
-        _check(L.gfdm_hip_burst_extractor_extract_host(self._h, out.ctypes.data, a.ctypes.data, a.size, off.ctypes.data,
-                                                       None if sc is None else sc.ctypes.data, None if rot is None else rot.ctypes.data, n))
+        _check(getattr(L, "gfdm_hip_burst_extractor_extract%s_host" % fmt)(self._h, out.ctypes.data, sptr, slen, off.ctypes.data,
+                                                                          None if sc is None else sc.ctypes.data, None if rot is None else rot.ctypes.data, n))
         return out

@@ -548,6 +548,56 @@ int gfdm_hip_burst_extractor_extract_host(gfdm_hip_burst_extractor* e, float* ou
 int gfdm_hip_burst_extractor_extract_device(gfdm_hip_burst_extractor* e, void* out, const void* samples, int64_t stream_len, const void* offsets,
                                             const void* scale, const void* sc_rot, int64_t n_bursts, void* stream);
 
+/* ---- sc16 captures: interleaved int16 I/Q as UHD streams and capture files deliver it --------------------------------------------
+ * Every call above that reads a capture has a *_sc16_* twin.  An sc16 capture of n samples is 2 n int16 values I0, Q0, I1, Q1, ... in
+ * native byte order; sample i is (float)I_i + j (float)Q_i, UNSCALED (pygfdm's convert_from_sc16).  stream_len, first, stride, starts
+ * and offsets count samples, not int16 values.  `samples` is const int16_t* in the host flavours and a device pointer (const void*) in
+ * the device flavours; it needs the alignment of one sample, 4 bytes, and no more (a capture may start at an odd sample of a larger
+ * buffer).  Everything else -- the other arguments, checks, error codes, limits, detect_workspace_bytes, count and the spare-slot
+ * sentinels, all outputs (complex64 / float32 / int64) -- is that of the call without _sc16.
+ * CONTRACT: a *_sc16_* call returns, bit for bit, what its twin returns on the same capture widened to complex64.  int16 -> fp32 is
+ * exact, the kernels are the same ones with the sample format as a launch-uniform field, and nothing behind the load depends on it.
+ * There is no full-scale argument: ac, ic, cfo, metric and the peak positions do not depend on the scale (an all-zero stretch gives
+ * ac = 0 as above), and the preamble equaliser divides any gain out of the receivers; the extractor keeps its per-burst `scale`
+ * (1 / 32768 there gives unit full scale).
+ * The device flavours neither allocate nor synchronise and are hipGraph-capturable, like their twins.  The host flavours upload the
+ * int16 data as it is -- half the bytes of the complex64 copy -- and never widen it on the host. */
+int gfdm_hip_burst_sync_find_frame_start_sc16_host(gfdm_hip_burst_sync* s, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
+                                                   const int16_t* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows);
+int gfdm_hip_burst_sync_find_frame_start_sc16_device(gfdm_hip_burst_sync* s, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                                     const void* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows,
+                                                     void* stream);
+int gfdm_hip_burst_sync_auto_correlate_sc16_host(gfdm_hip_burst_sync* s, float* ac, float* ic, const int16_t* samples, int64_t stream_len, int64_t first,
+                                                 int64_t stride, int64_t n_windows);
+int gfdm_hip_burst_sync_auto_correlate_sc16_device(gfdm_hip_burst_sync* s, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
+                                                   int64_t stride, int64_t n_windows, void* stream);
+int gfdm_hip_burst_sync_find_frame_start_at_sc16_host(gfdm_hip_burst_sync* s, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric,
+                                                      float* sc_rot, const int16_t* samples, int64_t stream_len, const int64_t* starts, int64_t n_windows);
+int gfdm_hip_burst_sync_find_frame_start_at_sc16_device(gfdm_hip_burst_sync* s, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                                        const void* samples, int64_t stream_len, const void* starts, int64_t n_windows, void* stream);
+int gfdm_hip_burst_sync_detect_sc16_host(gfdm_hip_burst_sync* s, int64_t* count, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric,
+                                         float* sc_rot, const int16_t* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead,
+                                         int64_t max_bursts);
+int gfdm_hip_burst_sync_detect_sc16_device(gfdm_hip_burst_sync* s, void* count, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
+                                           const void* samples, int64_t stream_len, float threshold, int64_t min_distance, int64_t lead, int64_t max_bursts,
+                                           void* workspace, void* stream);
+int gfdm_hip_burst_extractor_extract_sc16_host(gfdm_hip_burst_extractor* e, float* out, const int16_t* samples, int64_t stream_len, const int64_t* offsets,
+                                               const float* scale, const float* sc_rot, int64_t n_bursts);
+int gfdm_hip_burst_extractor_extract_sc16_device(gfdm_hip_burst_extractor* e, void* out, const void* samples, int64_t stream_len, const void* offsets,
+                                                 const void* scale, const void* sc_rot, int64_t n_bursts, void* stream);
+int gfdm_hip_receiver_demodulate_bursts_sc16_host(gfdm_hip_receiver* r, float* out, const int16_t* samples, int64_t stream_len, const int64_t* offsets,
+                                                  const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction,
+                                                  int noutput_size, int64_t n_bursts);
+int gfdm_hip_receiver_demodulate_bursts_sc16_device(gfdm_hip_receiver* r, void* out, const void* samples, int64_t stream_len, const void* offsets,
+                                                    const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
+                                                    int noutput_size, int64_t n_bursts, void* stream);
+int gfdm_hip_advanced_receiver_work_bursts_sc16_host(gfdm_hip_advanced_receiver* a, float* out, const int16_t* samples, int64_t stream_len,
+                                                     const int64_t* offsets, const float* sc_rot, const int64_t* count, int backoff, int preamble_offset,
+                                                     int cfo_correction, int noutput_size, int64_t n_bursts);
+int gfdm_hip_advanced_receiver_work_bursts_sc16_device(gfdm_hip_advanced_receiver* a, void* out, const void* samples, int64_t stream_len,
+                                                       const void* offsets, const void* sc_rot, const void* count, int backoff, int preamble_offset,
+                                                       int cfo_correction, int noutput_size, int64_t n_bursts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
