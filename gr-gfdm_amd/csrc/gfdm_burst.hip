@@ -22,8 +22,10 @@
 // Extractor: out[b][n] = scale_b s[off_b - backoff + n] (conj(r_b) / |r_b|)^n, samples outside [0, stream_len) read as zero.  The
 // phase of sample n is reduced in fp64 (n angle(r) mod 2 pi) and only then rounded to fp32 for sincos, so the rotation error does
 // not grow with n (an fp32 recurrence as in volk's rotator drifts by ~n ulp).
+//
+// The *_host flavours are the device entry points between an upload and a download on the handle's own stream (gfdm_hostcall.h).
 #include "../../include/gfdm_hip.h"
-#include "gfdm_plan.h"
+#include "gfdm_hostcall.h"
 #include "gfdm_dft.h"
 #include "gfdm_burstfetch.h"
 
@@ -36,38 +38,11 @@
 
 using gfdm::cf;
 using gfdm::api_fail;
-using gfdm::api_fail_hip;
+using gfdm::DeviceGuard;
+using gfdm::DevBuf;
+using gfdm::sample_bytes;
 
 namespace {
-
-#define BURST_TRY(expr)                                          \
-    do {                                                         \
-        hipError_t _e = (expr);                                  \
-        if (_e != hipSuccess) return api_fail_hip(_e, #expr);    \
-    } while (0)
-
-// as in gfdm_stages.hip: clears the sticky HIP error of earlier calls, selects the handle's device for the scope
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        (void)hipGetLastError();
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int open_device(int dev)
-{
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return api_fail(GFDM_HIP_ENODEV, "no HIP device available (this library has no CPU path)");
-    if (dev < 0 || dev >= count) return api_fail(GFDM_HIP_ENODEV, "HIP device ordinal out of range");
-    DeviceGuard guard(dev);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return GFDM_HIP_OK;
-}
 
 constexpr int kTile = 256;               // correlation positions per workgroup, one per lane
 constexpr int kMaxK = 1024;
@@ -494,40 +469,22 @@ __global__ __launch_bounds__(kTile) void k_detect_scatter(const int* __restrict_
 
 size_t sync_lds(int K, bool fine) { return (size_t)(kTile + 2 * K + (fine ? 2 * K : 0)) * sizeof(cf) + kTile * sizeof(float); }
 
-// bytes of one sample of a capture: the host flavours upload it in the caller's format
-size_t sample_bytes(int fmt) { return fmt == gfdm::SAMPLES_SC16 ? sizeof(gfdm::sc16_io) : sizeof(cf); }
-
-// a device buffer that lives for one host call
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
 }  // namespace
 
 struct gfdm_hip_burst_sync {
-    int device = 0;
-    hipStream_t stream = nullptr;
+    gfdm::DeviceCtx ctx;
     int K = 0, cp = 0, W = 0;
     cf* d_preamble = nullptr;          // [2K], normalised to unit average energy
     ~gfdm_hip_burst_sync()
     {
-        DeviceGuard guard(device);
+        DeviceGuard guard(ctx.device);
         if (d_preamble) (void)hipFree(d_preamble);
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 
 struct gfdm_hip_burst_extractor {
-    int device = 0;
-    hipStream_t stream = nullptr;
+    gfdm::DeviceCtx ctx;
     int burst_len = 0, backoff = 0, correct = 1;
-    ~gfdm_hip_burst_extractor()
-    {
-        DeviceGuard guard(device);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace {
@@ -551,7 +508,6 @@ int check_windows(const gfdm_hip_burst_sync* h, const void* samples, int64_t str
     return GFDM_HIP_OK;
 }
 
-// enqueue the synchroniser; fused (frame_start != NULL) or the auto-correlation stage (ac / ic)
 SyncArgs grid_args(const gfdm_hip_burst_sync* h, const void* samples, int fmt, int64_t first, int64_t stride, int64_t n, int64_t origin)
 {
     return SyncArgs{ samples, fmt, first, stride, n, origin, h->W, h->K, h->cp, h->W - 2 * h->K, nullptr, 0, 0, 0 };
@@ -563,93 +519,64 @@ SyncArgs list_args(const gfdm_hip_burst_sync* h, const void* samples, int fmt, i
     return SyncArgs{ samples, fmt, 0, 0, n, 0, h->W, h->K, h->cp, h->W - 2 * h->K, starts, nstarts, stream_len - h->W, skip_empty };
 }
 
-int sync_enqueue(gfdm_hip_burst_sync* h, const SyncArgs& a, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, cf* sc_rot, cf* ac, float* ic,
-                 hipStream_t s)
+// the five per-window outputs of a synchroniser call, on the device or (host paths) in the caller's arrays
+struct SyncOut {
+    int64_t* frame_start; int64_t* coarse; float* cfo; float* metric; cf* sc_rot;
+    bool complete() const { return frame_start && coarse && cfo && metric && sc_rot; }
+};
+SyncOut sync_out(void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot)      // from the pointers of the C-ABI
+{
+    return SyncOut{ static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric), static_cast<cf*>(sc_rot) };
+}
+
+dim3 sync_grid(const SyncArgs& a) { return dim3((unsigned)((a.P + kTile - 1) / kTile), (unsigned)std::min<int64_t>(a.nwin, kMaxGridY)); }
+
+// enqueue the auto-correlation stage: ac and / or ic of every position of every window
+int ac_enqueue(gfdm_hip_burst_sync* h, const SyncArgs& a, cf* ac, float* ic, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sync_ic, sync_grid(a), dim3(kTile), sync_lds(h->K, false), s, a, ac, ic, (unsigned long long*)nullptr);
+    GFDM_TRY(hipGetLastError());
+    return GFDM_HIP_OK;
+}
+
+// enqueue the fused synchroniser: the four launches of the file head, the argmax keys in o.coarse and o.frame_start until the last one
+int sync_enqueue(gfdm_hip_burst_sync* h, const SyncArgs& a, const SyncOut& o, hipStream_t s)
 {
     const int64_t n = a.nwin;
-    const dim3 grid((unsigned)((a.P + kTile - 1) / kTile), (unsigned)std::min<int64_t>(n, kMaxGridY));
-    if (!frame_start) {
-        hipLaunchKernelGGL(k_sync_ic, grid, dim3(kTile), sync_lds(h->K, false), s, a, ac, ic, (unsigned long long*)nullptr);
-        BURST_TRY(hipGetLastError());
-        return GFDM_HIP_OK;
-    }
-    BURST_TRY(hipMemsetAsync(frame_start, 0, (size_t)n * sizeof(int64_t), s));
-    BURST_TRY(hipMemsetAsync(coarse, 0, (size_t)n * sizeof(int64_t), s));
-    hipLaunchKernelGGL(k_sync_ic, grid, dim3(kTile), sync_lds(h->K, false), s, a, (cf*)nullptr, (float*)nullptr, (unsigned long long*)coarse);
-    BURST_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sync_coarse, dim3((unsigned)std::min<int64_t>(n, 1 << 20)), dim3(64), 0, s, a, (const unsigned long long*)coarse, cfo, metric, sc_rot);
-    BURST_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sync_fine, grid, dim3(kTile), sync_lds(h->K, true), s, a, (const cf*)h->d_preamble, (const float*)cfo, (unsigned long long*)frame_start);
-    BURST_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sync_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, frame_start, coarse);
-    BURST_TRY(hipGetLastError());
+    const dim3 grid = sync_grid(a);
+    GFDM_TRY(hipMemsetAsync(o.frame_start, 0, (size_t)n * sizeof(int64_t), s));
+    GFDM_TRY(hipMemsetAsync(o.coarse, 0, (size_t)n * sizeof(int64_t), s));
+    hipLaunchKernelGGL(k_sync_ic, grid, dim3(kTile), sync_lds(h->K, false), s, a, (cf*)nullptr, (float*)nullptr, (unsigned long long*)o.coarse);
+    GFDM_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sync_coarse, dim3((unsigned)std::min<int64_t>(n, 1 << 20)), dim3(64), 0, s, a, (const unsigned long long*)o.coarse, o.cfo, o.metric, o.sc_rot);
+    GFDM_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sync_fine, grid, dim3(kTile), sync_lds(h->K, true), s, a, (const cf*)h->d_preamble, (const float*)o.cfo, (unsigned long long*)o.frame_start);
+    GFDM_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sync_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, o.frame_start, o.coarse);
+    GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
 
-// host path of the synchroniser: the span the windows cover goes up, the results come back
-int sync_host(gfdm_hip_burst_sync* h, const void* samples, int fmt, int64_t first, int64_t stride, int64_t n, int64_t* frame_start, int64_t* coarse, float* cfo,
-              float* metric, float* sc_rot, float* ac, float* ic)
-{
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const int64_t span = (n - 1) * stride + h->W, P = h->W - 2 * h->K;
-    DevBuf d_in, d_out;
-    const size_t sb = sample_bytes(fmt);
-    BURST_TRY(d_in.alloc((size_t)span * sb));
-    const size_t n_res = (size_t)n * (2 * sizeof(int64_t) + 2 * sizeof(float) + sizeof(cf));
-    const size_t n_stage = (size_t)n * P * (sizeof(cf) + sizeof(float));
-    BURST_TRY(d_out.alloc(frame_start ? n_res : n_stage));
-    BURST_TRY(hipMemcpyAsync(d_in.p, static_cast<const unsigned char*>(samples) + (size_t)first * sb, (size_t)span * sb, hipMemcpyHostToDevice, h->stream));
-    unsigned char* o = static_cast<unsigned char*>(d_out.p);
-    int rc;
-    if (frame_start) {
-        int64_t* d_fs = reinterpret_cast<int64_t*>(o);
-        int64_t* d_co = d_fs + n;
-        cf* d_rot = reinterpret_cast<cf*>(d_co + n);
-        float* d_cfo = reinterpret_cast<float*>(d_rot + n);
-        float* d_met = d_cfo + n;
-        rc = sync_enqueue(h, grid_args(h, d_in.p, fmt, 0, stride, n, first), d_fs, d_co, d_cfo, d_met, d_rot, nullptr, nullptr, h->stream);
-        if (rc != GFDM_HIP_OK) return rc;
-        BURST_TRY(hipMemcpyAsync(frame_start, d_fs, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        BURST_TRY(hipMemcpyAsync(coarse, d_co, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        BURST_TRY(hipMemcpyAsync(sc_rot, d_rot, (size_t)n * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
-        BURST_TRY(hipMemcpyAsync(cfo, d_cfo, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        BURST_TRY(hipMemcpyAsync(metric, d_met, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    } else {
-        cf* d_ac = reinterpret_cast<cf*>(o);
-        float* d_ic = reinterpret_cast<float*>(d_ac + (size_t)n * P);
-        rc = sync_enqueue(h, grid_args(h, d_in.p, fmt, 0, stride, n, first), nullptr, nullptr, nullptr, nullptr, nullptr, d_ac, d_ic, h->stream);
-        if (rc != GFDM_HIP_OK) return rc;
-        if (ac) BURST_TRY(hipMemcpyAsync(ac, d_ac, (size_t)n * P * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
-        if (ic) BURST_TRY(hipMemcpyAsync(ic, d_ic, (size_t)n * P * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    }
-    BURST_TRY(hipStreamSynchronize(h->stream));
-    return GFDM_HIP_OK;
-}
-
-// ---- host side of find_frame_start_at and detect ----
-struct SyncOut { int64_t* frame_start; int64_t* coarse; float* cfo; float* metric; cf* sc_rot; };
-
-// the five per-window outputs of n windows in one device buffer (int64 first: alignment)
-SyncOut carve_out(void* p, int64_t n)
+// ---- host paths: the five outputs of n windows in one device buffer (int64 first: alignment), and back into the caller's arrays ----
+size_t out_bytes(int64_t n) { return (size_t)n * (2 * sizeof(int64_t) + 2 * sizeof(float) + sizeof(cf)); }
+SyncOut carve_out(DevBuf& b, int64_t n)
 {
     SyncOut o;
-    o.frame_start = static_cast<int64_t*>(p);
-    o.coarse = o.frame_start + n;
-    o.sc_rot = reinterpret_cast<cf*>(o.coarse + n);
-    o.cfo = reinterpret_cast<float*>(o.sc_rot + n);
-    o.metric = o.cfo + n;
+    o.frame_start = b.take<int64_t>(n);
+    o.coarse = b.take<int64_t>(n);
+    o.sc_rot = b.take<cf>(n);
+    o.cfo = b.take<float>(n);
+    o.metric = b.take<float>(n);
     return o;
 }
-size_t out_bytes(int64_t n) { return (size_t)n * (2 * sizeof(int64_t) + 2 * sizeof(float) + sizeof(cf)); }
 
-int fetch_out(const SyncOut& d, int64_t n, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot, hipStream_t s)
+int fetch_out(const SyncOut& host, const SyncOut& d, int64_t n, hipStream_t s)
 {
-    BURST_TRY(hipMemcpyAsync(frame_start, d.frame_start, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    BURST_TRY(hipMemcpyAsync(coarse, d.coarse, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    BURST_TRY(hipMemcpyAsync(sc_rot, d.sc_rot, (size_t)n * sizeof(cf), hipMemcpyDeviceToHost, s));
-    BURST_TRY(hipMemcpyAsync(cfo, d.cfo, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-    BURST_TRY(hipMemcpyAsync(metric, d.metric, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    GFDM_TRY(gfdm::download(host.frame_start, d.frame_start, (size_t)n * sizeof(int64_t), s));
+    GFDM_TRY(gfdm::download(host.coarse, d.coarse, (size_t)n * sizeof(int64_t), s));
+    GFDM_TRY(gfdm::download(host.sc_rot, d.sc_rot, (size_t)n * sizeof(cf), s));
+    GFDM_TRY(gfdm::download(host.cfo, d.cfo, (size_t)n * sizeof(float), s));
+    GFDM_TRY(gfdm::download(host.metric, d.metric, (size_t)n * sizeof(float), s));
     return GFDM_HIP_OK;
 }
 
@@ -724,15 +651,15 @@ int detect_enqueue(gfdm_hip_burst_sync* h, int64_t* count, const SyncOut& o, con
     const int P = (int)(stream_len - 2 * h->K);
     const ScanArgs a = { samples, fmt, (int)stream_len, h->K, h->cp, P, (int)std::min<int64_t>(R, P), g.per, g.cap, threshold };
     hipLaunchKernelGGL(k_detect_scan, dim3((unsigned)g.ntiles), dim3(kTile), scan_lds(h->K, g.per), s, a, counts, list);
-    BURST_TRY(hipGetLastError());
+    GFDM_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_detect_offsets, dim3(1), dim3(kTile), 0, s, (const int*)counts, offs, g.ntiles, count);
-    BURST_TRY(hipGetLastError());
+    GFDM_TRY(hipGetLastError());
     if (max_bursts == 0) return GFDM_HIP_OK;
     const int64_t nslots = std::min(max_bursts, g.nstarts);
     hipLaunchKernelGGL(k_detect_scatter, dim3((unsigned)std::min(g.ntiles, 1024)), dim3(kTile), 0, s, (const int*)counts, (const int*)offs, (const int*)list, g.cap,
                        g.ntiles, (int)lead, stream_len - h->W, starts, nslots, (const int64_t*)count);
-    BURST_TRY(hipGetLastError());
-    return sync_enqueue(h, list_args(h, samples, fmt, stream_len, starts, nslots, max_bursts, 1), o.frame_start, o.coarse, o.cfo, o.metric, o.sc_rot, nullptr, nullptr, s);
+    GFDM_TRY(hipGetLastError());
+    return sync_enqueue(h, list_args(h, samples, fmt, stream_len, starts, nslots, max_bursts, 1), o, s);
 }
 
 int extract_check(const gfdm_hip_burst_extractor* h, const void* out, const void* samples, int64_t stream_len, const void* offsets, int64_t n)
@@ -748,7 +675,7 @@ int extract_enqueue(gfdm_hip_burst_extractor* h, cf* out, const void* samples, i
 {
     const dim3 grid((unsigned)std::min((h->burst_len + kTile - 1) / kTile, 64), (unsigned)std::min<int64_t>(n, kMaxGridY));
     hipLaunchKernelGGL(k_extract, grid, dim3(kTile), 0, s, out, samples, fmt, stream_len, offsets, scale, sc_rot, h->correct, h->burst_len, h->backoff, n);
-    BURST_TRY(hipGetLastError());
+    GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
 
@@ -763,21 +690,36 @@ int sync_find_frame_start_device(int fmt, gfdm_hip_burst_sync* h, void* frame_st
 {
     int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->device);
+    const SyncOut o = sync_out(frame_start, coarse, cfo, metric, sc_rot);
+    if (!o.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->ctx.device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), static_cast<int64_t*>(frame_start),
-                        static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric), static_cast<cf*>(sc_rot), nullptr, nullptr,
-                        (hipStream_t)stream);
+    return sync_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), o, (hipStream_t)stream);
 }
 
+// host paths over a window grid: the span the windows cover goes up (the grid starts at its sample 0, origin = first), the results come back
 int sync_find_frame_start_host(int fmt, gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
                                               const void* samples, int64_t stream_len, int64_t first, int64_t stride, int64_t n_windows)
 {
     int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    return sync_host(h, samples, fmt, first, stride, n_windows, frame_start, coarse, cfo, metric, sc_rot, nullptr, nullptr);
+    const SyncOut host = sync_out(frame_start, coarse, cfo, metric, sc_rot);
+    if (!host.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->ctx.device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const int64_t n = n_windows;
+    const size_t sb = sample_bytes(fmt), span = (size_t)((n - 1) * stride + h->W) * sb;
+    DevBuf d_in, d_out;
+    GFDM_TRY(d_in.alloc(span));
+    GFDM_TRY(d_out.alloc(out_bytes(n)));
+    GFDM_TRY(gfdm::upload(d_in.p, static_cast<const unsigned char*>(samples) + (size_t)first * sb, span, h->ctx.stream));
+    const SyncOut o = carve_out(d_out, n);
+    rc = sync_enqueue(h, grid_args(h, d_in.p, fmt, 0, stride, n, first), o, h->ctx.stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    rc = fetch_out(host, o, n, h->ctx.stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
+    return GFDM_HIP_OK;
 }
 
 int sync_auto_correlate_device(int fmt, gfdm_hip_burst_sync* h, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
@@ -786,10 +728,9 @@ int sync_auto_correlate_device(int fmt, gfdm_hip_burst_sync* h, void* ac, void* 
     int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->ctx.device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), nullptr, nullptr, nullptr, nullptr, nullptr,
-                        static_cast<cf*>(ac), static_cast<float*>(ic), (hipStream_t)stream);
+    return ac_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), static_cast<cf*>(ac), static_cast<float*>(ic), (hipStream_t)stream);
 }
 
 int sync_auto_correlate_host(int fmt, gfdm_hip_burst_sync* h, float* ac, float* ic, const void* samples, int64_t stream_len, int64_t first,
@@ -798,7 +739,22 @@ int sync_auto_correlate_host(int fmt, gfdm_hip_burst_sync* h, float* ac, float* 
     int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
-    return sync_host(h, samples, fmt, first, stride, n_windows, nullptr, nullptr, nullptr, nullptr, nullptr, ac, ic);
+    DeviceGuard guard(h->ctx.device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const int64_t n = n_windows;
+    const size_t sb = sample_bytes(fmt), span = (size_t)((n - 1) * stride + h->W) * sb, np = (size_t)n * (h->W - 2 * h->K);
+    DevBuf d_in, d_out;
+    GFDM_TRY(d_in.alloc(span));
+    GFDM_TRY(d_out.alloc(np * (sizeof(cf) + sizeof(float))));
+    GFDM_TRY(gfdm::upload(d_in.p, static_cast<const unsigned char*>(samples) + (size_t)first * sb, span, h->ctx.stream));
+    cf* d_ac = d_out.take<cf>(np);
+    float* d_ic = d_out.take<float>(np);
+    rc = ac_enqueue(h, grid_args(h, d_in.p, fmt, 0, stride, n, first), d_ac, d_ic, h->ctx.stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    GFDM_TRY(gfdm::download(ac, d_ac, np * sizeof(cf), h->ctx.stream));          // (an output the caller left out is skipped)
+    GFDM_TRY(gfdm::download(ic, d_ic, np * sizeof(float), h->ctx.stream));
+    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
+    return GFDM_HIP_OK;
 }
 
 /* windows at arbitrary starts: the regular-grid kernels with a start array (bit-equal results per window) */
@@ -807,12 +763,11 @@ int sync_find_frame_start_at_device(int fmt, gfdm_hip_burst_sync* h, void* frame
 {
     int rc = check_at(h, samples, stream_len, starts, n_windows);
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->device);
+    const SyncOut o = sync_out(frame_start, coarse, cfo, metric, sc_rot);
+    if (!o.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->ctx.device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, list_args(h, samples, fmt, stream_len, static_cast<const int64_t*>(starts), n_windows, n_windows, 0),
-                        static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric),
-                        static_cast<cf*>(sc_rot), nullptr, nullptr, (hipStream_t)stream);
+    return sync_enqueue(h, list_args(h, samples, fmt, stream_len, static_cast<const int64_t*>(starts), n_windows, n_windows, 0), o, (hipStream_t)stream);
 }
 
 int sync_find_frame_start_at_host(int fmt, gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
@@ -820,23 +775,23 @@ int sync_find_frame_start_at_host(int fmt, gfdm_hip_burst_sync* h, int64_t* fram
 {
     int rc = check_at(h, samples, stream_len, starts, n_windows);
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
-    if (!frame_start || !coarse || !cfo || !metric || !sc_rot) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->device);
+    const SyncOut host = sync_out(frame_start, coarse, cfo, metric, sc_rot);
+    if (!host.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    DeviceGuard guard(h->ctx.device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const int64_t n = n_windows;
     DevBuf d_in, d_st, d_out;
-    BURST_TRY(d_in.alloc((size_t)stream_len * sample_bytes(fmt)));
-    BURST_TRY(d_st.alloc((size_t)n * sizeof(int64_t)));
-    BURST_TRY(d_out.alloc(out_bytes(n)));
-    BURST_TRY(hipMemcpyAsync(d_in.p, samples, (size_t)stream_len * sample_bytes(fmt), hipMemcpyHostToDevice, h->stream));
-    BURST_TRY(hipMemcpyAsync(d_st.p, starts, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    const SyncOut o = carve_out(d_out.p, n);
-    rc = sync_enqueue(h, list_args(h, d_in.p, fmt, stream_len, static_cast<const int64_t*>(d_st.p), n, n, 0), o.frame_start, o.coarse, o.cfo,
-                      o.metric, o.sc_rot, nullptr, nullptr, h->stream);
+    GFDM_TRY(d_in.alloc((size_t)stream_len * sample_bytes(fmt)));
+    GFDM_TRY(d_st.alloc((size_t)n * sizeof(int64_t)));
+    GFDM_TRY(d_out.alloc(out_bytes(n)));
+    GFDM_TRY(gfdm::upload(d_in.p, samples, (size_t)stream_len * sample_bytes(fmt), h->ctx.stream));
+    GFDM_TRY(gfdm::upload(d_st.p, starts, (size_t)n * sizeof(int64_t), h->ctx.stream));
+    const SyncOut o = carve_out(d_out, n);
+    rc = sync_enqueue(h, list_args(h, d_in.p, fmt, stream_len, d_st.as<const int64_t>(), n, n, 0), o, h->ctx.stream);
     if (rc != GFDM_HIP_OK) return rc;
-    rc = fetch_out(o, n, frame_start, coarse, cfo, metric, sc_rot, h->stream);
+    rc = fetch_out(host, o, n, h->ctx.stream);
     if (rc != GFDM_HIP_OK) return rc;
-    BURST_TRY(hipStreamSynchronize(h->stream));
+    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
     return GFDM_HIP_OK;
 }
 
@@ -848,12 +803,11 @@ int sync_detect_device(int fmt, gfdm_hip_burst_sync* h, void* count, void* frame
     int rc = detect_check(h->K, h->cp, h->W, stream_len, threshold, min_distance, lead, max_bursts);
     if (rc != GFDM_HIP_OK) return rc;
     if (!samples || !count || !workspace) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
-    if (max_bursts > 0 && (!frame_start || !coarse || !cfo || !metric || !sc_rot)) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    const SyncOut o = sync_out(frame_start, coarse, cfo, metric, sc_rot);
+    if (max_bursts > 0 && !o.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
     if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->ctx.device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const SyncOut o = { static_cast<int64_t*>(frame_start), static_cast<int64_t*>(coarse), static_cast<float*>(cfo), static_cast<float*>(metric),
-                        static_cast<cf*>(sc_rot) };
     return detect_enqueue(h, static_cast<int64_t*>(count), o, samples, fmt, stream_len, threshold, min_distance, lead, max_bursts, workspace,
                           (hipStream_t)stream);
 }
@@ -865,26 +819,27 @@ int sync_detect_host(int fmt, gfdm_hip_burst_sync* h, int64_t* count, int64_t* f
     int rc = detect_check(h->K, h->cp, h->W, stream_len, threshold, min_distance, lead, max_bursts);
     if (rc != GFDM_HIP_OK) return rc;
     if (!samples || !count) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
-    if (max_bursts > 0 && (!frame_start || !coarse || !cfo || !metric || !sc_rot)) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
+    const SyncOut host = sync_out(frame_start, coarse, cfo, metric, sc_rot);
+    if (max_bursts > 0 && !host.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
     if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->ctx.device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const int64_t n = max_bursts;
     DevBuf d_in, d_ws, d_out, d_count;
-    BURST_TRY(d_in.alloc((size_t)stream_len * sample_bytes(fmt)));
-    BURST_TRY(d_ws.alloc(detect_geom(h, stream_len).bytes));
-    BURST_TRY(d_out.alloc(out_bytes(n)));
-    BURST_TRY(d_count.alloc(sizeof(int64_t)));
-    BURST_TRY(hipMemcpyAsync(d_in.p, samples, (size_t)stream_len * sample_bytes(fmt), hipMemcpyHostToDevice, h->stream));
-    const SyncOut o = carve_out(d_out.p, n);
-    rc = detect_enqueue(h, static_cast<int64_t*>(d_count.p), o, d_in.p, fmt, stream_len, threshold, min_distance, lead, n, d_ws.p, h->stream);
+    GFDM_TRY(d_in.alloc((size_t)stream_len * sample_bytes(fmt)));
+    GFDM_TRY(d_ws.alloc(detect_geom(h, stream_len).bytes));
+    GFDM_TRY(d_out.alloc(out_bytes(n)));
+    GFDM_TRY(d_count.alloc(sizeof(int64_t)));
+    GFDM_TRY(gfdm::upload(d_in.p, samples, (size_t)stream_len * sample_bytes(fmt), h->ctx.stream));
+    const SyncOut o = carve_out(d_out, n);
+    rc = detect_enqueue(h, d_count.as<int64_t>(), o, d_in.p, fmt, stream_len, threshold, min_distance, lead, n, d_ws.p, h->ctx.stream);
     if (rc != GFDM_HIP_OK) return rc;
-    BURST_TRY(hipMemcpyAsync(count, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    GFDM_TRY(gfdm::download(count, d_count.p, sizeof(int64_t), h->ctx.stream));
     if (n > 0) {
-        rc = fetch_out(o, n, frame_start, coarse, cfo, metric, sc_rot, h->stream);
+        rc = fetch_out(host, o, n, h->ctx.stream);
         if (rc != GFDM_HIP_OK) return rc;
     }
-    BURST_TRY(hipStreamSynchronize(h->stream));
+    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
     return GFDM_HIP_OK;
 }
 
@@ -893,7 +848,7 @@ int extractor_extract_device(int fmt, gfdm_hip_burst_extractor* h, void* out, co
 {
     int rc = extract_check(h, out, samples, stream_len, offsets, n_bursts);
     if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->ctx.device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     return extract_enqueue(h, static_cast<cf*>(out), samples, fmt, stream_len, static_cast<const int64_t*>(offsets),
                            static_cast<const float*>(scale), static_cast<const cf*>(sc_rot), n_bursts, (hipStream_t)stream);
@@ -904,25 +859,24 @@ int extractor_extract_host(int fmt, gfdm_hip_burst_extractor* h, float* out, con
 {
     int rc = extract_check(h, out, samples, stream_len, offsets, n_bursts);
     if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->ctx.device);
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const size_t n = (size_t)n_bursts, L = (size_t)h->burst_len;
     DevBuf d_s, d_args, d_out;
-    BURST_TRY(d_s.alloc((size_t)stream_len * sample_bytes(fmt)));
-    BURST_TRY(d_args.alloc(n * (sizeof(int64_t) + sizeof(float) + sizeof(cf))));
-    BURST_TRY(d_out.alloc(n * L * sizeof(cf)));
-    int64_t* d_off = static_cast<int64_t*>(d_args.p);
-    cf* d_rot = reinterpret_cast<cf*>(d_off + n);
-    float* d_scale = reinterpret_cast<float*>(d_rot + n);
-    if (stream_len) BURST_TRY(hipMemcpyAsync(d_s.p, samples, (size_t)stream_len * sample_bytes(fmt), hipMemcpyHostToDevice, h->stream));
-    BURST_TRY(hipMemcpyAsync(d_off, offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    if (sc_rot) BURST_TRY(hipMemcpyAsync(d_rot, sc_rot, n * sizeof(cf), hipMemcpyHostToDevice, h->stream));
-    if (scale) BURST_TRY(hipMemcpyAsync(d_scale, scale, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    rc = extract_enqueue(h, static_cast<cf*>(d_out.p), d_s.p, fmt, stream_len, d_off, scale ? d_scale : nullptr, sc_rot ? d_rot : nullptr,
-                         n_bursts, h->stream);
+    GFDM_TRY(d_s.alloc((size_t)stream_len * sample_bytes(fmt)));
+    GFDM_TRY(d_args.alloc(n * (sizeof(int64_t) + sizeof(float) + sizeof(cf))));
+    GFDM_TRY(d_out.alloc(n * L * sizeof(cf)));
+    int64_t* d_off = d_args.take<int64_t>(n);
+    cf* d_rot = d_args.take<cf>(n);
+    float* d_scale = d_args.take<float>(n);
+    GFDM_TRY(gfdm::upload(d_s.p, samples, (size_t)stream_len * sample_bytes(fmt), h->ctx.stream));
+    GFDM_TRY(gfdm::upload(d_off, offsets, n * sizeof(int64_t), h->ctx.stream));
+    GFDM_TRY(gfdm::upload(d_rot, sc_rot, n * sizeof(cf), h->ctx.stream));
+    GFDM_TRY(gfdm::upload(d_scale, scale, n * sizeof(float), h->ctx.stream));
+    rc = extract_enqueue(h, d_out.as<cf>(), d_s.p, fmt, stream_len, d_off, scale ? d_scale : nullptr, sc_rot ? d_rot : nullptr, n_bursts, h->ctx.stream);
     if (rc != GFDM_HIP_OK) return rc;
-    BURST_TRY(hipMemcpyAsync(out, d_out.p, n * L * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
-    BURST_TRY(hipStreamSynchronize(h->stream));
+    GFDM_TRY(gfdm::download(out, d_out.p, n * L * sizeof(cf), h->ctx.stream));
+    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
     return GFDM_HIP_OK;
 }
 
@@ -954,21 +908,21 @@ int gfdm_hip_burst_sync_create(gfdm_hip_burst_sync** out, int fft_len, int cp_le
     const double g = 1.0 / std::sqrt(e / (2 * K));
     std::vector<float> pre(4 * K);
     for (int i = 0; i < 4 * K; ++i) pre[i] = (float)(core_preamble[i] * g);
-    int rc = open_device(device);
-    if (rc != GFDM_HIP_OK) return rc;
     gfdm_hip_burst_sync* h = new (std::nothrow) gfdm_hip_burst_sync();
     if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->device = device;
     h->K = K;
     h->cp = cp_len;
     h->W = (int)window_len;
-    DeviceGuard guard(device);
-    hipError_t err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipMalloc(&h->d_preamble, pre.size() * sizeof(float));
-    if (err == hipSuccess) err = hipMemcpy(h->d_preamble, pre.data(), pre.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
+    int rc = h->ctx.open(device);
+    if (rc == GFDM_HIP_OK) {
+        DeviceGuard guard(device);
+        hipError_t err = hipMalloc(&h->d_preamble, pre.size() * sizeof(float));
+        if (err == hipSuccess) err = hipMemcpy(h->d_preamble, pre.data(), pre.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (err != hipSuccess) rc = gfdm::api_fail_hip(err, "burst_sync_create");
+    }
+    if (rc != GFDM_HIP_OK) {
         delete h;
-        return api_fail_hip(err, "burst_sync_create");
+        return rc;
     }
     *out = h;
     return GFDM_HIP_OK;
@@ -999,19 +953,15 @@ int gfdm_hip_burst_extractor_create(gfdm_hip_burst_extractor** out, int burst_le
     if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
     *out = nullptr;
     if (burst_len < 1) return api_fail(GFDM_HIP_EINVAL, "burst_len must be >= 1");
-    int rc = open_device(device);
-    if (rc != GFDM_HIP_OK) return rc;
     gfdm_hip_burst_extractor* h = new (std::nothrow) gfdm_hip_burst_extractor();
     if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->device = device;
     h->burst_len = burst_len;
     h->backoff = tag_backoff;
     h->correct = activate_cfo_correction ? 1 : 0;
-    DeviceGuard guard(device);
-    const hipError_t err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (err != hipSuccess) {
+    const int rc = h->ctx.open(device);
+    if (rc != GFDM_HIP_OK) {
         delete h;
-        return api_fail_hip(err, "burst_extractor_create");
+        return rc;
     }
     *out = h;
     return GFDM_HIP_OK;

@@ -2,7 +2,7 @@
 // dispatch to the HIP kernel families.  No CPU compute path exists here by design: if the HIP
 // device or a kernel launch is unavailable the call fails with an error code.
 #include "../../include/gfdm_hip.h"
-#include "gfdm_plan.h"
+#include "gfdm_hostcall.h"
 #include "gfdm_rowgeom.h"
 #include "gfdm_tx.h"
 #include "gfdm_hostpipe.h"
@@ -22,6 +22,7 @@
 #include <vector>
 
 using gfdm::cf;
+using gfdm::DeviceGuard;
 
 namespace {
 
@@ -39,12 +40,6 @@ int fail_hip(hipError_t e, const char* what)
     (void)hipGetLastError();          // reported here: do not leave it behind as the thread's sticky error
     return GFDM_HIP_EHIP;
 }
-
-#define HIP_TRY(expr)                                            \
-    do {                                                         \
-        hipError_t _e = (expr);                                  \
-        if (_e != hipSuccess) return fail_hip(_e, #expr);        \
-    } while (0)
 
 }  // namespace
 
@@ -106,30 +101,11 @@ struct Plan {
 
     ~Plan()
     {
-        int prev = 0;
-        bool restore = (hipGetDevice(&prev) == hipSuccess);
-        (void)hipSetDevice(device);
+        DeviceGuard guard(device);
         pipe.release();
         if (d_tables) (void)hipFree(d_tables);
         if (stream) (void)hipStreamDestroy(stream);
-        if (restore) (void)hipSetDevice(prev);
     }
-};
-
-// RAII: make the handle's device current for the duration of a call.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        // hipGetLastError() is sticky: it keeps the error of ANY earlier failed runtime call of this thread (ours or the application's) until somebody reads
-        // it, and the launchers check their launches with it -- a call must not fail on somebody else's stale error (found by tests/sanitize: an allocation
-        // failure in one constructor failed the next handle's first launch).  Every entry point that launches builds a DeviceGuard first.
-        (void)hipGetLastError();
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
 int ilog2_exact(int v)
@@ -160,9 +136,8 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
     }
     if (receiver && L < 2) return fail(GFDM_HIP_EINVAL_OVERLAP, "overlap MUST be greater or equal 2");
     if ((int64_t)M * K > (1 << 24)) return fail(GFDM_HIP_EUNSUPPORTED, "block too large");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GFDM_HIP_ENODEV, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(GFDM_HIP_ENODEV, "HIP device ordinal out of range");
+    const int dev_rc = gfdm::check_device(device);
+    if (dev_rc != GFDM_HIP_OK) return dev_rc;
     const int N = M * K;
     // (whether the block fits the kernels' LDS tiles is checked once the kernel family is known, below)
 
@@ -311,9 +286,9 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
 
     DeviceGuard guard(device);
     if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    HIP_TRY(hipMalloc(&pl.d_tables, tables.size() * sizeof(cf)));
-    HIP_TRY(hipMemcpy(pl.d_tables, tables.data(), tables.size() * sizeof(cf), hipMemcpyHostToDevice));
-    HIP_TRY(hipStreamCreateWithFlags(&pl.stream, hipStreamNonBlocking));
+    GFDM_TRY(hipMalloc(&pl.d_tables, tables.size() * sizeof(cf)));
+    GFDM_TRY(hipMemcpy(pl.d_tables, tables.data(), tables.size() * sizeof(cf), hipMemcpyHostToDevice));
+    GFDM_TRY(hipStreamCreateWithFlags(&pl.stream, hipStreamNonBlocking));
 
     gfdm::DevicePlan& dp = pl.dp;
     dp.M = M; dp.K = K; dp.L = L; dp.N = N;
@@ -525,8 +500,8 @@ int frame_io_configure(FrameIo& f, const Plan& pl, int frame_len, int cp_len, co
     std::vector<short> rank(K, (short)-1);
     for (int a = 0; a < n_map; ++a) rank[sorted[a]] = (short)a;
     DeviceGuard guard(pl.device);
-    if (!f.d_rank) HIP_TRY(hipMalloc(&f.d_rank, (size_t)K * sizeof(short)));
-    HIP_TRY(hipMemcpy(f.d_rank, rank.data(), (size_t)K * sizeof(short), hipMemcpyHostToDevice));
+    if (!f.d_rank) GFDM_TRY(hipMalloc(&f.d_rank, (size_t)K * sizeof(short)));
+    GFDM_TRY(hipMemcpy(f.d_rank, rank.data(), (size_t)K * sizeof(short), hipMemcpyHostToDevice));
     f.device = pl.device;
     f.io.in_stride = frame_len; f.io.in_offset = cp_len;
     f.io.demap = n_map > 0 ? 1 : 0; f.io.per_timeslot = per_timeslot ? 1 : 0; f.io.A = n_map;
@@ -1347,9 +1322,9 @@ int gfdm_hip_channel_estimator_create(gfdm_hip_channel_estimator** out, int time
     for (int i = 0; i < 9; ++i) e.gauss[i] /= sum;
     DeviceGuard guard(device);
     if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    HIP_TRY(hipMalloc(&c->plan.d_tables, tables.size() * sizeof(cf)));
-    HIP_TRY(hipMemcpy(c->plan.d_tables, tables.data(), tables.size() * sizeof(cf), hipMemcpyHostToDevice));
-    HIP_TRY(hipStreamCreateWithFlags(&c->plan.stream, hipStreamNonBlocking));
+    GFDM_TRY(hipMalloc(&c->plan.d_tables, tables.size() * sizeof(cf)));
+    GFDM_TRY(hipMemcpy(c->plan.d_tables, tables.data(), tables.size() * sizeof(cf), hipMemcpyHostToDevice));
+    GFDM_TRY(hipStreamCreateWithFlags(&c->plan.stream, hipStreamNonBlocking));
     e.inv0 = c->plan.d_tables;
     e.inv1 = e.inv0 + K;
     e.wK = e.inv1 + K;
@@ -1714,11 +1689,6 @@ int bursts_device(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* 
     return status_of(rx_launch(pl, ic, mode, static_cast<cf*>(out), nullptr, nullptr, n_bursts, static_cast<hipStream_t>(stream), &ep.est));
 }
 
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-};
-
 // convenience, not a pipeline: capture (in the caller's format: an sc16 capture goes up as int16) and arrays to the device, ONE launch,
 // result back (the handle's private stream)
 int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, const gfdm::IcParams& ic, int mode, float* out, const void* samples, int fmt,
@@ -1732,24 +1702,23 @@ int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c,
     if (!out || !offsets || (!samples && stream_len > 0)) return fail(GFDM_HIP_EINVAL, "NULL buffer");
     DeviceGuard guard(pl.device);
     if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t n = (size_t)n_bursts, out_bytes = n * (size_t)io.nout * sizeof(cf);
-    DevMem d_s, d_args, d_out;
-    const size_t sb = fmt == gfdm::SAMPLES_SC16 ? 2 * sizeof(int16_t) : sizeof(cf);
-    HIP_TRY(hipMalloc(&d_s.p, std::max<size_t>((size_t)stream_len * sb, sizeof(cf))));
-    HIP_TRY(hipMalloc(&d_args.p, (n + 1) * sizeof(int64_t) + n * sizeof(cf)));
-    HIP_TRY(hipMalloc(&d_out.p, out_bytes));
-    int64_t* d_off = static_cast<int64_t*>(d_args.p);
-    int64_t* d_cnt = d_off + n;
-    cf* d_rot = reinterpret_cast<cf*>(d_cnt + 1);
-    if (stream_len) HIP_TRY(hipMemcpyAsync(d_s.p, samples, (size_t)stream_len * sb, hipMemcpyHostToDevice, pl.stream));
-    HIP_TRY(hipMemcpyAsync(d_off, offsets, n * sizeof(int64_t), hipMemcpyHostToDevice, pl.stream));
-    if (count) HIP_TRY(hipMemcpyAsync(d_cnt, count, sizeof(int64_t), hipMemcpyHostToDevice, pl.stream));
-    if (sc_rot) HIP_TRY(hipMemcpyAsync(d_rot, sc_rot, n * sizeof(cf), hipMemcpyHostToDevice, pl.stream));
+    const size_t n = (size_t)n_bursts, out_bytes = n * (size_t)io.nout * sizeof(cf), cap_bytes = (size_t)stream_len * gfdm::sample_bytes(fmt);
+    gfdm::DevBuf d_s, d_args, d_out;
+    GFDM_TRY(d_s.alloc(cap_bytes));
+    GFDM_TRY(d_args.alloc((n + 1) * sizeof(int64_t) + n * sizeof(cf)));
+    GFDM_TRY(d_out.alloc(out_bytes));
+    int64_t* d_off = d_args.take<int64_t>(n);
+    int64_t* d_cnt = d_args.take<int64_t>(1);
+    cf* d_rot = d_args.take<cf>(n);
+    GFDM_TRY(gfdm::upload(d_s.p, samples, cap_bytes, pl.stream));
+    GFDM_TRY(gfdm::upload(d_off, offsets, n * sizeof(int64_t), pl.stream));
+    GFDM_TRY(gfdm::upload(d_cnt, count, sizeof(int64_t), pl.stream));
+    GFDM_TRY(gfdm::upload(d_rot, sc_rot, n * sizeof(cf), pl.stream));
     rc = bursts_device(pl, f, c, ic, mode, d_out.p, d_s.p, fmt, stream_len, d_off, sc_rot ? d_rot : nullptr, count ? d_cnt : nullptr, backoff, preamble_offset,
                        cfo_correction, noutput_size, n_bursts, pl.stream);
     if (rc != GFDM_HIP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, pl.stream));
-    HIP_TRY(hipStreamSynchronize(pl.stream));
+    GFDM_TRY(gfdm::download(out, d_out.p, out_bytes, pl.stream));
+    GFDM_TRY(hipStreamSynchronize(pl.stream));
     return GFDM_HIP_OK;
 }
 

@@ -1,8 +1,7 @@
 // Host-buffer batch path (gfdm_hostpipe.h): operand classification, chunked bounce through pinned staging sets, completion tickets,
 // the copy-thread pool.  No GFDM arithmetic here and no CPU compute path: the kernels of a call are enqueued by the caller's `launch`.
 #include "gfdm_hostpipe.h"
-#include "../../include/gfdm_hip.h"
-#include "gfdm_plan.h"
+#include "gfdm_hostcall.h"
 
 #include <atomic>
 #include <chrono>

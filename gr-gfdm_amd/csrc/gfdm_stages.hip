@@ -12,7 +12,7 @@
 //   remove   out[N]          <- in[cp + N + cs]              reads 8 N + writes 8 N
 // Restated from gr-gfdm: lib/resource_mapper_kernel_cc.cc:30-163, lib/add_cyclic_prefix_cc.cc:30-104.
 #include "../../include/gfdm_hip.h"
-#include "gfdm_plan.h"
+#include "gfdm_hostcall.h"
 #include "gfdm_dft.h"
 #include "gfdm_hostpipe.h"
 
@@ -25,54 +25,20 @@
 
 using gfdm::cf;
 using gfdm::api_fail;
-using gfdm::api_fail_hip;
+using gfdm::DeviceGuard;
 
 namespace {
 
-#define STAGE_TRY(expr)                                          \
-    do {                                                         \
-        hipError_t _e = (expr);                                  \
-        if (_e != hipSuccess) return api_fail_hip(_e, #expr);    \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        // hipGetLastError() is sticky: it keeps the error of ANY earlier failed runtime call of this thread (ours or the application's) until somebody reads
-        // it, and the launchers check their launches with it -- a call must not fail on somebody else's stale error (found by tests/sanitize: an allocation
-        // failure in one constructor failed the next handle's first launch).  Every entry point that launches builds a DeviceGuard first.
-        (void)hipGetLastError();
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// device, private stream and the host-buffer path (gfdm_hostpipe.h) of the *_host entry points
-struct StageCtx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+// a handle's device and private stream (DeviceCtx) plus the host-buffer path (gfdm_hostpipe.h) of the *_host entry points and the handle's tables
+struct StageCtx : gfdm::DeviceCtx {
     gfdm::HostPipe pipe;
     void* d_tables = nullptr;
 
-    int open(int dev)
-    {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return api_fail(GFDM_HIP_ENODEV, "no HIP device available (this library has no CPU path)");
-        if (dev < 0 || dev >= count) return api_fail(GFDM_HIP_ENODEV, "HIP device ordinal out of range");
-        device = dev;
-        DeviceGuard guard(dev);
-        if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-        STAGE_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        return GFDM_HIP_OK;
-    }
     int upload(const void* host, size_t bytes)
     {
         DeviceGuard guard(device);
-        STAGE_TRY(hipMalloc(&d_tables, bytes > 0 ? bytes : 16));
-        if (bytes) STAGE_TRY(hipMemcpy(d_tables, host, bytes, hipMemcpyHostToDevice));
+        GFDM_TRY(hipMalloc(&d_tables, bytes > 0 ? bytes : 16));
+        if (bytes) GFDM_TRY(hipMemcpy(d_tables, host, bytes, hipMemcpyHostToDevice));
         return GFDM_HIP_OK;
     }
     ~StageCtx()
@@ -80,7 +46,6 @@ struct StageCtx {
         DeviceGuard guard(device);
         pipe.release();
         if (d_tables) (void)hipFree(d_tables);
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -323,7 +288,7 @@ int gfdm_hip_resource_mapper_map_device(gfdm_hip_resource_mapper* m, void* out, 
     else
         hipLaunchKernelGGL(k_map_to_resources, grid_for(N, nblocks), dim3(kThreads), 0, (hipStream_t)stream, (cf*)out, (const cf*)in, m->d_rank, m->M, N,
                            m->A, m->per_timeslot, ninput_size, nblocks);
-    STAGE_TRY(hipGetLastError());
+    GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
 
@@ -344,7 +309,7 @@ int gfdm_hip_resource_mapper_demap_device(gfdm_hip_resource_mapper* m, void* out
     else
         hipLaunchKernelGGL(k_demap_from_resources, grid_for(noutput_size, nblocks), dim3(kThreads), 0, (hipStream_t)stream, (cf*)out, (const cf*)in,
                            m->d_smap, m->M, m->K * m->M, m->A, m->per_timeslot, noutput_size, nblocks);
-    STAGE_TRY(hipGetLastError());
+    GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
 
@@ -424,7 +389,7 @@ int gfdm_hip_cyclic_prefixer_add_device(gfdm_hip_cyclic_prefixer* c, void* out, 
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     hipLaunchKernelGGL(k_add_cyclic_prefix, grid_for(c->N + c->cp + c->cs, nblocks), dim3(kThreads), 0, (hipStream_t)stream, (cf*)out, (const cf*)in,
                        c->d_front, c->d_back, c->N, c->cp, c->cs, c->ramp, cyclic_shift, nblocks);
-    STAGE_TRY(hipGetLastError());
+    GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
 
@@ -437,7 +402,7 @@ int gfdm_hip_cyclic_prefixer_remove_device(gfdm_hip_cyclic_prefixer* c, void* ou
     if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     hipLaunchKernelGGL(k_remove_cyclic_prefix, grid_for(c->N, nblocks), dim3(kThreads), 0, (hipStream_t)stream, (cf*)out, (const cf*)in, c->N,
                        c->N + c->cp + c->cs, c->cp, nblocks);
-    STAGE_TRY(hipGetLastError());
+    GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
 

@@ -274,3 +274,40 @@ def test_extract_burst_len_one():
                          torch.tensor(rot, device="cuda:0"))
         torch.cuda.synchronize()
         assert np.array_equal(dev.cpu().numpy(), got)
+
+
+@pytest.mark.parametrize("sc16", [False, True])
+def test_auto_correlate_host_with_one_output(sc16):
+    """the raw C call with ac or ic left out (the Python wrapper always passes both): the output that is asked for equals the one of the
+    both-outputs call bit for bit, nothing is written behind it (8-byte canary), and a call without any output is EINVAL"""
+    import gfdm_amd
+    K, cp, W, first, stride, nw = 4, 2, 24, 3, 5, 4
+    P = W - 2 * K
+    rng = np.random.default_rng(77)
+    s = (rng.standard_normal(64) + 1j * rng.standard_normal(64)).astype(np.complex64)
+    core = (rng.standard_normal(2 * K) + 1j * rng.standard_normal(2 * K)).astype(np.complex64)
+    if sc16:
+        s = gfdm_amd.to_sc16(s)
+    s = np.ascontiguousarray(s)
+    sync = gfdm_amd.BurstSync(K, cp, core, W)
+    fn = getattr(gfdm_amd.capi.lib(), "gfdm_hip_burst_sync_auto_correlate%s_host" % ("_sc16" if sc16 else ""))
+    CANARY = 0x5A
+
+    def call(want_ac, want_ic):
+        ac = np.full(nw * P * 8 + 8, CANARY, np.uint8)
+        ic = np.full(nw * P * 4 + 8, CANARY, np.uint8)
+        rc = fn(sync._h, ac.ctypes.data if want_ac else None, ic.ctypes.data if want_ic else None, s.ctypes.data, 64, first, stride, nw)
+        assert np.all(ac[-8:] == CANARY) and np.all(ic[-8:] == CANARY)
+        return rc, ac[:-8], ic[:-8]
+
+    rc, ac, ic = call(True, True)
+    assert rc == 0
+    assert np.any(ac != CANARY) and np.any(ic != CANARY)
+    wac, wic = sync.auto_correlate(s, first=first, stride=stride, n_windows=nw)          # ... and the wrapper's view of the same call
+    assert np.array_equal(ac.view(np.complex64).reshape(nw, P), wac) and np.array_equal(ic.view(np.float32).reshape(nw, P), wic)
+    rc, ac1, ic1 = call(True, False)
+    assert rc == 0 and np.array_equal(ac1, ac) and np.all(ic1 == CANARY)
+    rc, ac2, ic2 = call(False, True)
+    assert rc == 0 and np.array_equal(ic2, ic) and np.all(ac2 == CANARY)
+    rc, ac3, ic3 = call(False, False)
+    assert rc == gfdm_amd.capi.EINVAL and np.all(ac3 == CANARY) and np.all(ic3 == CANARY)
