@@ -44,7 +44,7 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64, cp, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_float
+    vp, i32, i64, cp, f32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_float, ctypes.c_double
     sig = {
         "gfdm_hip_strerror": (cp, [i32]),
         "gfdm_hip_last_error": (cp, []),
@@ -210,6 +210,22 @@ def lib():
         "gfdm_hip_burst_sync_detect_sc16_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64, vp, vp]),
         "gfdm_hip_burst_extractor_extract_sc16_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i64]),
         "gfdm_hip_burst_extractor_extract_sc16_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i64, vp]),
+        "gfdm_hip_burst_shaper_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, f32, f32, i32]),
+        "gfdm_hip_burst_shaper_destroy": (i32, [vp]),
+        "gfdm_hip_burst_shaper_frame_len": (i32, [vp]),
+        "gfdm_hip_burst_shaper_pre_padding": (i32, [vp]),
+        "gfdm_hip_burst_shaper_post_padding": (i32, [vp]),
+        "gfdm_hip_burst_shaper_scale": (i32, [vp, vp]),
+        "gfdm_hip_burst_shaper_check": (i32, [i32, i32, i32, f64, i64, i64]),
+        "gfdm_hip_burst_shaper_workspace_bytes": (i64, [vp, i64, i64]),
+        "gfdm_hip_burst_shaper_shape_host": (i32, [vp, vp, vp, i64]),
+        "gfdm_hip_burst_shaper_shape_device": (i32, [vp, vp, vp, i64, vp, vp]),
+        "gfdm_hip_burst_shaper_shape_sc16_host": (i32, [vp, vp, vp, i64, f64]),
+        "gfdm_hip_burst_shaper_shape_sc16_device": (i32, [vp, vp, vp, i64, f64, vp, vp]),
+        "gfdm_hip_burst_shaper_place_host": (i32, [vp, vp, i64, vp, vp, vp, i64]),
+        "gfdm_hip_burst_shaper_place_device": (i32, [vp, vp, i64, vp, vp, vp, i64, vp, vp]),
+        "gfdm_hip_burst_shaper_place_sc16_host": (i32, [vp, vp, i64, vp, vp, vp, i64, f64]),
+        "gfdm_hip_burst_shaper_place_sc16_device": (i32, [vp, vp, i64, vp, vp, vp, i64, f64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == the library does not export a declared symbol
@@ -1354,3 +1370,190 @@ class BurstExtractor(_Kernel):
         _check(getattr(L, "gfdm_hip_burst_extractor_extract%s_host" % fmt)(self._h, out.ctypes.data, sptr, slen, off.ctypes.data,
                                                                           None if sc is None else sc.ctypes.data, None if rot is None else rot.ctypes.data, n))
         return out
+
+
+class BurstShaper(_Kernel):
+    """Scaled frames in a TX stream (contract in include/gfdm_hip.h, gfdm_hip_burst_shaper): shape() is gr-gfdm's short_burst_shaper
+    (lib/short_burst_shaper_impl.cc:161-182) on a batch of frames, place() puts the frames at given sample positions of a stream of
+    out_len samples and writes the silence between them.  numpy frames -> numpy stream (host path); a torch complex64 device tensor ->
+    a tensor on its device (device path, current stream unless given).  sc16=True writes int16 I/Q of shape (n, 2) -- what the burst
+    calls read as a capture -- truncated and saturated; with `peak` the largest component of the scaled frames of the call goes to
+    `peak` (to_sc16's rule, found on the device), without it the scale alone carries the gain.  `frames` may be a list of per-port
+    arrays as Transmitter.transmit returns them: the result is then a list, one call (and one normalisation) per port."""
+    _destroy = "gfdm_hip_burst_shaper_destroy"
+
+    def __init__(self, frame_len, pre_padding=0, post_padding=0, scale=1.0, device=0):
+        h = ctypes.c_void_p()
+        sc = complex(scale)
+        _check(lib().gfdm_hip_burst_shaper_create(ctypes.byref(h), int(frame_len), int(pre_padding), int(post_padding), sc.real, sc.imag, device))
+        self._h = h
+        self._dev = int(device)
+
+    def frame_len(self):
+        return lib().gfdm_hip_burst_shaper_frame_len(self._h)
+
+    def pre_padding(self):
+        return lib().gfdm_hip_burst_shaper_pre_padding(self._h)
+
+    def post_padding(self):
+        return lib().gfdm_hip_burst_shaper_post_padding(self._h)
+
+    def slot_len(self):
+        """samples per burst of shape(): pre_padding + frame_len + post_padding"""
+        return self.pre_padding() + self.frame_len() + self.post_padding()
+
+    def scale(self):
+        v = (ctypes.c_float * 2)()
+        _check(lib().gfdm_hip_burst_shaper_scale(self._h, v))
+        return complex(v[0], v[1])
+
+    def workspace_bytes(self, n_bursts, out_len):
+        """bytes of device scratch a device call on n_bursts frames and out_len samples needs (used by normalised sc16 output only)"""
+        n = lib().gfdm_hip_burst_shaper_workspace_bytes(self._h, int(n_bursts), int(out_len))
+        if n < 0:
+            _check(n)
+        return n
+
+    @staticmethod
+    def _peak(sc16, peak):
+        if peak is None:
+            return 0.0
+        if not sc16:
+            raise ValueError("peak normalises sc16 output: pass sc16=True (complex64 output is scaled by `scale` alone)")
+        if not 0 < peak <= 32767:
+            raise ValueError("peak must lie in (0, 32767]")
+        return float(peak)
+
+    @staticmethod
+    def _kinds(frames, out, sc16):
+        """what can be said of frames and out without the handle (kind, dtype, layout): raised before the library is asked"""
+        if _is_tensor(frames):
+            import torch
+            if frames.dtype != torch.complex64 or not frames.is_cuda or not frames.is_contiguous():
+                raise TypeError("frames must be a contiguous complex64 CUDA/HIP tensor")
+        else:
+            a = np.asarray(frames)
+            if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.complexfloating)):
+                raise TypeError("frames must be complex samples, not %s" % a.dtype)
+            frames = _c64(a).ravel()
+        if out is not None:
+            if _is_tensor(out) != _is_tensor(frames):
+                raise TypeError("out must be a %s, as frames is" % ("CUDA/HIP tensor" if _is_tensor(frames) else "numpy array"))
+            if not _is_tensor(out) and not isinstance(out, np.ndarray):
+                raise TypeError("out must be a numpy array")
+            have = str(out.dtype).replace("torch.", "")
+            if have != ("int16" if sc16 else "complex64"):
+                raise TypeError("out must be %s, not %s" % ("int16 I/Q (sc16)" if sc16 else "complex64", have))
+            contiguous = out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous
+            if not contiguous:
+                raise TypeError("out must be contiguous")
+            if sc16:
+                _sc16_pairs(out.shape, "out")
+        return frames
+
+    def _frames(self, frames):
+        """n_bursts of the frames of one port: any shape whose size is a multiple of frame_len"""
+        F = self.frame_len()
+        size = frames.numel() if _is_tensor(frames) else frames.size
+        if size % F:
+            raise RuntimeError("frames size(%d) MUST be a multiple of frame_len(%d)!" % (size, F))
+        return size // F
+
+    def _out(self, out, n, sc16, like):
+        """the output array of n samples -- `out` (checked by _kinds), or a new one of `like`'s kind -- and its pointer"""
+        if out is None:
+            if _is_tensor(like):
+                import torch
+                out = torch.empty((n, 2) if sc16 else (n,), dtype=torch.int16 if sc16 else torch.complex64, device=like.device)
+            else:
+                out = np.empty((n, 2) if sc16 else (n,), np.int16 if sc16 else np.complex64)
+        have = _sc16_pairs(out.shape, "out") if sc16 else (out.numel() if _is_tensor(out) else out.size)
+        if have != n:
+            raise RuntimeError("out holds %d samples, expected %d" % (have, n))
+        if _is_tensor(out):
+            if out.device.index != self._dev:
+                raise RuntimeError("out lives on GPU %d, the handle on GPU %d" % (out.device.index, self._dev))
+            return out, out.data_ptr()
+        return out, out.ctypes.data
+
+    def _workspace(self, ws, like, n, out_len, pk):
+        """pointer of the device scratch of a normalised call (`ws`: a uint8 device tensor of workspace_bytes(), or None for a new one)"""
+        if not pk:
+            return None, None
+        import torch
+        need = self.workspace_bytes(n, out_len)
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=like.device)
+        elif not _is_tensor(ws) or ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < need or ws.device.index != self._dev:
+            raise TypeError("workspace must be a contiguous uint8 CUDA/HIP tensor of at least %d bytes on GPU %d" % (need, self._dev))
+        return ws, ws.data_ptr()
+
+    def shape(self, frames, sc16=False, peak=None, out=None, stream=None, workspace=None):
+        """n_bursts * slot_len() samples: every frame scaled, behind pre_padding and in front of post_padding zeros.  workspace (device path,
+        normalised sc16 only): a uint8 tensor of workspace_bytes() to use instead of a new one; afterwards its first two floats are the gain
+        and the largest component found."""
+        if isinstance(frames, (list, tuple)):
+            if out is not None and len(out) != len(frames):
+                raise ValueError("out must hold one array per port")
+            return [self.shape(f, sc16, peak, None if out is None else out[p], stream, workspace) for p, f in enumerate(frames)]
+        pk = self._peak(sc16, peak)
+        frames = self._kinds(frames, out, sc16)
+        n = self._frames(frames)
+        L = lib()
+        _check(L.gfdm_hip_burst_shaper_check(self.frame_len(), self.pre_padding(), self.post_padding(), pk, n, n * self.slot_len()))
+        res, optr = self._out(out, n * self.slot_len(), sc16, frames)
+        if _is_tensor(frames):
+            fptr = self._dp(frames, frames.numel(), "frames")
+            ws, wptr = self._workspace(workspace, frames, n, n * self.slot_len(), pk)
+            if sc16:
+                _check(L.gfdm_hip_burst_shaper_shape_sc16_device(self._h, optr, fptr, n, pk, wptr, self._sp(stream)))
+            else:
+                _check(L.gfdm_hip_burst_shaper_shape_device(self._h, optr, fptr, n, wptr, self._sp(stream)))
+            return res
+        if sc16:
+            _check(L.gfdm_hip_burst_shaper_shape_sc16_host(self._h, optr, frames.ctypes.data, n, pk))
+        else:
+            _check(L.gfdm_hip_burst_shaper_shape_host(self._h, optr, frames.ctypes.data, n))
+        return res
+
+    def place(self, frames, starts, out_len, count=None, sc16=False, peak=None, out=None, stream=None, workspace=None):
+        """out_len samples: frame b from sample starts[b] on (starts ascending, int64; a device tensor when frames is one), zeros
+        elsewhere.  count (an int, or on the device path a one-element int64 tensor such as detect's) limits the call to the first
+        count frames; it is clamped to [0, n_bursts].  workspace: as in shape()."""
+        if isinstance(frames, (list, tuple)):
+            if out is not None and len(out) != len(frames):
+                raise ValueError("out must hold one array per port")
+            return [self.place(f, starts, out_len, count, sc16, peak, None if out is None else out[p], stream, workspace) for p, f in enumerate(frames)]
+        pk = self._peak(sc16, peak)
+        frames = self._kinds(frames, out, sc16)
+        if _is_tensor(frames) != _is_tensor(starts):
+            raise TypeError("starts must be %s, as frames is" % ("a torch.int64 CUDA/HIP tensor" if _is_tensor(frames) else "an integer array"))
+        n = self._frames(frames)
+        out_len = int(out_len)
+        L = lib()
+        _check(L.gfdm_hip_burst_shaper_check(self.frame_len(), self.pre_padding(), self.post_padding(), pk, n, out_len))
+        if _is_tensor(frames):
+            import torch
+            sptr = _dev_arg(starts, torch.int64, n, "starts", self._dev)
+            if count is not None and not _is_tensor(count):
+                count = torch.full((1,), int(count), dtype=torch.int64, device=frames.device)
+            cptr = None if count is None else _dev_arg(count, torch.int64, 1, "count", self._dev)
+            res, optr = self._out(out, out_len, sc16, frames)
+            fptr = self._dp(frames, frames.numel(), "frames")
+            ws, wptr = self._workspace(workspace, frames, n, out_len, pk)
+            if sc16:
+                _check(L.gfdm_hip_burst_shaper_place_sc16_device(self._h, optr, out_len, fptr, sptr, cptr, n, pk, wptr, self._sp(stream)))
+            else:
+                _check(L.gfdm_hip_burst_shaper_place_device(self._h, optr, out_len, fptr, sptr, cptr, n, wptr, self._sp(stream)))
+            return res
+        st = np.ascontiguousarray(starts, dtype=np.int64).ravel()
+        if st.size != n:
+            raise RuntimeError("starts has %d elements, expected %d" % (st.size, n))
+        cnt = None if count is None else np.array([int(count)], np.int64)
+        res, optr = self._out(out, out_len, sc16, frames)
+        cptr = None if cnt is None else cnt.ctypes.data
+        if sc16:
+            _check(L.gfdm_hip_burst_shaper_place_sc16_host(self._h, optr, out_len, frames.ctypes.data, st.ctypes.data, cptr, n, pk))
+        else:
+            _check(L.gfdm_hip_burst_shaper_place_host(self._h, optr, out_len, frames.ctypes.data, st.ctypes.data, cptr, n))
+        return res

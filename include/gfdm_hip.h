@@ -598,6 +598,73 @@ int gfdm_hip_advanced_receiver_work_bursts_sc16_device(gfdm_hip_advanced_receive
                                                        const void* offsets, const void* sc_rot, const void* count, int backoff, int preamble_offset,
                                                        int cfo_correction, int noutput_size, int64_t n_bursts, void* stream);
 
+/* ---- gfdm_hip_burst_shaper: scaled frames in a TX stream, complex64 or sc16 ---------------------------------------------------------
+ * The stage between the transmitter's dense [n_bursts][frame_len] array and what a radio or a capture file takes: silence around each
+ * burst, the amplitude scale, frames at given sample positions of a continuous stream, conversion to int16 I/Q.  `shape` is gr-gfdm's
+ * short_burst_shaper (lib/short_burst_shaper_impl.cc:161-182: zero pre-padding, scale * in, zero post-padding), batched; `place` is the
+ * dual of find_frame_start_at / detect.  One handle serves one port; the block's timed commands and tx_time tags are not here.
+ * With F = frame_len and the complex `scale` of create:  y_b[n] = scale * frame_b[n], one fp32 complex product
+ *     (re = fma(sr, xr, -(si xi)), im = fma(sr, xi, si xr): exact products for a real scale, within 4 * 2^-24 |scale| |x| otherwise).
+ * shape: n_bursts frames -> n_bursts * S samples, S = pre_padding + F + post_padding:
+ *     out[b S + n] = 0 for n < pre_padding,  y_b[n - pre_padding] for the next F samples,  0 for the rest of the slot.
+ * place: the stream has out_len samples and EVERY one of them is written exactly once.  starts is int64[n_bursts], ascending (a device
+ *   array in the device flavour); count an optional int64 (on the device in the device flavour; NULL = n_bursts -- detect's count as it
+ *   is).  With n_live = clamp(*count, 0, n_bursts) and starts[n_live] := out_len:
+ *     out[i] = y_b[i - starts[b]]   where b is the live burst with starts[b] <= i < starts[b + 1], if i - starts[b] < F
+ *     out[i] = 0                    everywhere else (before the first start, behind a frame, all of it when n_live = 0).
+ *   So a frame that runs into its successor or past out_len is cut there, the part of a frame before sample 0 is dropped, and the frames
+ *   from n_live on never appear.  The host flavour refuses what it can see with GFDM_HIP_EINVAL, over the live bursts: starts[0] < 0,
+ *   starts that do not ascend, starts[b] + F > starts[b + 1], a last frame running past out_len.  The device flavour cannot check the
+ *   starts; the cutting rule keeps it memory-safe (as the clamped window starts do in find_frame_start_at): for starts that do not
+ *   ascend the CONTENT of out is unspecified (each sample is 0 or some in-range sample of some live frame), but even then all of
+ *   out[0, out_len) and nothing outside it is written, and nothing outside frames[0, n_live * F) is read.
+ * Output format: each call has a complex64 flavour and a *_sc16_* twin that writes interleaved int16 I, Q (the format the *_sc16_*
+ *   calls above read).  The sc16 value is q(y * g) per component, the product in fp32; q truncates toward zero and saturates to
+ *   [-32768, 32767], NaN gives 0.  peak == 0: g = 1, the caller's scale carries the gain.  peak in (0, 32767]: normalised as pygfdm's
+ *   convert_to_sc16 does: top = the largest |re| or |im| of y over the live frames of THIS call (whole frames, cut or not), found on
+ *   the device, g = (float)((double)peak / (double)top), g = 1 for top == 0.  Each call, and so each port, normalises on its own:
+ *   ports that must share one gain take peak = 0 and a common scale.  Non-finite input under normalisation: the values are
+ *   unspecified, the call still returns 0.  Against to_sc16 (float64 throughout) a component differs by at most 1 LSB.
+ * *_device: out, frames, starts and count are device arrays; out needs the alignment of one sample (8 bytes, sc16: 4 bytes) and no
+ *   more -- a stream may start at an odd sample of a larger buffer.  The call neither allocates nor synchronises and is
+ *   hipGraph-capturable.  Its scratch (the partial maxima and the gain of a normalised call) is the caller's `workspace` of
+ *   workspace_bytes(s, n_bursts, out_len) bytes: device memory, 16-byte aligned, content not preserved between calls and never
+ *   assumed; it may be NULL for complex64 and for peak == 0.  When a normalised call has run, its first two floats are g and top (for
+ *   the caller's records; nothing reads them back).  No memset fills the gaps: the kernel that writes the frames writes the
+ *   zeros.  The stream is written in 16-byte stores aligned in memory whatever pre_padding and the starts are (the first and last
+ *   samples of a stream that is itself unaligned go out one by one); byte offsets are 64-bit.
+ * *_host: a convenience, not a pipeline: uploads the frames (and starts, count), runs the device call, downloads the stream.
+ * GFDM_HIP_EINVAL from check (the argument table alone, without a handle or a device) and from every call: frame_len < 1; negative
+ *   paddings; peak outside {0} and (0, 32767]; n_bursts < 0; out_len < 0; byte sizes (8 n_bursts frame_len, 8 out_len, for shape
+ *   8 n_bursts S) that overflow int64.  Also: a NULL buffer that the call would touch.  out_len == 0 returns GFDM_HIP_OK without a
+ *   launch; n_bursts == 0 with out_len > 0 writes out_len zeros.
+ * Tested range (against a numpy restatement of the above: complex64 and fixed-gain sc16 equal, normalised sc16 equal with top compared
+ *   exactly): frame_len 1, 3, 5, 255, 256, 257, 721, 738; paddings 0, 1, 5; 1, 7, 5000 (of 3 samples) and 32768 + 7 (of 5 samples)
+ *   bursts per call (bursts are not a grid dimension: a workgroup takes 16 KiB of the stream, whatever lies there); output buffers at
+ *   every alignment of one sample.  Streams beyond 2^31 bytes are computed for (64-bit offsets throughout) but not part of the tests. */
+typedef struct gfdm_hip_burst_shaper gfdm_hip_burst_shaper;
+int gfdm_hip_burst_shaper_create(gfdm_hip_burst_shaper** out, int frame_len, int pre_padding, int post_padding, float scale_re, float scale_im, int device);
+int gfdm_hip_burst_shaper_destroy(gfdm_hip_burst_shaper* s);
+int gfdm_hip_burst_shaper_frame_len(const gfdm_hip_burst_shaper* s);
+int gfdm_hip_burst_shaper_pre_padding(const gfdm_hip_burst_shaper* s);
+int gfdm_hip_burst_shaper_post_padding(const gfdm_hip_burst_shaper* s);
+int gfdm_hip_burst_shaper_scale(const gfdm_hip_burst_shaper* s, float* scale);          /* scale[0] = re, scale[1] = im */
+int gfdm_hip_burst_shaper_check(int frame_len, int pre_padding, int post_padding, double peak, int64_t n_bursts, int64_t out_len);
+int64_t gfdm_hip_burst_shaper_workspace_bytes(const gfdm_hip_burst_shaper* s, int64_t n_bursts, int64_t out_len);
+int gfdm_hip_burst_shaper_shape_host(gfdm_hip_burst_shaper* s, float* out, const float* frames, int64_t n_bursts);
+int gfdm_hip_burst_shaper_shape_device(gfdm_hip_burst_shaper* s, void* out, const void* frames, int64_t n_bursts, void* workspace, void* stream);
+int gfdm_hip_burst_shaper_shape_sc16_host(gfdm_hip_burst_shaper* s, int16_t* out, const float* frames, int64_t n_bursts, double peak);
+int gfdm_hip_burst_shaper_shape_sc16_device(gfdm_hip_burst_shaper* s, void* out, const void* frames, int64_t n_bursts, double peak, void* workspace,
+                                            void* stream);
+int gfdm_hip_burst_shaper_place_host(gfdm_hip_burst_shaper* s, float* out, int64_t out_len, const float* frames, const int64_t* starts,
+                                     const int64_t* count, int64_t n_bursts);
+int gfdm_hip_burst_shaper_place_device(gfdm_hip_burst_shaper* s, void* out, int64_t out_len, const void* frames, const void* starts, const void* count,
+                                       int64_t n_bursts, void* workspace, void* stream);
+int gfdm_hip_burst_shaper_place_sc16_host(gfdm_hip_burst_shaper* s, int16_t* out, int64_t out_len, const float* frames, const int64_t* starts,
+                                          const int64_t* count, int64_t n_bursts, double peak);
+int gfdm_hip_burst_shaper_place_sc16_device(gfdm_hip_burst_shaper* s, void* out, int64_t out_len, const void* frames, const void* starts,
+                                            const void* count, int64_t n_bursts, double peak, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
