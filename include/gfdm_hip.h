@@ -193,10 +193,30 @@ int gfdm_hip_receiver_ic_filter_taps(const gfdm_hip_receiver* r, float* out);   
 const char* gfdm_hip_receiver_kernel_name(const gfdm_hip_receiver* r);
 
 /* generic_work (f_eq == NULL, .cc:322-326) / generic_work_equalize (f_eq != NULL, .cc:328-334);
- * f_eq holds one block_size vector PER BLOCK (lib/advanced_receiver_sb_cc_impl.cc:98-104) */
+ * f_eq holds one block_size vector PER BLOCK (lib/advanced_receiver_sb_cc_impl.cc:98-104)
+ *
+ * Zero, infinite and non-finite data (every receiver entry point: *_demodulate_*, *_fft_filter_downsample_*, the advanced receiver's *_work_*,
+ * the *_frames_*, *_estimated_* and *_bursts_* forms, and the modulator / transmitter likewise).  A non-finite result is confined to the block,
+ * frame or burst whose input, equaliser or preamble caused it: every other block of the launch is bit-identical to the launch without it.  The
+ * equaliser is the reference's division X / f_eq (volk_32fc_x2_divide_32fc, lib/receiver_kernel_cc.cc:315-316) computed as
+ * X conj(e) / |e|^2, and what it yields spreads exactly as far as the arithmetic carries it: a bin at subcarrier row j0, column m0 of a block
+ * reaches column m0 of the rows k in [j0 - overlap + 1 + overlap/2, j0 + overlap/2] mod subcarriers of fft_equalize_filter_downsample and these
+ * rows in full of generic_work_equalize; the advanced receiver decides a NaN like a zero (a finite constellation point), so the same rows stay
+ * non-finite, the rows within ic_iter of them may differ from the unpoisoned result and stay finite, and all other rows are bit-identical.
+ *   f_eq bin = 0 or NaN:  NaN in the elements named above, as numpy and C99 division give non-finite values there.
+ *   f_eq bin infinite:    DEVIATION: NaN in the same elements, on every kernel family (row-lane compiled and run-time instantiated, generic
+ *                         in LDS and in global scratch, with vector-ALU and matrix-core transforms and cancellation rounds, Rader), for
+ *                         +inf as for inf + inf j -- |e|^2 is inf and inf / inf is NaN -- where numpy and C99 give the quotient 0 for a
+ *                         finite X over a real +inf (observed by tests/test_poison_gpu.py::test_equaliser_bin_stays_in_its_rows_and_block).
+ *   One NaN or infinite input sample makes its whole block non-finite, one NaN symbol its whole modulated block (the transmitter's frame
+ *   behind the preamble); an all-zero received preamble (estimate 0) or one NaN preamble sample makes its whole block non-finite in the
+ *   *_estimated_* and *_bursts_* calls, and estimate_frame returns zeros resp. a wholly non-finite estimate for that frame alone.
+ *   Samples outside the part a call is documented to read -- a frame outside [cp_len, cp_len + block_size), the gap between two preambles
+ *   preamble_stride apart, the capture outside a burst's two windows -- are not read: NaN there changes no bit of the output, and with a
+ *   truncating noutput_size nothing is written outside [b noutput_size, (b + 1) noutput_size) of `out` (tests/test_poison_gpu.py). */
 int gfdm_hip_receiver_demodulate_host(gfdm_hip_receiver* r, float* out, const float* in, const float* f_eq, int64_t nblocks);
 int gfdm_hip_receiver_demodulate_device(gfdm_hip_receiver* r, void* out, const void* in, const void* f_eq, int64_t nblocks, void* stream);
-/* fft_filter_downsample (.cc:301-307) / fft_equalize_filter_downsample (.cc:309-320) */
+/* fft_filter_downsample (.cc:301-307) / fft_equalize_filter_downsample (.cc:309-320); zero, infinite and NaN f_eq bins: see above */
 int gfdm_hip_receiver_fft_filter_downsample_host(gfdm_hip_receiver* r, float* out, const float* in, const float* f_eq, int64_t nblocks);
 int gfdm_hip_receiver_fft_filter_downsample_device(gfdm_hip_receiver* r, void* out, const void* in, const void* f_eq, int64_t nblocks, void* stream);
 /* transform_subcarriers_to_td (.cc:211-225) */
@@ -227,7 +247,8 @@ const char* gfdm_hip_advanced_receiver_kernel_name(const gfdm_hip_advanced_recei
  * matrix-core rounds -- only for GNU Radio's unit constellations (every component within 6 * FLT_EPSILON relative of (+-1 +-j)/sqrt 2 resp. -1, +1 -- this admits gr::digital's 0.707107 literal -- in
  * that order); any other points, also when created with an explicit QPSK / BPSK, are decided by NEAREST over the points as given */
 int gfdm_hip_advanced_receiver_decision(const gfdm_hip_advanced_receiver* a);
-/* generic_work (f_eq == NULL, .cc:93-98) / generic_work_equalize (f_eq != NULL, .cc:100-107) */
+/* generic_work (f_eq == NULL, .cc:93-98) / generic_work_equalize (f_eq != NULL, .cc:100-107); zero, infinite and NaN f_eq bins, samples: as
+ * described at gfdm_hip_receiver_demodulate_* (the affected rows stay non-finite through the cancellation rounds, a halo of ic_iter rows may change) */
 int gfdm_hip_advanced_receiver_work_host(gfdm_hip_advanced_receiver* a, float* out, const float* in, const float* f_eq, int64_t nblocks);
 int gfdm_hip_advanced_receiver_work_device(gfdm_hip_advanced_receiver* a, void* out, const void* in, const void* f_eq, int64_t nblocks, void* stream);
 
