@@ -16,7 +16,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -59,6 +58,52 @@ std::atomic<int> g_jit{ 3 };
 std::atomic<int> g_ic_mfma{ 1 };
 std::atomic<int> g_dft_mfma{ 1 };
 
+// One part of a shape's run-time instantiated kernels, as one handle sees it.  Three of them decide which kernels a call launches (Plan below):
+// the family itself, the preamble-equalised receive kernels, the gather-load receive kernels of demodulate_bursts.  The state only moves
+// forward; a handle is used by ONE thread at a time (include/gfdm_hip.h, "Threading"), so it is plain per-handle data around the flag the
+// background build reports through.
+class JitPart {
+public:
+    enum State { NOT_REQUESTED, COMPILING, READY, FAILED };
+
+    // where the part stands now: picks up a background build that has finished, unless a *_host call holds the answer (freeze)
+    State poll()
+    {
+        if (st == COMPILING && !frozen) {
+            const int v = flag->load(std::memory_order_acquire);
+            if (v != 0) { st = v == 1 ? READY : FAILED; flag.reset(); }
+        }
+        return st;
+    }
+    // build on the background pool, once: the launch path asks for nothing else, so the *_device entry points never compile (graph-capturable)
+    void request_async(int M, int K, int L, unsigned parts, int device)
+    {
+        if (st != NOT_REQUESTED) return;
+        flag = std::make_shared<std::atomic<int>>(0);
+        st = COMPILING;
+        gfdm::jit_prepare_async(M, K, L, parts, device, flag);
+    }
+    // build now, on the current device (constructors and set_channel_estimator only); a failure leaves the state as it was
+    bool build_now(int M, int K, int L, unsigned parts, std::string& why)
+    {
+        if (!gfdm::jit_prepare(M, K, L, parts, why)) return false;
+        st = READY;
+        flag.reset();
+        return true;
+    }
+    void set_failed() { st = FAILED; flag.reset(); }
+    // a *_host call cuts its batch into chunks, one launch each: what poll() answers at its start holds for all of them, so that a background
+    // build finishing meanwhile cannot change the rounding inside one call's output (FamilyPin below)
+    void freeze() { frozen = true; }
+    void thaw() { frozen = false; }
+    bool is_frozen() const { return frozen; }
+
+private:
+    State st = NOT_REQUESTED;
+    bool frozen = false;
+    std::shared_ptr<std::atomic<int>> flag;          // COMPILING only: 0 running, 1 ready, -1 failed (gfdm::jit_prepare_async)
+};
+
 struct Plan {
     int device = 0;
     gfdm::DevicePlan dp{};
@@ -70,33 +115,36 @@ struct Plan {
     const cf* d_twT = nullptr;       // [M][K] twiddles W_N^{q m}, transposed so that lane q reads them coalesced (row-lane family)
     int family = gfdm::FAMILY_GENERIC;
     gfdm::JitCache jit;              // FAMILY_ROWLANE_JIT: this handle's pointers to the loaded kernel parts (no lock on the launch path)
-    // run-time instantiation in the background (gfdm_hip_set_jit modes 2 / 3): 0 compiling, 1 ready, -1 failed.  While it is 0 the handle
-    // runs on the generic family; the first call that sees 1 switches the handle over (a handle is used by one thread at a time)
-    std::shared_ptr<std::atomic<int>> jit_pending;
-    // the preamble-equalised receive kernels of a run-time instantiated shape, built in the background after set_channel_estimator when they
-    // are neither cached nor quick to compile: 0 compiling (estimated calls run on the generic family meanwhile), 1 ready, -1 failed (they stay there)
-    std::shared_ptr<std::atomic<int>> jit_pre_pending;
-    // the gather-load receive kernels (JIT_PART_RX_BURST) of a run-time instantiated shape, the kernels of demodulate_bursts: requested by
-    // set_channel_estimator, or by the first such call of a handle that switched to the tuned kernels later.  Only demodulate_bursts reads this
-    // state; while the part is not there (0 compiling, -1 failed) that call runs on the generic family
-    bool jit_burst_ready = false;
-    std::shared_ptr<std::atomic<int>> jit_burst_pending;
-
-    // a *_host call cuts its batch into chunks, one launch each: the family (and the preamble-equalised kernels' availability) it starts
-    // with is the one all of its chunks run on, so that a background instantiation finishing meanwhile cannot change the rounding inside
-    // one call's output (FamilyPin below); -1 = not pinned
-    int pinned_family = -1, pinned_pre = -1;
+    // run-time instantiation in the background (gfdm_hip_set_jit modes 2 / 3): while COMPILING the handle runs on the generic family, the first
+    // call that sees READY switches it over (current_family), FAILED leaves it on the generic family for good
+    JitPart jit_family;
+    // the preamble-equalised receive kernels (JIT_PART_RX_PREAMBLE).  NOT_REQUESTED launches them -- the run-time layer loads them on demand:
+    // handles whose family was built in the constructor or in the same background job --, as does READY; while COMPILING or FAILED (a request of
+    // set_channel_estimator) the estimated calls run on the generic family
+    JitPart jit_pre;
+    // the gather-load receive kernels (JIT_PART_RX_BURST), the kernels of demodulate_bursts: requested by set_channel_estimator, or by the first
+    // such call of a handle that switched to the tuned kernels later.  Only READY launches them; only demodulate_bursts reads this state
+    JitPart jit_burst;
 
     // the family to launch with right now
     int current_family()
     {
-        if (pinned_family >= 0) return pinned_family;
-        if (jit_pending) {
-            const int st = jit_pending->load(std::memory_order_acquire);
-            if (st == 1) { family = gfdm::FAMILY_ROWLANE_JIT; kernel_name = "rowlane_jit"; }
-            if (st != 0) jit_pending.reset();
-        }
+        if (family != gfdm::FAMILY_ROWLANE_JIT && jit_family.poll() == JitPart::READY) { family = gfdm::FAMILY_ROWLANE_JIT; kernel_name = "rowlane_jit"; }
         return family;
+    }
+
+    // "tuned kernels for this call?" of a receive launch on FAMILY_ROWLANE_JIT (est as in rx_launch)
+    bool jit_tuned(const gfdm::EstPlan* est)
+    {
+        if (gfdm::burst_io(est)) {
+            // never built inside the call: requested on the pool, this call and those until it is there run on the generic family
+            const JitPart::State st = jit_burst.poll();
+            if (st == JitPart::NOT_REQUESTED) jit_burst.request_async(dp.M, dp.K, dp.L, 1u << gfdm::JIT_PART_RX_BURST, device);
+            return st == JitPart::READY;
+        }
+        if (!est) return true;
+        const JitPart::State st = jit_pre.poll();
+        return st == JitPart::NOT_REQUESTED || st == JitPart::READY;
     }
 
     ~Plan()
@@ -116,32 +164,30 @@ int ilog2_exact(int v)
     return l;
 }
 
+constexpr double two_pi = 6.283185307179586476925286766559;
+
 void unit_roots(std::vector<cf>& dst, int n)
 {
-    const double two_pi = 6.283185307179586476925286766559;
     for (int i = 0; i < n; ++i) {
         const double a = -two_pi * (double)i / (double)n;
         dst.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
     }
 }
 
-// Build the plan: normalise taps exactly as the reference constructors do, derive IC taps and twiddle tables.
-int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int device, bool receiver, unsigned jit_parts = 0)
-{
-    if (M < 1 || K < 1 || L < 1 || taps == nullptr) return fail(GFDM_HIP_EINVAL, "timeslots, subcarriers, overlap must be >= 1 and taps non-NULL");
-    if (ntaps != M * L) {
-        char buf[256];
-        snprintf(buf, sizeof(buf), "number of frequency taps(%d) MUST be equal to n_timeslots(%d) * overlap(%d) = %d!", ntaps, M, L, M * L);
-        return fail(GFDM_HIP_EINVAL_TAPS, buf);
-    }
-    if (receiver && L < 2) return fail(GFDM_HIP_EINVAL_OVERLAP, "overlap MUST be greater or equal 2");
-    if ((int64_t)M * K > (1 << 24)) return fail(GFDM_HIP_EUNSUPPORTED, "block too large");
-    const int dev_rc = gfdm::check_device(device);
-    if (dev_rc != GFDM_HIP_OK) return dev_rc;
-    const int N = M * K;
-    // (whether the block fits the kernels' LDS tiles is checked once the kernel family is known, below)
+// the host-side tables of a plan in upload order, and where the optional ones start (0 = absent: none of them comes first)
+struct PlanTables {
+    std::vector<cf> tables;          // taps | ictaps | ictaps / M | g | wM | wK | wN | twT | [icA] | [dftA] | [raderB]
+    bool taps_real = false, ic_real_sym = true;
+    size_t twT_off = 0, icA_off = 0, dftA_off = 0, rader_off = 0;
+    unsigned ic_sig = 0;
+    int dft_mt = 0, dft_ks = 0;
+};
 
-    pl.device = device;
+// Host only: normalise the taps exactly as the reference constructors do (pl.h_taps), derive the IC taps (pl.h_ictaps), the twiddles and the
+// operand tables of the matrix-core forms.
+int plan_tables(Plan& pl, PlanTables& pt, int M, int K, int L, const float* taps, int ntaps, bool receiver)
+{
+    const int N = M * K;
     // energy |sum t conj(t)|, factor formed in double and cast (lib/modulator_kernel_cc.cc:75-85)
     double energy = 0.0;
     for (int i = 0; i < ntaps; ++i) energy += (double)taps[2 * i] * taps[2 * i] + (double)taps[2 * i + 1] * taps[2 * i + 1];
@@ -161,16 +207,16 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
             pl.h_ictaps[m] = make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
         }
 
-    std::vector<cf> tables;
+    pt.taps_real = taps_real;
+    std::vector<cf>& tables = pt.tables;
     tables.reserve((size_t)ntaps + 4 * M + K + 2 * (size_t)N);
     for (const cf& t : pl.h_taps) tables.push_back(taps_real ? make_float2(t.x, 0.f) : t);
     tables.insert(tables.end(), pl.h_ictaps.begin(), pl.h_ictaps.end());
     for (int m = 0; m < M; ++m) tables.push_back(make_float2(pl.h_ictaps[m].x / (float)M, pl.h_ictaps[m].y / (float)M));
     // g = IDFT_M(ic)/M in double: one IC round is d_new = d0 - g (*) (dec_{k-1} + dec_{k+1})  (gfdm_rowlane_impl.h)
-    bool ic_real_sym = true;
+    bool& ic_real_sym = pt.ic_real_sym;
     std::vector<float> g_real(M);
     {
-        const double two_pi = 6.283185307179586476925286766559;
         std::vector<double> gr(M), gi(M);
         double gmax = 0.0;
         for (int r = 0; r < M; ++r) {
@@ -192,9 +238,8 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
     unit_roots(tables, M);
     unit_roots(tables, K);
     unit_roots(tables, N);
-    const size_t twT_off = tables.size();
+    pt.twT_off = tables.size();
     {
-        const double two_pi = 6.283185307179586476925286766559;
         for (int m = 0; m < M; ++m)
             for (int q = 0; q < K; ++q) {
                 const double a = -two_pi * (double)(((int64_t)q * m) % N) / (double)N;
@@ -208,8 +253,8 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
     // so that the B operand of lane row cr is made of the decisions of exactly the four timeslots the C / D operand of that lane row holds --
     // with a[p][r] = -s g[(p - r) mod M] 2^e (s = 1/sqrt 2: the QPSK amplitude; e puts the largest entry near 2^8 so that the residual terms
     // stay normal f16 numbers).  The decisions enter as +-2^-e, exact in f16.
-    size_t icA_off = 0;                     // (behind every other table: the pointers below are offsets into `tables`)
-    unsigned ic_sig = 0;
+    size_t& icA_off = pt.icA_off;           // (behind every other table: the offsets become pointers once the tables are on the device)
+    unsigned& ic_sig = pt.ic_sig;
     const int mx_mode = g_ic_mfma.load();
     if (receiver && ic_real_sym && (mx_mode == 2 ? gfdm::rowgeom::ic_mfma(K, M) : mx_mode == 1 && gfdm::rowgeom::ic_mfma_preferred(K, M))) {
         const double s = (double)0.70710678118654752f;
@@ -248,10 +293,9 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
     //   Q1 = C a.x, Q2 = C a.y, Q3 = S b.x, Q4 = S b.y   with a = v_p + v_{M-p}, b = v_p - v_{M-p}, C[m][p] = Re W_M^{m p}, S[m][p] = Im W_M^{m p}
     // as products of the CONSTANT matrices C, S (rows: outputs m <= M/2, columns: p = 0 (C = 1: the sample v_0 itself), the pairs p = 1..(M-1)/2,
     // the middle sample of an even M) with the block's samples.  A operand of v_mfma_f32_16x16x4_f32: lane l holds A[row l & 15][k = l >> 4].
-    size_t dftA_off = 0;
-    int dft_mt = 0, dft_ks = 0;
+    size_t& dftA_off = pt.dftA_off;
+    int &dft_mt = pt.dft_mt, &dft_ks = pt.dft_ks;
     if (g_dft_mfma.load() && M >= gfdm::MX_DFT_MIN_M) {
-        const double two_pi = 6.283185307179586476925286766559;
         const int H = M / 2 + 1, HP = (M - 1) / 2, KD = HP + 1 + ((M & 1) == 0 ? 1 : 0);
         dft_mt = (H + 15) / 16;
         dft_ks = (KD + 3) / 4;
@@ -274,7 +318,7 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
     }
 
     // Rader transforms for prime timeslot counts above the register codelets (gfdm_rader.hip): the kernel spectrum, default mode only
-    size_t rader_off = 0;
+    size_t& rader_off = pt.rader_off;
     if (g_dft_mfma.load() == 1 && !g_force_generic.load() && gfdm::rader_supports(M, K)) {
         std::vector<cf> rtab;
         gfdm::rader_host_table(M, rtab);
@@ -284,35 +328,14 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
         }
     }
 
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    GFDM_TRY(hipMalloc(&pl.d_tables, tables.size() * sizeof(cf)));
-    GFDM_TRY(hipMemcpy(pl.d_tables, tables.data(), tables.size() * sizeof(cf), hipMemcpyHostToDevice));
-    GFDM_TRY(hipStreamCreateWithFlags(&pl.stream, hipStreamNonBlocking));
+    return GFDM_HIP_OK;
+}
 
-    gfdm::DevicePlan& dp = pl.dp;
-    dp.M = M; dp.K = K; dp.L = L; dp.N = N;
-    dp.log2K = ilog2_exact(K);
-    dp.part_len = (M * L / 2 < M) ? (M * L / 2) : M;
-    dp.taps = pl.d_tables;
-    dp.taps_real = taps_real ? 1 : 0;
-    dp.ictaps = dp.taps + ntaps;
-    dp.ictaps_m = dp.ictaps + M;
-    dp.icg = dp.ictaps_m + M;
-    dp.ic_real_sym = ic_real_sym ? 1 : 0;
-    dp.icA = ic_sig ? static_cast<const void*>(pl.d_tables + icA_off) : nullptr;
-    dp.ic_sig = ic_sig;
-    dp.wM = dp.icg + M;
-    dp.wK = dp.wM + M;
-    dp.wN = dp.wK + K;
-    pl.d_twT = pl.d_tables + twT_off;
-    dp.dftA = dft_mt ? reinterpret_cast<const float*>(pl.d_tables + dftA_off) : nullptr;
-    dp.dft_mt = dft_mt;
-    dp.dft_ks = dft_ks;
-    dp.dft_always = g_dft_mfma.load() == 2 ? 1 : 0;
-    dp.raderB = rader_off ? pl.d_tables + rader_off : nullptr;
-    // kernel family: row-lane where the shape is instantiated, else the generic LDS family.  Only the explicit test hook
-    // gfdm_hip_force_generic_family_for_testing changes that; no environment variable does.
+// Kernel family of a new handle: row-lane where the shape is instantiated, else the generic LDS family.  Only the explicit test hook
+// gfdm_hip_force_generic_family_for_testing changes that; no environment variable does.
+int plan_choose_family(Plan& pl, bool receiver, unsigned jit_parts)
+{
+    const int M = pl.dp.M, K = pl.dp.K, L = pl.dp.L;
     pl.family = gfdm::FAMILY_GENERIC;
     if (!g_force_generic.load()) {
         if (gfdm::rowlane_supports(M, K, L)) {
@@ -323,7 +346,7 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
             // no compiler, ...) leaves the handle on the generic HIP family; the reason stays readable from gfdm_hip_last_error().
             // Only the parts this kind of handle launches are prepared (a modulator never compiles receiver kernels).
             std::string why;
-            DeviceGuard guard(device);
+            DeviceGuard guard(pl.device);
             if (jit_parts == 0) jit_parts = receiver ? (1u << gfdm::JIT_PART_RX) : (1u << gfdm::JIT_PART_MOD);
             int mode = g_jit.load();
             if (mode == 3) {
@@ -336,52 +359,101 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
             if (mode == 2 && gfdm::generic_supports(M, K, false)) {
                 // a receiver may get a channel estimator attached later: its preamble-equalised kernels are built in the same go, so that
                 // the switch-over never leaves a compile for the first estimated call
-                const unsigned parts = jit_parts | (receiver ? (1u << gfdm::JIT_PART_RX_PREAMBLE) : 0u);
-                pl.jit_pending = std::make_shared<std::atomic<int>>(0);
-                gfdm::jit_prepare_async(M, K, L, parts, device, pl.jit_pending);
-            } else if (gfdm::jit_prepare(M, K, L, jit_parts, why)) {
+                pl.jit_family.request_async(M, K, L, jit_parts | (receiver ? (1u << gfdm::JIT_PART_RX_PREAMBLE) : 0u), pl.device);
+            } else if (pl.jit_family.build_now(M, K, L, jit_parts, why)) {
                 pl.family = gfdm::FAMILY_ROWLANE_JIT;
             } else {
+                pl.jit_family.set_failed();
                 g_last_error = "run-time instantiation of the row-lane kernels failed, using the generic family: " + why;
             }
         }
     }
     pl.kernel_name = pl.family == gfdm::FAMILY_ROWLANE ? "rowlane" : pl.family == gfdm::FAMILY_ROWLANE_JIT ? "rowlane_jit" :
-                     dp.raderB ? "generic_rader" : "generic_lds";       // generic_rader: plain blocks on the Rader kernels (gfdm_rader.hip), the rest generic
+                     pl.dp.raderB ? "generic_rader" : "generic_lds";    // generic_rader: plain blocks on the Rader kernels (gfdm_rader.hip), the rest generic
     // the generic family holds two tiles of the block in LDS; handles on the row-lane families only use it for the stand-alone
     // transform_subcarriers_to_td / cancel_sc_interference entry points (one tile)
     if (!gfdm::generic_supports(M, K, pl.family != gfdm::FAMILY_GENERIC)) return fail(GFDM_HIP_EUNSUPPORTED, "root tables (2 * timeslots + subcarriers values) do not fit LDS");
     return GFDM_HIP_OK;
 }
 
-int status_of(hipError_t e) { return e == hipSuccess ? GFDM_HIP_OK : fail_hip(e, "kernel launch"); }
+// Build the plan: check the arguments, build the tables on the host, put them on the device, choose the kernel family.
+int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int device, bool receiver, unsigned jit_parts = 0)
+{
+    if (M < 1 || K < 1 || L < 1 || taps == nullptr) return fail(GFDM_HIP_EINVAL, "timeslots, subcarriers, overlap must be >= 1 and taps non-NULL");
+    if (ntaps != M * L) {
+        char buf[256];
+        snprintf(buf, sizeof(buf), "number of frequency taps(%d) MUST be equal to n_timeslots(%d) * overlap(%d) = %d!", ntaps, M, L, M * L);
+        return fail(GFDM_HIP_EINVAL_TAPS, buf);
+    }
+    if (receiver && L < 2) return fail(GFDM_HIP_EINVAL_OVERLAP, "overlap MUST be greater or equal 2");
+    if ((int64_t)M * K > (1 << 24)) return fail(GFDM_HIP_EUNSUPPORTED, "block too large");
+    const int dev_rc = gfdm::check_device(device);
+    if (dev_rc != GFDM_HIP_OK) return dev_rc;
+    pl.device = device;
+    PlanTables pt;
+    const int rc = plan_tables(pl, pt, M, K, L, taps, ntaps, receiver);
+    if (rc != GFDM_HIP_OK) return rc;
 
-// resolves the handle's kernel family once, for the duration of one *_host call (Plan::pinned_family).  A handle is used by ONE thread at a time
-// (include/gfdm_hip.h, "Threading"), so the pin is plain per-handle state; a pin that is already in place -- a *_host entry point reached from
-// inside another one's launch callback -- is inherited and left to its owner, not reset (round-5 advisor).
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    GFDM_TRY(hipMalloc(&pl.d_tables, pt.tables.size() * sizeof(cf)));
+    GFDM_TRY(hipMemcpy(pl.d_tables, pt.tables.data(), pt.tables.size() * sizeof(cf), hipMemcpyHostToDevice));
+    GFDM_TRY(hipStreamCreateWithFlags(&pl.stream, hipStreamNonBlocking));
+
+    gfdm::DevicePlan& dp = pl.dp;
+    dp.M = M; dp.K = K; dp.L = L; dp.N = M * K;
+    dp.log2K = ilog2_exact(K);
+    dp.part_len = (M * L / 2 < M) ? (M * L / 2) : M;
+    dp.taps = pl.d_tables;
+    dp.taps_real = pt.taps_real ? 1 : 0;
+    dp.ictaps = dp.taps + ntaps;
+    dp.ictaps_m = dp.ictaps + M;
+    dp.icg = dp.ictaps_m + M;
+    dp.ic_real_sym = pt.ic_real_sym ? 1 : 0;
+    dp.icA = pt.ic_sig ? static_cast<const void*>(pl.d_tables + pt.icA_off) : nullptr;
+    dp.ic_sig = pt.ic_sig;
+    dp.wM = dp.icg + M;
+    dp.wK = dp.wM + M;
+    dp.wN = dp.wK + K;
+    pl.d_twT = pl.d_tables + pt.twT_off;
+    dp.dftA = pt.dft_mt ? reinterpret_cast<const float*>(pl.d_tables + pt.dftA_off) : nullptr;
+    dp.dft_mt = pt.dft_mt;
+    dp.dft_ks = pt.dft_ks;
+    dp.dft_always = g_dft_mfma.load() == 2 ? 1 : 0;
+    dp.raderB = pt.rader_off ? pl.d_tables + pt.rader_off : nullptr;
+    return plan_choose_family(pl, receiver, jit_parts);
+}
+
+int status_of(hipError_t e) { return e == hipSuccess ? GFDM_HIP_OK : fail_hip(e, "kernel launch"); }
+int status_of(int status) { return status; }        // (a launch that had to check an argument first reports a status itself)
+
+// holds the answers of the handle's JitPart states for the duration of one *_host call, so that all of its chunks launch the same kernels.
+// A handle is used by ONE thread at a time (include/gfdm_hip.h, "Threading"), so the pin is plain per-handle state; a pin that is already in
+// place -- a *_host entry point reached from inside another one's launch callback -- is inherited and left to its owner, not released.
+// (The gather-load part is not pinned: demodulate_bursts is one launch per call.)
 struct FamilyPin {
     Plan& pl;
     bool owner;
-    explicit FamilyPin(Plan& p) : pl(p), owner(p.pinned_family < 0)
+    explicit FamilyPin(Plan& p) : pl(p), owner(!p.jit_family.is_frozen())
     {
         if (!owner) return;
-        const int f = pl.current_family();
-        int pre = 1;
-        if (pl.jit_pre_pending) {
-            if (pl.jit_pre_pending->load(std::memory_order_acquire) == 1) pl.jit_pre_pending.reset(); else pre = 0;
-        }
-        pl.pinned_family = f;
-        pl.pinned_pre = pre;
+        (void)pl.current_family();
+        (void)pl.jit_pre.poll();
+        pl.jit_family.freeze();
+        pl.jit_pre.freeze();
     }
-    ~FamilyPin() { if (owner) pl.pinned_family = pl.pinned_pre = -1; }
+    ~FamilyPin() { if (owner) { pl.jit_family.thaw(); pl.jit_pre.thaw(); } }
     FamilyPin(const FamilyPin&) = delete;
     FamilyPin& operator=(const FamilyPin&) = delete;
 };
 
-// Host-pointer path of the block entry points (gfdm_hostpipe.h): operands the GPU can address are used in place, the others bounce through
-// pinned staging sets in chunks, the kernels run across the link.  `launch(out, in0, in1, nb, stream)` enqueues the kernels of nb blocks and
-// returns a status.  Sizes are complex samples per block (frames in / demapped symbols out may differ from the block size); in1 may be read at
-// a stride (the preambles of the self-estimating receivers).
+// An operation of a handle is ONE function object `launch(out, in0, in1, nblocks, stream) -> hipError_t` that enqueues the kernels of nblocks
+// blocks; its *_device entry point hands it to run_device, its *_host entry point to run_host_sized.  Everything here is a template or a lambda
+// the compiler inlines: no std::function, no allocation per call.
+//
+// Host-pointer path (gfdm_hostpipe.h): operands the GPU can address are used in place, the others bounce through pinned staging sets in
+// chunks, one launch per chunk on what FamilyPin holds.  Sizes are complex samples per block (frames in / demapped symbols out may differ
+// from the block size); in1 may be read at a stride (the preambles of the self-estimating receivers).
 template <typename Launch>
 int run_host_sized(Plan& pl, float* out, size_t out_pb, const float* in0, size_t in0_pb, const float* in1, size_t in1_stride, size_t in1_pb,
                    int64_t nblocks, Launch launch)
@@ -395,7 +467,7 @@ int run_host_sized(Plan& pl, float* out, size_t out_pb, const float* in0, size_t
                                        { const_cast<float*>(in1), in1_stride * sizeof(cf), in1_pb * sizeof(cf), false } };
     const int nops = in1 ? 3 : 2;
     auto fn = [&](void* const* d, int64_t nb, hipStream_t s) {
-        return launch(static_cast<cf*>(d[0]), static_cast<const cf*>(d[1]), nops == 3 ? static_cast<const cf*>(d[2]) : nullptr, nb, s);
+        return status_of(launch(static_cast<cf*>(d[0]), static_cast<const cf*>(d[1]), nops == 3 ? static_cast<const cf*>(d[2]) : nullptr, nb, s));
     };
     FamilyPin pin(pl);
     return pl.pipe.run(pl.stream, ops, nops, nblocks, fn);
@@ -408,17 +480,17 @@ int run_host(Plan& pl, float* out, const float* in0, const float* in1, int64_t n
     return run_host_sized(pl, out, n, in0, n, in1, n, n, nblocks, launch);
 }
 
+// Device-pointer path: the checks and ONE launch on the caller's stream -- no compile, no allocation, no synchronisation, so that the
+// *_device entry points can be captured into a graph.
 template <typename Launch>
-int run_device(Plan& pl, void* out, const void* in0, int64_t nblocks, Launch launch)
+int run_device(Plan& pl, void* out, const void* in0, const void* in1, int64_t nblocks, void* stream, Launch launch)
 {
     if (nblocks < 0 || out == nullptr || in0 == nullptr) return fail(GFDM_HIP_EINVAL, "NULL buffer or negative block count");
     if (nblocks == 0) return GFDM_HIP_OK;
     if (nblocks > 0x7fffffff) return fail(GFDM_HIP_EINVAL, "more than 2^31 - 1 blocks per call (one workgroup or wavefront per block)");
     DeviceGuard guard(pl.device);
     if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    hipError_t e = launch();
-    if (e != hipSuccess) return fail_hip(e, "kernel launch");
-    return GFDM_HIP_OK;
+    return status_of(launch(static_cast<cf*>(out), static_cast<const cf*>(in0), static_cast<const cf*>(in1), nblocks, static_cast<hipStream_t>(stream)));
 }
 
 // est != nullptr: f_eq points at the received preambles and the kernel derives the equaliser itself (EQ_PREAMBLE)
@@ -427,26 +499,8 @@ hipError_t rx_launch(Plan& pl, const gfdm::IcParams& ic, int mode, cf* out, cons
 {
     const int family = pl.current_family();
     if (family == gfdm::FAMILY_ROWLANE) return gfdm::launch_rowlane_receive(pl.dp, ic, est, pl.d_twT, mode, out, in, f_eq, nblocks, s);
-    bool tuned = family == gfdm::FAMILY_ROWLANE_JIT;
-    if (tuned && gfdm::burst_io(est)) {
-        // demodulate_bursts: its own part, its own state (never compiled inside the call: the device entry point is graph-capturable)
-        if (!pl.jit_burst_ready) {
-            if (!pl.jit_burst_pending) {
-                pl.jit_burst_pending = std::make_shared<std::atomic<int>>(0);
-                gfdm::jit_prepare_async(pl.dp.M, pl.dp.K, pl.dp.L, 1u << gfdm::JIT_PART_RX_BURST, pl.device, pl.jit_burst_pending);
-            } else if (pl.jit_burst_pending->load(std::memory_order_acquire) == 1) {
-                pl.jit_burst_ready = true;
-                pl.jit_burst_pending.reset();
-            }
-        }
-        tuned = pl.jit_burst_ready;
-    }
-    else if (tuned && est && pl.pinned_pre >= 0) tuned = pl.pinned_pre == 1;
-    else if (tuned && est && pl.jit_pre_pending) {
-        const int st = pl.jit_pre_pending->load(std::memory_order_acquire);
-        if (st == 1) pl.jit_pre_pending.reset(); else tuned = false;       // still compiling (or failed): this estimated call runs on the generic family
-    }
-    if (tuned) return gfdm::jit_launch_receive(&pl.jit, pl.dp, ic, est, pl.d_twT, mode, out, in, f_eq, nblocks, s);
+    if (family == gfdm::FAMILY_ROWLANE_JIT && pl.jit_tuned(est))
+        return gfdm::jit_launch_receive(&pl.jit, pl.dp, ic, est, pl.d_twT, mode, out, in, f_eq, nblocks, s);
     return gfdm::launch_generic_receive(pl.dp, ic, est, mode, out, in, f_eq, nblocks, s);
 }
 
@@ -532,13 +586,18 @@ int frame_io_for_call(const FrameIo& f, const Plan& pl, int noutput_size, gfdm::
     return GFDM_HIP_OK;
 }
 
-struct gfdm_hip_receiver { Plan plan; FrameIo frames; const gfdm_hip_channel_estimator* est = nullptr; };
-struct gfdm_hip_advanced_receiver {
+// what the plain and the interference-cancelling receiver share, and every call kind written once against it (rx_* below)
+struct RxCore {
     Plan plan;
     FrameIo frames;
     const gfdm_hip_channel_estimator* est = nullptr;
-    gfdm::IcParams ic{};
+    gfdm::IcParams ic = kNoIc;       // the plain receiver's stays kNoIc
+    int mode = gfdm::RX_DEMOD;       // what the handle's own call kinds launch: RX_DEMOD or RX_IC
+};
+struct gfdm_hip_receiver : RxCore {};
+struct gfdm_hip_advanced_receiver : RxCore {
     void* d_ic = nullptr;     // points | smap | active
+    gfdm_hip_advanced_receiver() { mode = gfdm::RX_IC; }
     ~gfdm_hip_advanced_receiver()
     {
         if (d_ic) {
@@ -547,6 +606,46 @@ struct gfdm_hip_advanced_receiver {
         }
     }
 };
+
+namespace {
+
+// the receive launch of one call: `ic` carries the call's I/O layout, `est` its estimator plan (none: the caller brings the equaliser)
+auto rx_op(RxCore& c, const gfdm::IcParams& ic, int mode, const gfdm::EstPlan* est = nullptr)
+{
+    return [&c, &ic, mode, est](cf* o, const cf* i, const cf* e, int64_t nb, hipStream_t s) { return rx_launch(c.plan, ic, mode, o, i, e, nb, s, est); };
+}
+
+// plain blocks; mode: the handle's own, or RX_FD for fft_filter_downsample
+int rx_block_device(RxCore& c, int mode, void* out, const void* in, const void* f_eq, int64_t nblocks, void* stream)
+{
+    return run_device(c.plan, out, in, f_eq, nblocks, stream, rx_op(c, c.ic, mode));
+}
+
+int rx_block_host(RxCore& c, int mode, float* out, const float* in, const float* f_eq, int64_t nblocks)
+{
+    return run_host(c.plan, out, in, f_eq, nblocks, rx_op(c, c.ic, mode));
+}
+
+// raw frames in, demapped symbols out (configure_frames)
+int rx_frames_device(RxCore& c, void* out, const void* in, const void* f_eq, int noutput_size, int64_t nblocks, void* stream)
+{
+    gfdm::IcParams ic = c.ic;
+    int rc = frame_io_for_call(c.frames, c.plan, noutput_size, ic.io);
+    if (rc != GFDM_HIP_OK) return rc;
+    return run_device(c.plan, out, in, f_eq, nblocks, stream, rx_op(c, ic, c.mode));
+}
+
+int rx_frames_host(RxCore& c, float* out, const float* in, const float* f_eq, int noutput_size, int64_t nblocks)
+{
+    if (nblocks < 0) return fail(GFDM_HIP_EINVAL, "negative block count");
+    gfdm::IcParams ic = c.ic;
+    int rc = frame_io_for_call(c.frames, c.plan, noutput_size, ic.io);
+    if (rc != GFDM_HIP_OK) return rc;
+    const size_t n = (size_t)c.plan.dp.N;
+    return run_host_sized(c.plan, out, (size_t)ic.io.nout, in, (size_t)ic.io.in_stride, f_eq, n, n, nblocks, rx_op(c, ic, c.mode));
+}
+
+}  // namespace
 
 // ---------------------------------------------------------------------------------------------
 
@@ -688,20 +787,21 @@ int gfdm_hip_modulator_filter_taps(const gfdm_hip_modulator* m, float* out)
 
 const char* gfdm_hip_modulator_kernel_name(const gfdm_hip_modulator* m) { return m ? plan_kernel_name(m->plan) : ""; }
 
+static auto mod_op(gfdm_hip_modulator* m)
+{
+    return [m](cf* o, const cf* i, const cf*, int64_t nb, hipStream_t s) { return mod_launch(m->plan, kNoTx, o, i, nb, s); };
+}
+
 int gfdm_hip_modulator_work_device(gfdm_hip_modulator* m, void* out, const void* in, int64_t nblocks, void* stream)
 {
     if (!m) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_device(m->plan, out, in, nblocks, [&]() {
-        return mod_launch(m->plan, kNoTx, (cf*)out, (const cf*)in, nblocks, (hipStream_t)stream);
-    });
+    return run_device(m->plan, out, in, nullptr, nblocks, stream, mod_op(m));
 }
 
 int gfdm_hip_modulator_work_host(gfdm_hip_modulator* m, float* out, const float* in, int64_t nblocks)
 {
     if (!m) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_host(m->plan, out, in, nullptr, nblocks, [&](cf* o, const cf* i, const cf*, int64_t nb, hipStream_t s) {
-        return status_of(mod_launch(m->plan, kNoTx, o, i, nb, s));
-    });
+    return run_host(m->plan, out, in, nullptr, nblocks, mod_op(m));
 }
 
 // ---- receiver ----
@@ -744,50 +844,49 @@ const char* gfdm_hip_receiver_kernel_name(const gfdm_hip_receiver* r) { return r
 int gfdm_hip_receiver_demodulate_device(gfdm_hip_receiver* r, void* out, const void* in, const void* f_eq, int64_t nblocks, void* stream)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_device(r->plan, out, in, nblocks, [&]() {
-        return rx_launch(r->plan, kNoIc, gfdm::RX_DEMOD, (cf*)out, (const cf*)in, (const cf*)f_eq, nblocks, (hipStream_t)stream);
-    });
+    return rx_block_device(*r, r->mode, out, in, f_eq, nblocks, stream);
 }
 
 int gfdm_hip_receiver_demodulate_host(gfdm_hip_receiver* r, float* out, const float* in, const float* f_eq, int64_t nblocks)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_host(r->plan, out, in, f_eq, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, hipStream_t s) {
-        return status_of(rx_launch(r->plan, kNoIc, gfdm::RX_DEMOD, o, i, e, nb, s));
-    });
+    return rx_block_host(*r, r->mode, out, in, f_eq, nblocks);
 }
 
 int gfdm_hip_receiver_fft_filter_downsample_device(gfdm_hip_receiver* r, void* out, const void* in, const void* f_eq, int64_t nblocks,
                                                    void* stream)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_device(r->plan, out, in, nblocks, [&]() {
-        return rx_launch(r->plan, kNoIc, gfdm::RX_FD, (cf*)out, (const cf*)in, (const cf*)f_eq, nblocks, (hipStream_t)stream);
-    });
+    return rx_block_device(*r, gfdm::RX_FD, out, in, f_eq, nblocks, stream);
 }
 
 int gfdm_hip_receiver_fft_filter_downsample_host(gfdm_hip_receiver* r, float* out, const float* in, const float* f_eq, int64_t nblocks)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_host(r->plan, out, in, f_eq, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, hipStream_t s) {
-        return status_of(rx_launch(r->plan, kNoIc, gfdm::RX_FD, o, i, e, nb, s));
-    });
+    return rx_block_host(*r, gfdm::RX_FD, out, in, f_eq, nblocks);
+}
+
+// the two stand-alone stages of the reference's receiver kernel: always the generic family's kernels
+static auto to_td_op(gfdm_hip_receiver* r)
+{
+    return [r](cf* o, const cf* i, const cf*, int64_t nb, hipStream_t s) { return gfdm::launch_generic_to_td(r->plan.dp, o, i, nb, s); };
+}
+
+static auto cancel_op(gfdm_hip_receiver* r)
+{
+    return [r](cf* o, const cf* td, const cf* fd, int64_t nb, hipStream_t s) { return gfdm::launch_generic_cancel(r->plan.dp, o, td, fd, nb, s); };
 }
 
 int gfdm_hip_receiver_transform_subcarriers_to_td_device(gfdm_hip_receiver* r, void* out, const void* in, int64_t nblocks, void* stream)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_device(r->plan, out, in, nblocks, [&]() {
-        return gfdm::launch_generic_to_td(r->plan.dp, (cf*)out, (const cf*)in, nblocks, (hipStream_t)stream);
-    });
+    return run_device(r->plan, out, in, nullptr, nblocks, stream, to_td_op(r));
 }
 
 int gfdm_hip_receiver_transform_subcarriers_to_td_host(gfdm_hip_receiver* r, float* out, const float* in, int64_t nblocks)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_host(r->plan, out, in, nullptr, nblocks, [&](cf* o, const cf* i, const cf*, int64_t nb, hipStream_t s) {
-        return status_of(gfdm::launch_generic_to_td(r->plan.dp, o, i, nb, s));
-    });
+    return run_host(r->plan, out, in, nullptr, nblocks, to_td_op(r));
 }
 
 int gfdm_hip_receiver_cancel_sc_interference_device(gfdm_hip_receiver* r, void* out, const void* td_in, const void* fd_in,
@@ -795,9 +894,7 @@ int gfdm_hip_receiver_cancel_sc_interference_device(gfdm_hip_receiver* r, void* 
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
     if (!fd_in) return fail(GFDM_HIP_EINVAL, "NULL buffer");
-    return run_device(r->plan, out, td_in, nblocks, [&]() {
-        return gfdm::launch_generic_cancel(r->plan.dp, (cf*)out, (const cf*)td_in, (const cf*)fd_in, nblocks, (hipStream_t)stream);
-    });
+    return run_device(r->plan, out, td_in, fd_in, nblocks, stream, cancel_op(r));
 }
 
 int gfdm_hip_receiver_cancel_sc_interference_host(gfdm_hip_receiver* r, float* out, const float* td_in, const float* fd_in,
@@ -805,9 +902,7 @@ int gfdm_hip_receiver_cancel_sc_interference_host(gfdm_hip_receiver* r, float* o
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
     if (!fd_in) return fail(GFDM_HIP_EINVAL, "NULL buffer");
-    return run_host(r->plan, out, td_in, fd_in, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, hipStream_t s) {
-        return status_of(gfdm::launch_generic_cancel(r->plan.dp, o, i, e, nb, s));
-    });
+    return run_host(r->plan, out, td_in, fd_in, nblocks, cancel_op(r));
 }
 
 // ---- advanced receiver ----
@@ -919,24 +1014,16 @@ int gfdm_hip_advanced_receiver_work_device(gfdm_hip_advanced_receiver* a, void* 
                                            void* stream)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_device(a->plan, out, in, nblocks, [&]() {
-        return rx_launch(a->plan, a->ic, gfdm::RX_IC, (cf*)out, (const cf*)in, (const cf*)f_eq, nblocks, (hipStream_t)stream);
-    });
+    return rx_block_device(*a, a->mode, out, in, f_eq, nblocks, stream);
 }
 
 int gfdm_hip_advanced_receiver_work_host(gfdm_hip_advanced_receiver* a, float* out, const float* in, const float* f_eq, int64_t nblocks)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_host(a->plan, out, in, f_eq, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, hipStream_t s) {
-        return status_of(rx_launch(a->plan, a->ic, gfdm::RX_IC, o, i, e, nb, s));
-    });
+    return rx_block_host(*a, a->mode, out, in, f_eq, nblocks);
 }
 
-}  // extern "C"
-
 // ---- receiver / advanced receiver on raw frames with demapped output ----
-
-extern "C" {
 
 int gfdm_hip_receiver_configure_frames(gfdm_hip_receiver* r, int frame_len, int cp_len, const int* subcarrier_map, int n_subcarrier_map,
                                        int per_timeslot)
@@ -956,52 +1043,28 @@ int gfdm_hip_receiver_demodulate_frames_device(gfdm_hip_receiver* r, void* out, 
                                                int64_t nblocks, void* stream)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    gfdm::IcParams ic = kNoIc;
-    int rc = frame_io_for_call(r->frames, r->plan, noutput_size, ic.io);
-    if (rc != GFDM_HIP_OK) return rc;
-    return run_device(r->plan, out, in, nblocks, [&]() {
-        return rx_launch(r->plan, ic, gfdm::RX_DEMOD, (cf*)out, (const cf*)in, (const cf*)f_eq, nblocks, (hipStream_t)stream);
-    });
+    return rx_frames_device(*r, out, in, f_eq, noutput_size, nblocks, stream);
 }
 
 int gfdm_hip_advanced_receiver_work_frames_device(gfdm_hip_advanced_receiver* a, void* out, const void* in, const void* f_eq,
                                                   int noutput_size, int64_t nblocks, void* stream)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    gfdm::IcParams ic = a->ic;
-    int rc = frame_io_for_call(a->frames, a->plan, noutput_size, ic.io);
-    if (rc != GFDM_HIP_OK) return rc;
-    return run_device(a->plan, out, in, nblocks, [&]() {
-        return rx_launch(a->plan, ic, gfdm::RX_IC, (cf*)out, (const cf*)in, (const cf*)f_eq, nblocks, (hipStream_t)stream);
-    });
+    return rx_frames_device(*a, out, in, f_eq, noutput_size, nblocks, stream);
 }
 
 int gfdm_hip_receiver_demodulate_frames_host(gfdm_hip_receiver* r, float* out, const float* in, const float* f_eq, int noutput_size,
                                              int64_t nblocks)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    if (nblocks < 0) return fail(GFDM_HIP_EINVAL, "negative block count");
-    gfdm::RxIo io;
-    int rc = frame_io_for_call(r->frames, r->plan, noutput_size, io);
-    if (rc != GFDM_HIP_OK) return rc;
-    const size_t n = (size_t)r->plan.dp.N;
-    return run_host_sized(r->plan, out, (size_t)io.nout, in, (size_t)io.in_stride, f_eq, n, n, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, hipStream_t s) {
-        return gfdm_hip_receiver_demodulate_frames_device(r, o, i, e, noutput_size, nb, (void*)s);
-    });
+    return rx_frames_host(*r, out, in, f_eq, noutput_size, nblocks);
 }
 
 int gfdm_hip_advanced_receiver_work_frames_host(gfdm_hip_advanced_receiver* a, float* out, const float* in, const float* f_eq,
                                                 int noutput_size, int64_t nblocks)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    if (nblocks < 0) return fail(GFDM_HIP_EINVAL, "negative block count");
-    gfdm::RxIo io;
-    int rc = frame_io_for_call(a->frames, a->plan, noutput_size, io);
-    if (rc != GFDM_HIP_OK) return rc;
-    const size_t n = (size_t)a->plan.dp.N;
-    return run_host_sized(a->plan, out, (size_t)io.nout, in, (size_t)io.in_stride, f_eq, n, n, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, hipStream_t s) {
-        return gfdm_hip_advanced_receiver_work_frames_device(a, o, i, e, noutput_size, nb, (void*)s);
-    });
+    return rx_frames_host(*a, out, in, f_eq, noutput_size, nblocks);
 }
 
 }  // extern "C"
@@ -1111,7 +1174,11 @@ int gfdm_hip_transmitter_cyclic_shift(const gfdm_hip_transmitter* t, int port)
 }
 const char* gfdm_hip_transmitter_kernel_name(const gfdm_hip_transmitter* t) { return t ? plan_kernel_name(t->plan) : ""; }
 
-static int tx_check_nin(const gfdm_hip_transmitter* t, int ninput_size)
+}  // extern "C"
+
+namespace {
+
+int tx_check_nin(const gfdm_hip_transmitter* t, int ninput_size)
 {
     if (ninput_size < 0 || ninput_size > t->A * t->M) {
         char buf[200];
@@ -1121,47 +1188,60 @@ static int tx_check_nin(const gfdm_hip_transmitter* t, int ninput_size)
     return GFDM_HIP_OK;
 }
 
-int gfdm_hip_transmitter_work_device(gfdm_hip_transmitter* t, void* const* outs, int n_outs, const void* in, int ninput_size,
-                                     int64_t nblocks, void* stream)
+// The three transmitter operations as launches over the device pointers of one call or one chunk (`outs`: the output ports).  The arguments
+// were checked by the entry point; add_frame's cyclic shift is looked up by tx_add_frame_params.
+auto tx_work_op(gfdm_hip_transmitter* t, int n_outs, int ninput_size)
 {
-    if (!t || !outs || !in) return fail(GFDM_HIP_EINVAL, "NULL argument");
-    if (n_outs < 1 || n_outs > t->tx.nports) return fail(GFDM_HIP_EINVAL, "n_outs must be between 1 and the number of cyclic shifts");
-    int rc = tx_check_nin(t, ninput_size);
-    if (rc != GFDM_HIP_OK) return rc;
-    gfdm::TxParams tx = t->tx;
-    tx.mapped = 1; tx.framed = 1; tx.nin = ninput_size; tx.nports = n_outs;
-    for (int i = 0; i < n_outs; ++i) {
-        if (!outs[i]) return fail(GFDM_HIP_EINVAL, "NULL output port");
-        tx.outs[i] = (cf*)outs[i];
-    }
-    return run_device(t->plan, outs[0], in, nblocks, [&]() { return mod_launch(t->plan, tx, nullptr, (const cf*)in, nblocks, (hipStream_t)stream); });
+    return [=](void* const* outs, const cf* in, int64_t nb, hipStream_t s) {
+        gfdm::TxParams tx = t->tx;
+        tx.mapped = 1; tx.framed = 1; tx.nin = ninput_size; tx.nports = n_outs;
+        for (int i = 0; i < n_outs; ++i) tx.outs[i] = (cf*)outs[i];
+        return mod_launch(t->plan, tx, nullptr, in, nb, s);
+    };
 }
 
-int gfdm_hip_transmitter_modulate_device(gfdm_hip_transmitter* t, void* out, const void* in, int ninput_size, int64_t nblocks, void* stream)
+auto tx_modulate_op(gfdm_hip_transmitter* t, int ninput_size)
 {
-    if (!t) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    int rc = tx_check_nin(t, ninput_size);
-    if (rc != GFDM_HIP_OK) return rc;
-    gfdm::TxParams tx = t->tx;
-    tx.mapped = 1; tx.framed = 0; tx.nin = ninput_size;
-    return run_device(t->plan, out, in, nblocks, [&]() { return mod_launch(t->plan, tx, (cf*)out, (const cf*)in, nblocks, (hipStream_t)stream); });
+    return [=](void* const* outs, const cf* in, int64_t nb, hipStream_t s) {
+        gfdm::TxParams tx = t->tx;
+        tx.mapped = 1; tx.framed = 0; tx.nin = ninput_size;
+        return mod_launch(t->plan, tx, (cf*)outs[0], in, nb, s);
+    };
 }
 
-int gfdm_hip_transmitter_add_frame_device(gfdm_hip_transmitter* t, void* out, const void* in, int cyclic_shift, int64_t nblocks, void* stream)
+int tx_add_frame_params(const gfdm_hip_transmitter* t, int cyclic_shift, gfdm::TxParams& tx)
 {
-    if (!t) return fail(GFDM_HIP_EINVAL, "NULL handle");
     int port = -1;
     for (int i = 0; i < t->tx.nports; ++i) if (t->tx.shifts[i] == cyclic_shift) { port = i; break; }
     if (port < 0) return fail(GFDM_HIP_EINVAL, "no preamble was registered for this cyclic shift");     // d_preambles lookup, transmitter_kernel.cc:86-90
-    gfdm::TxParams tx = t->tx;
-    tx.mapped = 0; tx.framed = 1; tx.nports = 1; tx.shifts[0] = cyclic_shift; tx.outs[0] = (cf*)out;
+    tx = t->tx;
+    tx.mapped = 0; tx.framed = 1; tx.nports = 1; tx.shifts[0] = cyclic_shift;
     tx.preambles = t->tx.preambles + (int64_t)port * t->tx.plen;
-    return run_device(t->plan, out, in, nblocks, [&]() { return gfdm::launch_add_frame(t->plan.dp, tx, (const cf*)in, nblocks, (hipStream_t)stream); });
+    return GFDM_HIP_OK;
 }
 
-// host-pointer variants (gfdm_hostpipe.h): operands = the output ports, then the symbols
-static int tx_host(gfdm_hip_transmitter* t, float* const* outs, int n_outs, size_t out_elems_per_block, const float* in,
-                   size_t in_elems_per_block, int64_t nblocks, const std::function<int(void* const*, const void*, int64_t, hipStream_t)>& enqueue)
+auto tx_add_frame_op(gfdm_hip_transmitter* t, const gfdm::TxParams& params)
+{
+    return [t, &params](void* const* outs, const cf* in, int64_t nb, hipStream_t s) {
+        gfdm::TxParams tx = params;
+        tx.outs[0] = (cf*)outs[0];
+        return gfdm::launch_add_frame(t->plan.dp, tx, in, nb, s);
+    };
+}
+
+// a transmitter operation on the caller's stream: outs[0] and `in` stand for all operands in run_device's checks
+template <typename TxLaunch>
+int tx_device(gfdm_hip_transmitter* t, void* const* outs, const void* in, int64_t nblocks, void* stream, TxLaunch launch)
+{
+    return run_device(t->plan, outs[0], in, nullptr, nblocks, stream,
+                      [&](cf*, const cf* i, const cf*, int64_t nb, hipStream_t s) { return launch(outs, i, nb, s); });
+}
+
+// ... and on host pointers (gfdm_hostpipe.h): operands = the output ports, then the symbols; one launch per chunk (a status instead of a
+// hipError_t passes through: add_frame_host)
+template <typename TxLaunch>
+int tx_host(gfdm_hip_transmitter* t, float* const* outs, int n_outs, size_t out_elems_per_block, const float* in,
+                   size_t in_elems_per_block, int64_t nblocks, TxLaunch launch)
 {
     if (nblocks < 0 || !outs || !in) return fail(GFDM_HIP_EINVAL, "NULL buffer or negative block count");
     if (nblocks == 0) return GFDM_HIP_OK;
@@ -1174,9 +1254,42 @@ static int tx_host(gfdm_hip_transmitter* t, float* const* outs, int n_outs, size
         ops[i] = gfdm::HostOperand{ outs[i], out_elems_per_block * sizeof(cf), out_elems_per_block * sizeof(cf), true };
     }
     ops[n_outs] = gfdm::HostOperand{ const_cast<float*>(in), in_elems_per_block * sizeof(cf), in_elems_per_block * sizeof(cf), false };
-    auto fn = [&](void* const* d, int64_t nb, hipStream_t s) { return enqueue(d, d[n_outs], nb, s); };
+    auto fn = [&](void* const* d, int64_t nb, hipStream_t s) { return status_of(launch(d, static_cast<const cf*>(d[n_outs]), nb, s)); };
     FamilyPin pin(pl);
     return pl.pipe.run(pl.stream, ops, n_outs + 1, nblocks, fn);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gfdm_hip_transmitter_work_device(gfdm_hip_transmitter* t, void* const* outs, int n_outs, const void* in, int ninput_size,
+                                     int64_t nblocks, void* stream)
+{
+    if (!t || !outs || !in) return fail(GFDM_HIP_EINVAL, "NULL argument");
+    if (n_outs < 1 || n_outs > t->tx.nports) return fail(GFDM_HIP_EINVAL, "n_outs must be between 1 and the number of cyclic shifts");
+    int rc = tx_check_nin(t, ninput_size);
+    if (rc != GFDM_HIP_OK) return rc;
+    for (int i = 0; i < n_outs; ++i)
+        if (!outs[i]) return fail(GFDM_HIP_EINVAL, "NULL output port");
+    return tx_device(t, outs, in, nblocks, stream, tx_work_op(t, n_outs, ninput_size));
+}
+
+int gfdm_hip_transmitter_modulate_device(gfdm_hip_transmitter* t, void* out, const void* in, int ninput_size, int64_t nblocks, void* stream)
+{
+    if (!t) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    int rc = tx_check_nin(t, ninput_size);
+    if (rc != GFDM_HIP_OK) return rc;
+    return tx_device(t, &out, in, nblocks, stream, tx_modulate_op(t, ninput_size));
+}
+
+int gfdm_hip_transmitter_add_frame_device(gfdm_hip_transmitter* t, void* out, const void* in, int cyclic_shift, int64_t nblocks, void* stream)
+{
+    if (!t) return fail(GFDM_HIP_EINVAL, "NULL handle");
+    gfdm::TxParams tx;
+    int rc = tx_add_frame_params(t, cyclic_shift, tx);
+    if (rc != GFDM_HIP_OK) return rc;
+    return tx_device(t, &out, in, nblocks, stream, tx_add_frame_op(t, tx));
 }
 
 int gfdm_hip_transmitter_work_host(gfdm_hip_transmitter* t, float* const* outs, int n_outs, const float* in, int ninput_size, int64_t nblocks)
@@ -1185,9 +1298,7 @@ int gfdm_hip_transmitter_work_host(gfdm_hip_transmitter* t, float* const* outs, 
     if (n_outs < 1 || n_outs > t->tx.nports) return fail(GFDM_HIP_EINVAL, "n_outs must be between 1 and the number of cyclic shifts");
     int rc = tx_check_nin(t, ninput_size);
     if (rc != GFDM_HIP_OK) return rc;
-    return tx_host(t, outs, n_outs, (size_t)t->tx.F, in, (size_t)ninput_size, nblocks, [&](void* const* d_outs, const void* d_in, int64_t nb, hipStream_t s) {
-        return gfdm_hip_transmitter_work_device(t, d_outs, n_outs, d_in, ninput_size, nb, (void*)s);
-    });
+    return tx_host(t, outs, n_outs, (size_t)t->tx.F, in, (size_t)ninput_size, nblocks, tx_work_op(t, n_outs, ninput_size));
 }
 
 int gfdm_hip_transmitter_modulate_host(gfdm_hip_transmitter* t, float* out, const float* in, int ninput_size, int64_t nblocks)
@@ -1196,17 +1307,19 @@ int gfdm_hip_transmitter_modulate_host(gfdm_hip_transmitter* t, float* out, cons
     int rc = tx_check_nin(t, ninput_size);
     if (rc != GFDM_HIP_OK) return rc;
     float* outs[1] = { out };
-    return tx_host(t, outs, 1, (size_t)t->plan.dp.N, in, (size_t)ninput_size, nblocks, [&](void* const* d_outs, const void* d_in, int64_t nb, hipStream_t s) {
-        return gfdm_hip_transmitter_modulate_device(t, d_outs[0], d_in, ninput_size, nb, (void*)s);
-    });
+    return tx_host(t, outs, 1, (size_t)t->plan.dp.N, in, (size_t)ninput_size, nblocks, tx_modulate_op(t, ninput_size));
 }
 
 int gfdm_hip_transmitter_add_frame_host(gfdm_hip_transmitter* t, float* out, const float* in, int cyclic_shift, int64_t nblocks)
 {
     if (!t) return fail(GFDM_HIP_EINVAL, "NULL handle");
     float* outs[1] = { out };
-    return tx_host(t, outs, 1, (size_t)t->tx.F, in, (size_t)t->plan.dp.N, nblocks, [&](void* const* d_outs, const void* d_in, int64_t nb, hipStream_t s) {
-        return gfdm_hip_transmitter_add_frame_device(t, d_outs[0], d_in, cyclic_shift, nb, (void*)s);
+    // the cyclic shift is looked up when the first chunk is enqueued, behind the buffer checks and the zero-block return: as it always was
+    return tx_host(t, outs, 1, (size_t)t->tx.F, in, (size_t)t->plan.dp.N, nblocks, [&](void* const* d_outs, const cf* d_in, int64_t nb, hipStream_t s) {
+        gfdm::TxParams tx;
+        int rc = tx_add_frame_params(t, cyclic_shift, tx);
+        if (rc != GFDM_HIP_OK) return rc;
+        return status_of(tx_add_frame_op(t, tx)(d_outs, d_in, nb, s));
     });
 }
 
@@ -1225,7 +1338,6 @@ namespace {
 // plain O(K^2) DFT in double: constructor-time only (the reference runs FFTW here, :99-107)
 void host_dft(std::vector<std::complex<double>>& out, const float* in, int K)
 {
-    const double two_pi = 6.283185307179586476925286766559;
     out.assign(K, std::complex<double>(0.0, 0.0));
     std::vector<std::complex<double>> w(K);
     for (int i = 0; i < K; ++i) w[i] = std::complex<double>(std::cos(two_pi * i / K), -std::sin(two_pi * i / K));
@@ -1251,17 +1363,27 @@ int est_stage_elems(const gfdm::EstPlan& e, int stage)
     }
 }
 
+// stages in_stage -> out_stage of the estimator; the whole chain (received preamble -> frame estimate) has row-lane kernels
+auto est_op(gfdm_hip_channel_estimator* c, int in_stage, int out_stage)
+{
+    return [=](cf* o, const cf* i, const cf*, int64_t nf, hipStream_t s) {
+        const int family = c->plan.current_family();
+        const bool chain = in_stage == gfdm::EST_RX_PREAMBLE && out_stage == gfdm::EST_FRAME;
+        if (chain && family == gfdm::FAMILY_ROWLANE) return gfdm::launch_rowlane_estimate(c->ep, o, i, nf, s);
+        if (chain && family == gfdm::FAMILY_ROWLANE_JIT) return gfdm::jit_launch_estimate(&c->plan.jit, c->ep, o, i, nf, s);
+        return gfdm::launch_estimate(c->ep, in_stage, out_stage, o, i, nf, s);
+    };
+}
+
+auto zf_op(gfdm_hip_channel_estimator* c)
+{
+    return [c](cf* o, const cf* i, const cf*, int64_t nf, hipStream_t s) { return gfdm::launch_prepare_for_zf(o, i, nf * c->ep.M * c->ep.K, s); };
+}
+
 int est_run_device(gfdm_hip_channel_estimator* c, int in_stage, int out_stage, void* out, const void* in, int64_t nframes, void* stream)
 {
     if (!c) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_device(c->plan, out, in, nframes, [&]() {
-        if (c->plan.current_family() == gfdm::FAMILY_ROWLANE && in_stage == gfdm::EST_RX_PREAMBLE && out_stage == gfdm::EST_FRAME)
-            return gfdm::launch_rowlane_estimate(c->ep, static_cast<cf*>(out), static_cast<const cf*>(in), nframes, static_cast<hipStream_t>(stream));
-        if (c->plan.family == gfdm::FAMILY_ROWLANE_JIT && in_stage == gfdm::EST_RX_PREAMBLE && out_stage == gfdm::EST_FRAME)
-            return gfdm::jit_launch_estimate(&c->plan.jit, c->ep, static_cast<cf*>(out), static_cast<const cf*>(in), nframes, static_cast<hipStream_t>(stream));
-        return gfdm::launch_estimate(c->ep, in_stage, out_stage, static_cast<cf*>(out), static_cast<const cf*>(in), nframes,
-                                     static_cast<hipStream_t>(stream));
-    });
+    return run_device(c->plan, out, in, nullptr, nframes, stream, est_op(c, in_stage, out_stage));
 }
 
 int est_run_host(gfdm_hip_channel_estimator* c, int in_stage, int out_stage, float* out, const float* in, int64_t nframes)
@@ -1269,13 +1391,7 @@ int est_run_host(gfdm_hip_channel_estimator* c, int in_stage, int out_stage, flo
     if (!c) return fail(GFDM_HIP_EINVAL, "NULL handle");
     if (nframes < 0) return fail(GFDM_HIP_EINVAL, "negative frame count");
     const size_t nout = est_stage_elems(c->ep, out_stage), nin = est_stage_elems(c->ep, in_stage);
-    return run_host_sized(c->plan, out, nout, in, nin, nullptr, 0, 0, nframes, [&](cf* o, const cf* i, const cf*, int64_t nf, hipStream_t s) {
-        if (c->plan.current_family() == gfdm::FAMILY_ROWLANE && in_stage == gfdm::EST_RX_PREAMBLE && out_stage == gfdm::EST_FRAME)
-            return status_of(gfdm::launch_rowlane_estimate(c->ep, o, i, nf, s));
-        if (c->plan.family == gfdm::FAMILY_ROWLANE_JIT && in_stage == gfdm::EST_RX_PREAMBLE && out_stage == gfdm::EST_FRAME)
-            return status_of(gfdm::jit_launch_estimate(&c->plan.jit, c->ep, o, i, nf, s));
-        return status_of(gfdm::launch_estimate(c->ep, in_stage, out_stage, o, i, nf, s));
-    });
+    return run_host_sized(c->plan, out, nout, in, nin, nullptr, 0, 0, nframes, est_op(c, in_stage, out_stage));
 }
 
 }  // namespace
@@ -1340,8 +1456,7 @@ int gfdm_hip_channel_estimator_create(gfdm_hip_channel_estimator** out, int time
             int mode = g_jit.load();
             if (mode == 3) mode = (timeslots <= 16 || gfdm::jit_cached(timeslots, K, 2, gfdm::JIT_PART_EST)) ? 1 : 2;
             if (mode == 2) {
-                c->plan.jit_pending = std::make_shared<std::atomic<int>>(0);
-                gfdm::jit_prepare_async(timeslots, K, 2, 1u << gfdm::JIT_PART_EST, device, c->plan.jit_pending);
+                c->plan.jit_family.request_async(timeslots, K, 2, 1u << gfdm::JIT_PART_EST, device);
             } else if (gfdm::jit_prepare_estimate(timeslots, K, why)) {
                 c->plan.family = gfdm::FAMILY_ROWLANE_JIT;
             }
@@ -1417,10 +1532,7 @@ int gfdm_hip_channel_estimator_prepare_for_zf_device(gfdm_hip_channel_estimator*
                                                      int64_t nframes, void* stream)
 {
     if (!c) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return run_device(c->plan, transformed_frame, frame_estimate, nframes, [&]() {
-        return gfdm::launch_prepare_for_zf(static_cast<cf*>(transformed_frame), static_cast<const cf*>(frame_estimate),
-                                           nframes * c->ep.M * c->ep.K, static_cast<hipStream_t>(stream));
-    });
+    return run_device(c->plan, transformed_frame, frame_estimate, nullptr, nframes, stream, zf_op(c));
 }
 
 int gfdm_hip_channel_estimator_prepare_for_zf_host(gfdm_hip_channel_estimator* c, float* transformed_frame, const float* frame_estimate,
@@ -1429,9 +1541,7 @@ int gfdm_hip_channel_estimator_prepare_for_zf_host(gfdm_hip_channel_estimator* c
     if (!c) return fail(GFDM_HIP_EINVAL, "NULL handle");
     if (nframes < 0) return fail(GFDM_HIP_EINVAL, "negative frame count");
     const size_t n = (size_t)c->ep.M * c->ep.K;
-    return run_host_sized(c->plan, transformed_frame, n, frame_estimate, n, nullptr, 0, 0, nframes, [&](cf* o, const cf* i, const cf*, int64_t nf, hipStream_t s) {
-        return status_of(gfdm::launch_prepare_for_zf(o, i, nf * (int64_t)n, s));
-    });
+    return run_host_sized(c->plan, transformed_frame, n, frame_estimate, n, nullptr, 0, 0, nframes, zf_op(c));
 }
 
 int gfdm_hip_channel_estimator_estimate_snr_device(gfdm_hip_channel_estimator* c, float* snr_lin, float* cnrs, const void* rx_preamble,
@@ -1439,8 +1549,8 @@ int gfdm_hip_channel_estimator_estimate_snr_device(gfdm_hip_channel_estimator* c
 {
     if (!c) return fail(GFDM_HIP_EINVAL, "NULL handle");
     if (!cnrs) return fail(GFDM_HIP_EINVAL, "NULL buffer");
-    return run_device(c->plan, snr_lin, rx_preamble, nframes, [&]() {
-        return gfdm::launch_estimate_snr(c->ep, snr_lin, cnrs, static_cast<const cf*>(rx_preamble), nframes, static_cast<hipStream_t>(stream));
+    return run_device(c->plan, snr_lin, rx_preamble, nullptr, nframes, stream, [&](cf*, const cf* pre, const cf*, int64_t nf, hipStream_t s) {
+        return gfdm::launch_estimate_snr(c->ep, snr_lin, cnrs, pre, nf, s);
     });
 }
 
@@ -1467,8 +1577,31 @@ int gfdm_hip_channel_estimator_estimate_snr_host(gfdm_hip_channel_estimator* c, 
 
 namespace {
 
-int est_attach(Plan& pl, const gfdm_hip_channel_estimator*& slot, const gfdm_hip_channel_estimator* c)
+// One part of a run-time instantiated shape at set_channel_estimator: load it now rather than in the first call -- in the foreground when
+// that is quick (cached, few timeslots, or gfdm_hip_set_jit(1)) or the generic family cannot serve the shape, else on the background pool,
+// the calls that launch the part running on the generic family until it is there (a handle whose other parts came from gfdm_hip_precompile
+// must not block for a compile here).  `required`: the part of the *_estimated_* calls -- a foreground build is made whatever was asked
+// for earlier, and its failure fails the attach.  The other part (demodulate_bursts) is asked for once, and whatever happens to it -- still
+// compiling, failed -- is recorded in its state alone: attaching succeeds.
+int est_attach_part(Plan& pl, JitPart& part, int which, bool required)
 {
+    const int M = pl.dp.M, K = pl.dp.K, L = pl.dp.L;
+    if (!required && part.poll() != JitPart::NOT_REQUESTED) return GFDM_HIP_OK;
+    if (g_jit.load() == 1 || M <= 16 || gfdm::jit_cached(M, K, L, which) || !gfdm::generic_supports(M, K, false)) {
+        std::string why;
+        DeviceGuard guard(pl.device);
+        if (part.build_now(M, K, L, 1u << which, why)) return GFDM_HIP_OK;
+        if (required) return fail(GFDM_HIP_EHIP, "run-time instantiation of the preamble-equalised receive kernels failed: " + why);
+        part.set_failed();
+    } else {
+        part.request_async(M, K, L, 1u << which, pl.device);
+    }
+    return GFDM_HIP_OK;
+}
+
+int est_attach(RxCore& rx, const gfdm_hip_channel_estimator* c)
+{
+    Plan& pl = rx.plan;
     if (c && (c->ep.M != pl.dp.M || c->ep.K != pl.dp.K)) {
         char buf[200];
         snprintf(buf, sizeof buf, "estimator is for timeslots %d x fft_len %d, the receiver for timeslots %d x subcarriers %d", c->ep.M, c->ep.K,
@@ -1477,169 +1610,128 @@ int est_attach(Plan& pl, const gfdm_hip_channel_estimator*& slot, const gfdm_hip
     }
     if (c && c->plan.device != pl.device) return fail(GFDM_HIP_EINVAL, "estimator and receiver live on different devices");
     if (c && pl.current_family() == gfdm::FAMILY_ROWLANE_JIT) {
-        // the preamble-equalised receive kernels of a run-time instantiated shape: load them now rather than in the first call -- in the
-        // foreground when that is quick (cached, few timeslots, or gfdm_hip_set_jit(1)), else on the background pool, the estimated calls running
-        // on the generic family until they are there (a handle whose other parts came from gfdm_hip_precompile must not block for a compile here)
-        const int M = pl.dp.M, K = pl.dp.K, L = pl.dp.L;
-        const int mode = g_jit.load();
-        if (mode == 1 || M <= 16 || gfdm::jit_cached(M, K, L, gfdm::JIT_PART_RX_PREAMBLE) || !gfdm::generic_supports(M, K, false)) {
-            std::string why;
-            DeviceGuard guard(pl.device);
-            if (!gfdm::jit_prepare(M, K, L, 1u << gfdm::JIT_PART_RX_PREAMBLE, why))
-                return fail(GFDM_HIP_EHIP, "run-time instantiation of the preamble-equalised receive kernels failed: " + why);
-            pl.jit_pre_pending.reset();
-        } else if (!pl.jit_pre_pending) {
-            pl.jit_pre_pending = std::make_shared<std::atomic<int>>(0);
-            gfdm::jit_prepare_async(M, K, L, 1u << gfdm::JIT_PART_RX_PREAMBLE, pl.device, pl.jit_pre_pending);
-        }
-        // ... and the kernels of demodulate_bursts (JIT_PART_RX_BURST), under a state of their own that only that call consults: whatever
-        // happens to this part -- still compiling, failed -- the *_estimated_* calls launch what they always launched, and attaching succeeds
-        if (!pl.jit_burst_ready && !pl.jit_burst_pending) {
-            if (mode == 1 || M <= 16 || gfdm::jit_cached(M, K, L, gfdm::JIT_PART_RX_BURST) || !gfdm::generic_supports(M, K, false)) {
-                std::string why;
-                DeviceGuard guard(pl.device);
-                if (gfdm::jit_prepare(M, K, L, 1u << gfdm::JIT_PART_RX_BURST, why)) pl.jit_burst_ready = true;
-                else pl.jit_burst_pending = std::make_shared<std::atomic<int>>(-1);      // failed: demodulate_bursts stays on the generic family
-            } else {
-                pl.jit_burst_pending = std::make_shared<std::atomic<int>>(0);
-                gfdm::jit_prepare_async(M, K, L, 1u << gfdm::JIT_PART_RX_BURST, pl.device, pl.jit_burst_pending);
-            }
-        }
+        int rc = est_attach_part(pl, pl.jit_pre, gfdm::JIT_PART_RX_PREAMBLE, true);
+        if (rc != GFDM_HIP_OK) return rc;
+        (void)est_attach_part(pl, pl.jit_burst, gfdm::JIT_PART_RX_BURST, false);
     }
-    slot = c;
+    rx.est = c;
     return GFDM_HIP_OK;
 }
 
 // I/O of one estimated call: the frame configuration if there is one, plain blocks otherwise
-int est_call_io(const FrameIo& f, const Plan& pl, const gfdm_hip_channel_estimator* c, int preamble_stride, int noutput_size, gfdm::RxIo& io,
-                gfdm::EstPlan& ep)
+int est_call_io(const RxCore& rx, int preamble_stride, int noutput_size, gfdm::RxIo& io, gfdm::EstPlan& ep)
 {
-    if (!c) return fail(GFDM_HIP_EINVAL, "set_channel_estimator has not been called on this handle");
+    const Plan& pl = rx.plan;
+    if (!rx.est) return fail(GFDM_HIP_EINVAL, "set_channel_estimator has not been called on this handle");
     if (preamble_stride != 0 && preamble_stride < 2 * pl.dp.K) return fail(GFDM_HIP_EINVAL, "preamble_stride must be 0 (packed) or at least 2 * fft_len");
-    if (f.configured) {
-        int rc = frame_io_for_call(f, pl, noutput_size, io);
+    if (rx.frames.configured) {
+        int rc = frame_io_for_call(rx.frames, pl, noutput_size, io);
         if (rc != GFDM_HIP_OK) return rc;
     } else {
         if (noutput_size > 0 && noutput_size != pl.dp.N) return fail(GFDM_HIP_EINVAL, "noutput_size needs configure_frames with a subcarrier map");
         io.in_stride = pl.dp.N;
         io.nout = pl.dp.N;
     }
-    ep = c->ep;
+    ep = rx.est->ep;
     ep.pre_stride = preamble_stride ? preamble_stride : 2 * pl.dp.K;
     return GFDM_HIP_OK;
 }
 
-template <typename DeviceCall>
-int est_call_host(Plan& pl, const gfdm::RxIo& io, const gfdm::EstPlan& ep, float* out, const float* in, const float* rx_preamble, int64_t nblocks,
-                  DeviceCall call)
+int rx_estimated_device(RxCore& rx, void* out, const void* in, const void* rx_preamble, int preamble_stride, int noutput_size, int64_t nblocks,
+                        void* stream)
 {
+    if (!rx_preamble) return fail(GFDM_HIP_EINVAL, "NULL buffer");
+    gfdm::IcParams ic = rx.ic;
+    gfdm::EstPlan ep;
+    int rc = est_call_io(rx, preamble_stride, noutput_size, ic.io, ep);
+    if (rc != GFDM_HIP_OK) return rc;
+    return run_device(rx.plan, out, in, rx_preamble, nblocks, stream, rx_op(rx, ic, rx.mode, &ep));
+}
+
+int rx_estimated_host(RxCore& rx, float* out, const float* in, const float* rx_preamble, int preamble_stride, int noutput_size, int64_t nblocks)
+{
+    gfdm::IcParams ic = rx.ic;
+    gfdm::EstPlan ep;
+    int rc = est_call_io(rx, preamble_stride, noutput_size, ic.io, ep);
+    if (rc != GFDM_HIP_OK) return rc;
     if (nblocks < 0) return fail(GFDM_HIP_EINVAL, "negative block count");
     if (!rx_preamble) return fail(GFDM_HIP_EINVAL, "NULL buffer");
-    return run_host_sized(pl, out, (size_t)io.nout, in, (size_t)io.in_stride, rx_preamble, (size_t)ep.pre_stride, 2 * (size_t)ep.K, nblocks,
-                          [&](cf* o, const cf* i, const cf* e, int64_t nb, hipStream_t s) { return call(o, i, e, nb, (void*)s); });
+    return run_host_sized(rx.plan, out, (size_t)ic.io.nout, in, (size_t)ic.io.in_stride, rx_preamble, (size_t)ep.pre_stride, 2 * (size_t)ep.K, nblocks,
+                          rx_op(rx, ic, rx.mode, &ep));
+}
+
+int rx_io_layout(const RxCore& rx, int estimated, int noutput_size, int* n_in, int* n_out, int* est_fft_len)
+{
+    gfdm::RxIo io{};
+    int rc;
+    if (estimated) {
+        gfdm::EstPlan ep;
+        rc = est_call_io(rx, 0, noutput_size, io, ep);
+    } else {
+        rc = frame_io_for_call(rx.frames, rx.plan, noutput_size, io);
+    }
+    if (rc != GFDM_HIP_OK) return rc;
+    if (n_in) *n_in = io.in_stride;
+    if (n_out) *n_out = io.nout;
+    if (est_fft_len) *est_fft_len = rx.est ? rx.est->ep.K : 0;
+    return GFDM_HIP_OK;
 }
 
 }  // namespace
 
 extern "C" {
 
-namespace {
-int io_layout(const FrameIo& f, const Plan& pl, const gfdm_hip_channel_estimator* c, int estimated, int noutput_size, int* n_in, int* n_out,
-              int* est_fft_len)
-{
-    gfdm::RxIo io{};
-    int rc;
-    if (estimated) {
-        gfdm::EstPlan ep;
-        rc = est_call_io(f, pl, c, 0, noutput_size, io, ep);
-    } else {
-        rc = frame_io_for_call(f, pl, noutput_size, io);
-    }
-    if (rc != GFDM_HIP_OK) return rc;
-    if (n_in) *n_in = io.in_stride;
-    if (n_out) *n_out = io.nout;
-    if (est_fft_len) *est_fft_len = c ? c->ep.K : 0;
-    return GFDM_HIP_OK;
-}
-}  // namespace
-
 int gfdm_hip_receiver_io_layout(const gfdm_hip_receiver* r, int estimated, int noutput_size, int* n_in, int* n_out, int* est_fft_len)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return io_layout(r->frames, r->plan, r->est, estimated, noutput_size, n_in, n_out, est_fft_len);
+    return rx_io_layout(*r, estimated, noutput_size, n_in, n_out, est_fft_len);
 }
 
 int gfdm_hip_advanced_receiver_io_layout(const gfdm_hip_advanced_receiver* a, int estimated, int noutput_size, int* n_in, int* n_out,
                                          int* est_fft_len)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return io_layout(a->frames, a->plan, a->est, estimated, noutput_size, n_in, n_out, est_fft_len);
+    return rx_io_layout(*a, estimated, noutput_size, n_in, n_out, est_fft_len);
 }
 
 int gfdm_hip_receiver_set_channel_estimator(gfdm_hip_receiver* r, const gfdm_hip_channel_estimator* c)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return est_attach(r->plan, r->est, c);
+    return est_attach(*r, c);
 }
 
 int gfdm_hip_advanced_receiver_set_channel_estimator(gfdm_hip_advanced_receiver* a, const gfdm_hip_channel_estimator* c)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return est_attach(a->plan, a->est, c);
+    return est_attach(*a, c);
 }
 
 int gfdm_hip_receiver_demodulate_estimated_device(gfdm_hip_receiver* r, void* out, const void* in, const void* rx_preamble, int preamble_stride,
                                                   int noutput_size, int64_t nblocks, void* stream)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    if (!rx_preamble) return fail(GFDM_HIP_EINVAL, "NULL buffer");
-    gfdm::IcParams ic = kNoIc;
-    gfdm::EstPlan ep;
-    int rc = est_call_io(r->frames, r->plan, r->est, preamble_stride, noutput_size, ic.io, ep);
-    if (rc != GFDM_HIP_OK) return rc;
-    return run_device(r->plan, out, in, nblocks, [&]() {
-        return rx_launch(r->plan, ic, gfdm::RX_DEMOD, (cf*)out, (const cf*)in, (const cf*)rx_preamble, nblocks, (hipStream_t)stream, &ep);
-    });
+    return rx_estimated_device(*r, out, in, rx_preamble, preamble_stride, noutput_size, nblocks, stream);
 }
 
 int gfdm_hip_advanced_receiver_work_estimated_device(gfdm_hip_advanced_receiver* a, void* out, const void* in, const void* rx_preamble,
                                                      int preamble_stride, int noutput_size, int64_t nblocks, void* stream)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    if (!rx_preamble) return fail(GFDM_HIP_EINVAL, "NULL buffer");
-    gfdm::IcParams ic = a->ic;
-    gfdm::EstPlan ep;
-    int rc = est_call_io(a->frames, a->plan, a->est, preamble_stride, noutput_size, ic.io, ep);
-    if (rc != GFDM_HIP_OK) return rc;
-    return run_device(a->plan, out, in, nblocks, [&]() {
-        return rx_launch(a->plan, ic, gfdm::RX_IC, (cf*)out, (const cf*)in, (const cf*)rx_preamble, nblocks, (hipStream_t)stream, &ep);
-    });
+    return rx_estimated_device(*a, out, in, rx_preamble, preamble_stride, noutput_size, nblocks, stream);
 }
 
 int gfdm_hip_receiver_demodulate_estimated_host(gfdm_hip_receiver* r, float* out, const float* in, const float* rx_preamble, int preamble_stride,
                                                 int noutput_size, int64_t nblocks)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    gfdm::RxIo io{};
-    gfdm::EstPlan ep;
-    int rc = est_call_io(r->frames, r->plan, r->est, preamble_stride, noutput_size, io, ep);
-    if (rc != GFDM_HIP_OK) return rc;
-    return est_call_host(r->plan, io, ep, out, in, rx_preamble, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, void* s) {
-        return gfdm_hip_receiver_demodulate_estimated_device(r, o, i, e, preamble_stride, noutput_size, nb, s);
-    });
+    return rx_estimated_host(*r, out, in, rx_preamble, preamble_stride, noutput_size, nblocks);
 }
 
 int gfdm_hip_advanced_receiver_work_estimated_host(gfdm_hip_advanced_receiver* a, float* out, const float* in, const float* rx_preamble,
                                                    int preamble_stride, int noutput_size, int64_t nblocks)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    gfdm::RxIo io{};
-    gfdm::EstPlan ep;
-    int rc = est_call_io(a->frames, a->plan, a->est, preamble_stride, noutput_size, io, ep);
-    if (rc != GFDM_HIP_OK) return rc;
-    return est_call_host(a->plan, io, ep, out, in, rx_preamble, nblocks, [&](cf* o, const cf* i, const cf* e, int64_t nb, void* s) {
-        return gfdm_hip_advanced_receiver_work_estimated_device(a, o, i, e, preamble_stride, noutput_size, nb, s);
-    });
+    return rx_estimated_host(*a, out, in, rx_preamble, preamble_stride, noutput_size, nblocks);
 }
 
 }  // extern "C"
@@ -1649,9 +1741,12 @@ int gfdm_hip_advanced_receiver_work_estimated_host(gfdm_hip_advanced_receiver* a
 namespace {
 
 // arguments of one demodulate_bursts call -> RxIo and estimator plan + BurstIo of the launch (the contract is in include/gfdm_hip.h)
-int bursts_call_io(const FrameIo& f, const Plan& pl, const gfdm_hip_channel_estimator* c, int64_t stream_len, int backoff, int preamble_offset,
-                   int noutput_size, int64_t n_bursts, gfdm::RxIo& io, gfdm::BurstEstPlan& ep)
+int bursts_call_io(const RxCore& rx, int64_t stream_len, int backoff, int preamble_offset, int noutput_size, int64_t n_bursts, gfdm::RxIo& io,
+                   gfdm::BurstEstPlan& ep)
 {
+    const FrameIo& f = rx.frames;
+    const Plan& pl = rx.plan;
+    const gfdm_hip_channel_estimator* c = rx.est;
     if (!f.configured) return fail(GFDM_HIP_EINVAL, "configure_frames has not been called on this handle");
     if (!c) return fail(GFDM_HIP_EINVAL, "set_channel_estimator has not been called on this handle");
     if (preamble_offset < 0 || (int64_t)preamble_offset + 2 * pl.dp.K > f.io.in_stride)
@@ -1670,12 +1765,12 @@ int bursts_call_io(const FrameIo& f, const Plan& pl, const gfdm_hip_channel_esti
     return GFDM_HIP_OK;
 }
 
-int bursts_device(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, gfdm::IcParams ic, int mode, void* out, const void* samples, int fmt,
-                  int64_t stream_len, const void* offsets, const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction,
-                  int noutput_size, int64_t n_bursts, void* stream)
+int bursts_device(RxCore& rx, void* out, const void* samples, int fmt, int64_t stream_len, const void* offsets, const void* sc_rot, const void* count,
+                  int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
 {
+    gfdm::IcParams ic = rx.ic;
     gfdm::BurstEstPlan ep;
-    int rc = bursts_call_io(f, pl, c, stream_len, backoff, preamble_offset, noutput_size, n_bursts, ic.io, ep);
+    int rc = bursts_call_io(rx, stream_len, backoff, preamble_offset, noutput_size, n_bursts, ic.io, ep);
     if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
     if (!out || !offsets || (!samples && stream_len > 0)) return fail(GFDM_HIP_EINVAL, "NULL buffer");
     if (n_bursts > 0x7fffffff) return fail(GFDM_HIP_EINVAL, "more than 2^31 - 1 bursts per call");
@@ -1684,20 +1779,20 @@ int bursts_device(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* 
     ep.io.off = static_cast<const int64_t*>(offsets);
     ep.io.rot = cfo_correction ? static_cast<const cf*>(sc_rot) : nullptr;
     ep.io.count = static_cast<const int64_t*>(count);
-    DeviceGuard guard(pl.device);
+    DeviceGuard guard(rx.plan.device);
     if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return status_of(rx_launch(pl, ic, mode, static_cast<cf*>(out), nullptr, nullptr, n_bursts, static_cast<hipStream_t>(stream), &ep.est));
+    return status_of(rx_launch(rx.plan, ic, rx.mode, static_cast<cf*>(out), nullptr, nullptr, n_bursts, static_cast<hipStream_t>(stream), &ep.est));
 }
 
 // convenience, not a pipeline: capture (in the caller's format: an sc16 capture goes up as int16) and arrays to the device, ONE launch,
 // result back (the handle's private stream)
-int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c, const gfdm::IcParams& ic, int mode, float* out, const void* samples, int fmt,
-                int64_t stream_len, const int64_t* offsets, const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction,
-                int noutput_size, int64_t n_bursts)
+int bursts_host(RxCore& rx, float* out, const void* samples, int fmt, int64_t stream_len, const int64_t* offsets, const float* sc_rot, const int64_t* count,
+                int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
 {
+    Plan& pl = rx.plan;
     gfdm::RxIo io{};
     gfdm::BurstEstPlan ep;
-    int rc = bursts_call_io(f, pl, c, stream_len, backoff, preamble_offset, noutput_size, n_bursts, io, ep);
+    int rc = bursts_call_io(rx, stream_len, backoff, preamble_offset, noutput_size, n_bursts, io, ep);
     if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
     if (!out || !offsets || (!samples && stream_len > 0)) return fail(GFDM_HIP_EINVAL, "NULL buffer");
     DeviceGuard guard(pl.device);
@@ -1714,7 +1809,7 @@ int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c,
     GFDM_TRY(gfdm::upload(d_off, offsets, n * sizeof(int64_t), pl.stream));
     GFDM_TRY(gfdm::upload(d_cnt, count, sizeof(int64_t), pl.stream));
     GFDM_TRY(gfdm::upload(d_rot, sc_rot, n * sizeof(cf), pl.stream));
-    rc = bursts_device(pl, f, c, ic, mode, d_out.p, d_s.p, fmt, stream_len, d_off, sc_rot ? d_rot : nullptr, count ? d_cnt : nullptr, backoff, preamble_offset,
+    rc = bursts_device(rx, d_out.p, d_s.p, fmt, stream_len, d_off, sc_rot ? d_rot : nullptr, count ? d_cnt : nullptr, backoff, preamble_offset,
                        cfo_correction, noutput_size, n_bursts, pl.stream);
     if (rc != GFDM_HIP_OK) return rc;
     GFDM_TRY(gfdm::download(out, d_out.p, out_bytes, pl.stream));
@@ -1726,69 +1821,61 @@ int bursts_host(Plan& pl, const FrameIo& f, const gfdm_hip_channel_estimator* c,
 
 extern "C" {
 
-/* the four calls and their sc16 twins (include/gfdm_hip.h): thin wrappers over bursts_device / bursts_host, which take the sample format */
+/* the four calls and their sc16 twins (include/gfdm_hip.h): forwards to bursts_device / bursts_host, which take the sample format */
 int gfdm_hip_receiver_demodulate_bursts_device(gfdm_hip_receiver* r, void* out, const void* samples, int64_t stream_len, const void* offsets,
     const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_device(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
-                         cfo_correction, noutput_size, n_bursts, stream);
+    return bursts_device(*r, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset, cfo_correction, noutput_size, n_bursts, stream);
 }
 
 int gfdm_hip_receiver_demodulate_bursts_host(gfdm_hip_receiver* r, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
     const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_host(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
-                       cfo_correction, noutput_size, n_bursts);
+    return bursts_host(*r, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset, cfo_correction, noutput_size, n_bursts);
 }
 
 int gfdm_hip_advanced_receiver_work_bursts_device(gfdm_hip_advanced_receiver* a, void* out, const void* samples, int64_t stream_len, const void* offsets,
     const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_device(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
-                         cfo_correction, noutput_size, n_bursts, stream);
+    return bursts_device(*a, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset, cfo_correction, noutput_size, n_bursts, stream);
 }
 
 int gfdm_hip_advanced_receiver_work_bursts_host(gfdm_hip_advanced_receiver* a, float* out, const float* samples, int64_t stream_len, const int64_t* offsets,
     const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_host(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
-                       cfo_correction, noutput_size, n_bursts);
+    return bursts_host(*a, out, samples, gfdm::SAMPLES_CF32, stream_len, offsets, sc_rot, count, backoff, preamble_offset, cfo_correction, noutput_size, n_bursts);
 }
 
 int gfdm_hip_receiver_demodulate_bursts_sc16_device(gfdm_hip_receiver* r, void* out, const void* samples, int64_t stream_len, const void* offsets,
     const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_device(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
-                         cfo_correction, noutput_size, n_bursts, stream);
+    return bursts_device(*r, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset, cfo_correction, noutput_size, n_bursts, stream);
 }
 
 int gfdm_hip_receiver_demodulate_bursts_sc16_host(gfdm_hip_receiver* r, float* out, const int16_t* samples, int64_t stream_len, const int64_t* offsets,
     const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
 {
     if (!r) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_host(r->plan, r->frames, r->est, kNoIc, gfdm::RX_DEMOD, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
-                       cfo_correction, noutput_size, n_bursts);
+    return bursts_host(*r, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset, cfo_correction, noutput_size, n_bursts);
 }
 
 int gfdm_hip_advanced_receiver_work_bursts_sc16_device(gfdm_hip_advanced_receiver* a, void* out, const void* samples, int64_t stream_len, const void* offsets,
     const void* sc_rot, const void* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts, void* stream)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_device(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
-                         cfo_correction, noutput_size, n_bursts, stream);
+    return bursts_device(*a, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset, cfo_correction, noutput_size, n_bursts, stream);
 }
 
 int gfdm_hip_advanced_receiver_work_bursts_sc16_host(gfdm_hip_advanced_receiver* a, float* out, const int16_t* samples, int64_t stream_len, const int64_t* offsets,
     const float* sc_rot, const int64_t* count, int backoff, int preamble_offset, int cfo_correction, int noutput_size, int64_t n_bursts)
 {
     if (!a) return fail(GFDM_HIP_EINVAL, "NULL handle");
-    return bursts_host(a->plan, a->frames, a->est, a->ic, gfdm::RX_IC, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset,
-                       cfo_correction, noutput_size, n_bursts);
+    return bursts_host(*a, out, samples, gfdm::SAMPLES_SC16, stream_len, offsets, sc_rot, count, backoff, preamble_offset, cfo_correction, noutput_size, n_bursts);
 }
 
 }  // extern "C"

@@ -493,9 +493,6 @@ def set_dft_matrix_cores(mode):
 class _Kernel:
     """Shared plumbing: host (numpy) and device (torch) batched calls."""
     _destroy = None
-    _frames_prefix = None          # C-ABI name stem of the *_frames_* entry points (receivers only)
-    _configure_frames = None
-    _io_layout = None
     _dev = 0                       # GPU the handle was created on: every tensor and the stream of a call must belong to it
 
     def _dp(self, t, n_elems, what):
@@ -503,126 +500,6 @@ class _Kernel:
 
     def _sp(self, stream):
         return _stream_ptr(stream, self._dev)
-
-    def _layout(self, estimated, nout_arg):
-        """(n_in, n_out, estimator fft_len) of one frames / estimated call, asked from the library (gfdm_hip_*_io_layout): it alone
-        knows what its kernels write for this configuration, so no output buffer is ever sized from Python-side bookkeeping."""
-        n_in, n_out, fft_len = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        _check(getattr(lib(), self._io_layout)(self._h, int(estimated), int(nout_arg), ctypes.byref(n_in), ctypes.byref(n_out), ctypes.byref(fft_len)))
-        return n_in.value, n_out.value, fft_len.value
-
-    # ---- raw frames in, demapped symbols out (SURVEY.md section 8f row 2) ----
-    def configure_frames(self, frame_len, cp_len, subcarrier_map=None, per_timeslot=True):
-        """Declare the frame layout once: frames of frame_len samples whose block starts cp_len samples in; with a
-        subcarrier_map only the active subcarriers' symbols are emitted, in resource-mapper order."""
-        smap = np.ascontiguousarray([] if subcarrier_map is None else subcarrier_map, dtype=np.int32)
-        fn = getattr(lib(), self._configure_frames)
-        _check(fn(self._h, int(frame_len), int(cp_len), smap.ctypes.data if smap.size else None, smap.size, int(bool(per_timeslot))))
-
-    def demodulate_frames(self, frames, f_eq=None, noutput_size=None, out=None, stream=None):
-        """frames: nframes * frame_len samples; returns (nframes, noutput_size) symbols (all active symbols by default)."""
-        L = lib()
-        nout_arg = -1 if noutput_size is None else int(noutput_size)
-        frame_len, nout, _ = self._layout(False, nout_arg)
-        N = self.block_size()
-        if _is_tensor(frames):
-            import torch
-            if frames.numel() % frame_len:
-                raise RuntimeError("frames size(%d) MUST be a multiple of frame_len(%d)!" % (frames.numel(), frame_len))
-            nb = frames.numel() // frame_len
-            out = torch.empty(nb, nout, dtype=torch.complex64, device=frames.device) if out is None else out
-            feq = None if f_eq is None else self._dp(f_eq, nb * N, "f_eq")
-            _check(getattr(L, self._frames_prefix + "_device")(self._h, self._dp(out, nb * nout, "out"), self._dp(frames, nb * frame_len, "frames"),
-                                                              feq, nout_arg, nb, self._sp(stream)))
-            return out
-        x = _c64(frames)
-        if x.size % frame_len:
-            raise RuntimeError("frames size(%d) MUST be a multiple of frame_len(%d)!" % (x.size, frame_len))
-        nb = x.size // frame_len
-        e = None if f_eq is None else _c64(f_eq)
-        if e is not None and e.size != nb * N:
-            raise RuntimeError("Channel vector size(%d) MUST be equal to nframes * block_size(%d)!" % (e.size, nb * N))
-        res = np.empty((nb, nout), np.complex64)
-        _check(getattr(L, self._frames_prefix + "_host")(self._h, res.ctypes.data, x.ctypes.data, None if e is None else e.ctypes.data, nout_arg, nb))
-        return res
-
-    # ---- channel estimator fused in front of the receiver (SURVEY.md section 8f row 3) ----
-    def set_channel_estimator(self, estimator):
-        """Attach a ChannelEstimator (or None): demodulate_estimated then derives the equaliser from each block's received preamble."""
-        _check(getattr(lib(), self._set_estimator)(self._h, None if estimator is None else estimator._h))
-        self._estimator = estimator                    # keeps the handle alive
-
-    def demodulate_estimated(self, x, rx_preamble, preamble_stride=0, noutput_size=None, out=None, stream=None):
-        """x: blocks (frames when configure_frames was called); rx_preamble: the received core preamble of every block, preamble b at
-        b * preamble_stride (0 = packed, 2 * subcarriers).  Equals estimate_frame + demodulate_equalize, in one kernel."""
-        L = lib()
-        if getattr(self, "_estimator", None) is None:
-            raise ValueError("set_channel_estimator has not been called on this handle")
-        nout_arg = -1 if noutput_size is None else int(noutput_size)
-        n_in, nout, fft_len = self._layout(True, nout_arg)
-        stride = int(preamble_stride) if preamble_stride else 2 * fft_len
-        if _is_tensor(x):
-            import torch
-            if x.numel() % n_in:
-                raise RuntimeError("Input size(%d) MUST be a multiple of %d!" % (x.numel(), n_in))
-            nb = x.numel() // n_in
-            out = torch.empty(nb, nout, dtype=torch.complex64, device=x.device) if out is None else out
-            need = (nb - 1) * stride + 2 * fft_len if nb else 0
-            if rx_preamble.numel() < need:
-                raise RuntimeError("rx_preamble has %d elements, at least %d are needed" % (rx_preamble.numel(), need))
-            self._dp(rx_preamble, rx_preamble.numel(), "rx_preamble")
-            _check(getattr(L, self._estimated_prefix + "_device")(self._h, self._dp(out, nb * nout, "out"), self._dp(x, nb * n_in, "in"),
-                                                                 rx_preamble.data_ptr(), int(preamble_stride), nout_arg, nb, self._sp(stream)))
-            return out
-        a = _c64(x)
-        if a.size % n_in:
-            raise RuntimeError("Input size(%d) MUST be a multiple of %d!" % (a.size, n_in))
-        nb = a.size // n_in
-        pre = _c64(rx_preamble)
-        need = (nb - 1) * stride + 2 * fft_len if nb else 0
-        if pre.size < need:
-            raise RuntimeError("rx_preamble size(%d) MUST be at least %d!" % (pre.size, need))
-        res = np.empty((nb, nout), np.complex64)
-        _check(getattr(L, self._estimated_prefix + "_host")(self._h, res.ctypes.data, a.ctypes.data, pre.ctypes.data, int(preamble_stride), nout_arg, nb))
-        return res
-
-    def demodulate_bursts(self, samples, offsets, sc_rot=None, count=None, backoff=0, preamble_offset=0, cfo_correction=True, noutput_size=None,
-                          out=None, stream=None):
-        """The bursts at `offsets` of the capture `samples`, demodulated straight from it: BurstExtractor.extract (offset - backoff, zero
-        outside the capture, CFO rotation by sc_rot) as the load stage of demodulate_estimated, preamble at preamble_offset of each burst.
-        Needs configure_frames and set_channel_estimator.  count (one int64, e.g. detect's): rows from count on are zeros.
-        r = sync.detect(...) feeds it as demodulate_bursts(samples, r["frame_start"], r["sc_rot"], r["count"], ...).
-        Torch device tensors run the device entry point (no allocation beyond `out`, no synchronisation), numpy arrays the host one.
-        An int16 capture, shape (n, 2) or (2n,), is read as sc16 (the *_sc16_* entry points): bit-equal to the call on from_sc16(samples)."""
-        sptr, slen, fmt, _keep = _capture(samples, self._dev)
-        L = lib()
-        if getattr(self, "_estimator", None) is None:
-            raise ValueError("set_channel_estimator has not been called on this handle")
-        nout_arg = -1 if noutput_size is None else int(noutput_size)
-        _, nout, _ = self._layout(True, nout_arg)
-        args = (int(backoff), int(preamble_offset), int(bool(cfo_correction)), nout_arg)
-        if _is_tensor(samples):
-            import torch
-            n = offsets.numel()
-            out = torch.empty(n, nout, dtype=torch.complex64, device=samples.device) if out is None else out
-            rp = None if sc_rot is None else _dev_arg(sc_rot, torch.complex64, n, "sc_rot", self._dev)
-            cp = None if count is None else _dev_arg(count, torch.int64, 1, "count", self._dev)
-            _check(getattr(L, self._bursts_prefix + fmt + "_device")(self._h, self._dp(out, n * nout, "out"), sptr, slen,
-                                                                    _dev_arg(offsets, torch.int64, n, "offsets", self._dev), rp, cp, *args, n,
-                                                                    self._sp(stream)))
-            return out
-        off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
-        n = off.size
-        rot = None if sc_rot is None else _c64(sc_rot).ravel()
-        if rot is not None and rot.size != n:
-            raise RuntimeError("sc_rot has %d elements, expected %d" % (rot.size, n))
-        cnt = None if count is None else np.ascontiguousarray(count, dtype=np.int64).ravel()
-        if cnt is not None and cnt.size != 1:
-            raise RuntimeError("count has %d elements, expected 1" % cnt.size)
-        res = np.empty((n, nout), np.complex64)
-        _check(getattr(L, self._bursts_prefix + fmt + "_host")(self._h, res.ctypes.data, sptr, slen, off.ctypes.data,
-                                                              None if rot is None else rot.ctypes.data, None if cnt is None else cnt.ctypes.data, *args, n))
-        return res
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -669,6 +546,138 @@ class _Kernel:
         return out
 
 
+class _Receiver(_Kernel):
+    """What Demodulator and AdvancedReceiver share: frames in / demapped symbols out, the fused channel estimator, bursts straight from a
+    capture.  The C-ABI names are <_stem>_<name> for the settings and <_stem>_<_verb>_<call kind>[_sc16]_{host,device} for the calls."""
+    _stem = None                   # "gfdm_hip_receiver" | "gfdm_hip_advanced_receiver"
+    _verb = None                   # "demodulate" | "work"
+
+    def _fn(self, name):
+        return getattr(lib(), self._stem + "_" + name)
+
+    @property
+    def _bursts_prefix(self):
+        return "%s_%s_bursts" % (self._stem, self._verb)
+
+    def _layout(self, estimated, nout_arg):
+        """(n_in, n_out, estimator fft_len) of one frames / estimated call, asked from the library (gfdm_hip_*_io_layout): it alone
+        knows what its kernels write for this configuration, so no output buffer is ever sized from Python-side bookkeeping."""
+        n_in, n_out, fft_len = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _check(self._fn("io_layout")(self._h, int(estimated), int(nout_arg), ctypes.byref(n_in), ctypes.byref(n_out), ctypes.byref(fft_len)))
+        return n_in.value, n_out.value, fft_len.value
+
+    # ---- raw frames in, demapped symbols out (SURVEY.md section 8f row 2) ----
+    def configure_frames(self, frame_len, cp_len, subcarrier_map=None, per_timeslot=True):
+        """Declare the frame layout once: frames of frame_len samples whose block starts cp_len samples in; with a
+        subcarrier_map only the active subcarriers' symbols are emitted, in resource-mapper order."""
+        smap = np.ascontiguousarray([] if subcarrier_map is None else subcarrier_map, dtype=np.int32)
+        fn = self._fn("configure_frames")
+        _check(fn(self._h, int(frame_len), int(cp_len), smap.ctypes.data if smap.size else None, smap.size, int(bool(per_timeslot))))
+
+    def demodulate_frames(self, frames, f_eq=None, noutput_size=None, out=None, stream=None):
+        """frames: nframes * frame_len samples; returns (nframes, noutput_size) symbols (all active symbols by default)."""
+        nout_arg = -1 if noutput_size is None else int(noutput_size)
+        frame_len, nout, _ = self._layout(False, nout_arg)
+        N = self.block_size()
+        if _is_tensor(frames):
+            import torch
+            if frames.numel() % frame_len:
+                raise RuntimeError("frames size(%d) MUST be a multiple of frame_len(%d)!" % (frames.numel(), frame_len))
+            nb = frames.numel() // frame_len
+            out = torch.empty(nb, nout, dtype=torch.complex64, device=frames.device) if out is None else out
+            feq = None if f_eq is None else self._dp(f_eq, nb * N, "f_eq")
+            _check(self._fn(self._verb + "_frames_device")(self._h, self._dp(out, nb * nout, "out"), self._dp(frames, nb * frame_len, "frames"),
+                                                        feq, nout_arg, nb, self._sp(stream)))
+            return out
+        x = _c64(frames)
+        if x.size % frame_len:
+            raise RuntimeError("frames size(%d) MUST be a multiple of frame_len(%d)!" % (x.size, frame_len))
+        nb = x.size // frame_len
+        e = None if f_eq is None else _c64(f_eq)
+        if e is not None and e.size != nb * N:
+            raise RuntimeError("Channel vector size(%d) MUST be equal to nframes * block_size(%d)!" % (e.size, nb * N))
+        res = np.empty((nb, nout), np.complex64)
+        _check(self._fn(self._verb + "_frames_host")(self._h, res.ctypes.data, x.ctypes.data, None if e is None else e.ctypes.data, nout_arg, nb))
+        return res
+
+    # ---- channel estimator fused in front of the receiver (SURVEY.md section 8f row 3) ----
+    def set_channel_estimator(self, estimator):
+        """Attach a ChannelEstimator (or None): demodulate_estimated then derives the equaliser from each block's received preamble."""
+        _check(self._fn("set_channel_estimator")(self._h, None if estimator is None else estimator._h))
+        self._estimator = estimator                    # keeps the handle alive
+
+    def demodulate_estimated(self, x, rx_preamble, preamble_stride=0, noutput_size=None, out=None, stream=None):
+        """x: blocks (frames when configure_frames was called); rx_preamble: the received core preamble of every block, preamble b at
+        b * preamble_stride (0 = packed, 2 * subcarriers).  Equals estimate_frame + demodulate_equalize, in one kernel."""
+        if getattr(self, "_estimator", None) is None:
+            raise ValueError("set_channel_estimator has not been called on this handle")
+        nout_arg = -1 if noutput_size is None else int(noutput_size)
+        n_in, nout, fft_len = self._layout(True, nout_arg)
+        stride = int(preamble_stride) if preamble_stride else 2 * fft_len
+        if _is_tensor(x):
+            import torch
+            if x.numel() % n_in:
+                raise RuntimeError("Input size(%d) MUST be a multiple of %d!" % (x.numel(), n_in))
+            nb = x.numel() // n_in
+            out = torch.empty(nb, nout, dtype=torch.complex64, device=x.device) if out is None else out
+            need = (nb - 1) * stride + 2 * fft_len if nb else 0
+            if rx_preamble.numel() < need:
+                raise RuntimeError("rx_preamble has %d elements, at least %d are needed" % (rx_preamble.numel(), need))
+            self._dp(rx_preamble, rx_preamble.numel(), "rx_preamble")
+            _check(self._fn(self._verb + "_estimated_device")(self._h, self._dp(out, nb * nout, "out"), self._dp(x, nb * n_in, "in"),
+                                                              rx_preamble.data_ptr(), int(preamble_stride), nout_arg, nb, self._sp(stream)))
+            return out
+        a = _c64(x)
+        if a.size % n_in:
+            raise RuntimeError("Input size(%d) MUST be a multiple of %d!" % (a.size, n_in))
+        nb = a.size // n_in
+        pre = _c64(rx_preamble)
+        need = (nb - 1) * stride + 2 * fft_len if nb else 0
+        if pre.size < need:
+            raise RuntimeError("rx_preamble size(%d) MUST be at least %d!" % (pre.size, need))
+        res = np.empty((nb, nout), np.complex64)
+        _check(self._fn(self._verb + "_estimated_host")(self._h, res.ctypes.data, a.ctypes.data, pre.ctypes.data, int(preamble_stride), nout_arg, nb))
+        return res
+
+    def demodulate_bursts(self, samples, offsets, sc_rot=None, count=None, backoff=0, preamble_offset=0, cfo_correction=True, noutput_size=None,
+                          out=None, stream=None):
+        """The bursts at `offsets` of the capture `samples`, demodulated straight from it: BurstExtractor.extract (offset - backoff, zero
+        outside the capture, CFO rotation by sc_rot) as the load stage of demodulate_estimated, preamble at preamble_offset of each burst.
+        Needs configure_frames and set_channel_estimator.  count (one int64, e.g. detect's): rows from count on are zeros.
+        r = sync.detect(...) feeds it as demodulate_bursts(samples, r["frame_start"], r["sc_rot"], r["count"], ...).
+        Torch device tensors run the device entry point (no allocation beyond `out`, no synchronisation), numpy arrays the host one.
+        An int16 capture, shape (n, 2) or (2n,), is read as sc16 (the *_sc16_* entry points): bit-equal to the call on from_sc16(samples)."""
+        sptr, slen, fmt, _keep = _capture(samples, self._dev)
+        L = lib()
+        if getattr(self, "_estimator", None) is None:
+            raise ValueError("set_channel_estimator has not been called on this handle")
+        nout_arg = -1 if noutput_size is None else int(noutput_size)
+        _, nout, _ = self._layout(True, nout_arg)
+        args = (int(backoff), int(preamble_offset), int(bool(cfo_correction)), nout_arg)
+        if _is_tensor(samples):
+            import torch
+            n = offsets.numel()
+            out = torch.empty(n, nout, dtype=torch.complex64, device=samples.device) if out is None else out
+            rp = None if sc_rot is None else _dev_arg(sc_rot, torch.complex64, n, "sc_rot", self._dev)
+            cp = None if count is None else _dev_arg(count, torch.int64, 1, "count", self._dev)
+            _check(getattr(L, self._bursts_prefix + fmt + "_device")(self._h, self._dp(out, n * nout, "out"), sptr, slen,
+                                                                    _dev_arg(offsets, torch.int64, n, "offsets", self._dev), rp, cp, *args, n,
+                                                                    self._sp(stream)))
+            return out
+        off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+        n = off.size
+        rot = None if sc_rot is None else _c64(sc_rot).ravel()
+        if rot is not None and rot.size != n:
+            raise RuntimeError("sc_rot has %d elements, expected %d" % (rot.size, n))
+        cnt = None if count is None else np.ascontiguousarray(count, dtype=np.int64).ravel()
+        if cnt is not None and cnt.size != 1:
+            raise RuntimeError("count has %d elements, expected 1" % cnt.size)
+        res = np.empty((n, nout), np.complex64)
+        _check(getattr(L, self._bursts_prefix + fmt + "_host")(self._h, res.ctypes.data, sptr, slen, off.ctypes.data,
+                                                              None if rot is None else rot.ctypes.data, None if cnt is None else cnt.ctypes.data, *args, n))
+        return res
+
+
 def _taps_arg(taps):
     t = _c64(np.asarray(taps).ravel())
     return t, t.ctypes.data, t.size
@@ -708,15 +717,10 @@ class Modulator(_Kernel):
         return self._host(lib().gfdm_hip_modulator_work_host, x, out=out)
 
 
-class Demodulator(_Kernel):
+class Demodulator(_Receiver):
     """gr::gfdm::receiver_kernel_cc (include/gfdm/receiver_kernel_cc.h:52-89) on the GPU."""
     _destroy = "gfdm_hip_receiver_destroy"
-    _frames_prefix = "gfdm_hip_receiver_demodulate_frames"
-    _configure_frames = "gfdm_hip_receiver_configure_frames"
-    _io_layout = "gfdm_hip_receiver_io_layout"
-    _estimated_prefix = "gfdm_hip_receiver_demodulate_estimated"
-    _bursts_prefix = "gfdm_hip_receiver_demodulate_bursts"
-    _set_estimator = "gfdm_hip_receiver_set_channel_estimator"
+    _stem, _verb = "gfdm_hip_receiver", "demodulate"
 
     def __init__(self, timeslots, subcarriers, overlap, taps, device=0):
         L = lib()
@@ -779,7 +783,7 @@ class Demodulator(_Kernel):
         return self._call("gfdm_hip_receiver_cancel_sc_interference", td, (fd,), out, stream)
 
 
-class AdvancedReceiver(_Kernel):
+class AdvancedReceiver(_Receiver):
     """gr::gfdm::advanced_receiver_kernel_cc (include/gfdm/advanced_receiver_kernel_cc.h:37-78) on the GPU.
 
     The reference takes a gr::digital::constellation_sptr; here the constellation is its points() array plus a
@@ -788,12 +792,7 @@ class AdvancedReceiver(_Kernel):
     matrix-core cancellation rounds); scaled or rotated points are decided by the nearest-point rule over the points as given, also when
     'qpsk' / 'bpsk' was asked for.  decision_rule() reports the rule the handle runs."""
     _destroy = "gfdm_hip_advanced_receiver_destroy"
-    _frames_prefix = "gfdm_hip_advanced_receiver_work_frames"
-    _configure_frames = "gfdm_hip_advanced_receiver_configure_frames"
-    _io_layout = "gfdm_hip_advanced_receiver_io_layout"
-    _estimated_prefix = "gfdm_hip_advanced_receiver_work_estimated"
-    _bursts_prefix = "gfdm_hip_advanced_receiver_work_bursts"
-    _set_estimator = "gfdm_hip_advanced_receiver_set_channel_estimator"
+    _stem, _verb = "gfdm_hip_advanced_receiver", "work"
 
     def __init__(self, timeslots, subcarriers, overlap, taps, subcarrier_map, ic_iter, constellation_points,
                  do_phase_compensation=0, decision="auto", device=0):

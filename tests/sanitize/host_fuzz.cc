@@ -578,6 +578,144 @@ void edge_cases(unsigned seed)
     printf("edge cases: undersized / foreign-GPU device operands refused, argument checks, both unknown-pointer conventions of the runtime\n");
 }
 
+// The states of the run-time instantiated parts as a handle walks through them (JitPart in gfdm_hip_api.hip: not requested, compiling, ready, failed), in order,
+// on both receiver kinds, shapes of more than 16 timeslots that no other section touches (nothing of them is cached), gfdm_hip_set_jit(2).  The loop-back kernels
+// add their family's tag to every output: which kernels a call launched, and that all of its chunks launched the same, is read from the result.
+struct WalkRx {
+    Shape s{};
+    gfdm_hip_receiver* rx = nullptr;
+    gfdm_hip_advanced_receiver* adv = nullptr;
+    gfdm_hip_channel_estimator* est = nullptr;
+    int ic_iter = 2;
+    WalkRx(const Shape& shape, bool advanced) : s(shape)
+    {
+        const std::vector<float> taps = taps_for(s);
+        std::vector<int> smap;
+        for (int k = 1; k < s.K; ++k) smap.push_back(k);
+        const float qpsk[8] = { -0.70710678f, -0.70710678f, 0.70710678f, -0.70710678f, -0.70710678f, 0.70710678f, 0.70710678f, 0.70710678f };
+        if (advanced)
+            CHECK(gfdm_hip_advanced_receiver_create(&adv, s.M, s.K, s.L, taps.data(), s.M * s.L, smap.data(), (int)smap.size(), ic_iter, qpsk, 4, GFDM_HIP_DECIDE_AUTO, 0, 0) == GFDM_HIP_OK,
+                  "advanced receiver M%d K%d", s.M, s.K);
+        else
+            CHECK(gfdm_hip_receiver_create(&rx, s.M, s.K, s.L, taps.data(), s.M * s.L, 0) == GFDM_HIP_OK, "receiver M%d K%d", s.M, s.K);
+        std::vector<float> pre((size_t)4 * s.K);
+        for (size_t i = 0; i < pre.size(); ++i) pre[i] = 1.f + (float)(i % 7);
+        CHECK(gfdm_hip_channel_estimator_create(&est, s.M, s.K, (s.K - 2) & ~1, 1, 1, pre.data(), 2 * s.K, 0) == GFDM_HIP_OK, "estimator M%d K%d", s.M, s.K);
+    }
+    ~WalkRx()
+    {
+        if (rx) gfdm_hip_receiver_destroy(rx);
+        if (adv) gfdm_hip_advanced_receiver_destroy(adv);
+        if (est) gfdm_hip_channel_estimator_destroy(est);
+    }
+    bool tuned_name() const { return strcmp(adv ? gfdm_hip_advanced_receiver_kernel_name(adv) : gfdm_hip_receiver_kernel_name(rx), "rowlane_jit") == 0; }
+    int attach() { return adv ? gfdm_hip_advanced_receiver_set_channel_estimator(adv, est) : gfdm_hip_receiver_set_channel_estimator(rx, est); }
+    // one host call of 13 blocks in five chunks, estimated (the preambles as third operand) or on plain blocks; returns the family tag ALL of its blocks carried
+    float call(bool estimated, unsigned seed, std::mt19937& rng)
+    {
+        const int N = s.M * s.K, ps = 2 * s.K, mode = adv ? 2 : 1, rounds = adv ? ic_iter : 0;
+        const int64_t nb = 13;
+        CHECK(gfdm_hip_set_host_pipeline(0, 3 * (int64_t)N * 8 + 5, 2, 1, 1) == GFDM_HIP_OK, "set_host_pipeline");
+        CHECK(hipSetDevice(0) == hipSuccess, "hipSetDevice");
+        Buf out, in0, in1;
+        in0.alloc(PAGEABLE, (size_t)nb * N * 8, rng); fill(in0, seed, nb * N);
+        in1.alloc(PAGEABLE, (size_t)nb * ps * 8, rng); fill(in1, seed ^ 0x4242, nb * ps);
+        out.alloc(PAGEABLE, (size_t)nb * N * 8, rng); poison(out, nb * N);
+        int rc;
+        if (estimated) rc = adv ? gfdm_hip_advanced_receiver_work_estimated_host(adv, out.p, in0.p, in1.p, 0, 0, nb) : gfdm_hip_receiver_demodulate_estimated_host(rx, out.p, in0.p, in1.p, 0, 0, nb);
+        else rc = adv ? gfdm_hip_advanced_receiver_work_host(adv, out.p, in0.p, nullptr, nb) : gfdm_hip_receiver_demodulate_host(rx, out.p, in0.p, nullptr, nb);
+        CHECK(rc == GFDM_HIP_OK, "%s call on M%d K%d returned %d", estimated ? "estimated" : "block", s.M, s.K, rc);
+        int64_t chunks = 0;
+        gfdm_hip_host_call_stats(&chunks, nullptr, nullptr, nullptr, nullptr, nullptr);
+        CHECK(chunks > 1, "the walk's calls are cut into chunks (%ld)", (long)chunks);
+        float tag = -1.f;
+        for (int64_t b = 0; b < nb; ++b)
+            for (int i = 0; i < N; ++i) {
+                const c2 sv = at(in0, b * N + i), ev = estimated ? at(in1, b * ps + (i % ps)) : c2{ 0.f, 0.f }, got = at(out, b * N + i);
+                if (b == 0 && i == 0) {
+                    for (float t : { loopback::kTagJit, loopback::kTagGeneric })
+                        if (same(got, loopback::rx_value(sv, ev, mode, rounds, t))) tag = t;
+                    CHECK(tag >= 0.f, "family tag of the first element: got (%g, %g)", got.x, got.y);
+                }
+                CHECK(same(got, loopback::rx_value(sv, ev, mode, rounds, tag)), "block %ld element %d does not carry the call's tag %g", (long)b, i, tag);
+            }
+        g_calls.fetch_add(1);
+        return tag;
+    }
+};
+
+void part_state_walk(unsigned seed)
+{
+    std::mt19937 rng(seed);
+    const double limit = 120.0;                                 // seconds a background build may take before the walk gives up
+    auto since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+    long generic_calls = 0, tuned_calls = 0;
+    loopback::set_compile_ms(40, 80);
+    for (int advanced = 0; advanced < 2; ++advanced) {
+        // (1) the family itself on the pool, the preamble-equalised kernels in the same job: generic while compiling, the first call that sees "ready" switches
+        //     handle and name, and from then on every call, estimated ones included (their part: not requested), launches the tuned kernels
+        {
+            (void)gfdm_hip_set_jit(2);
+            WalkRx w(Shape{ 19 + 2 * advanced, 32, 2, 2 }, advanced != 0);
+            CHECK(w.attach() == GFDM_HIP_OK, "set_channel_estimator while the family compiles");
+            const bool attached_generic = !w.tuned_name();
+            const auto t0 = std::chrono::steady_clock::now();
+            bool tuned = w.tuned_name();
+            while (!tuned) {
+                const float tag = w.call(true, (unsigned)rng(), rng);
+                tuned = w.tuned_name();
+                if (!tuned) CHECK(tag == loopback::kTagGeneric, "a call that left the handle on the generic family carried tag %g", tag);
+                (tag == loopback::kTagGeneric ? generic_calls : tuned_calls)++;
+                CHECK(since(t0) < limit, "family of M%d K%d not ready after %g s", w.s.M, w.s.K, limit);
+            }
+            for (int i = 0; i < 3; ++i) {
+                CHECK(w.call(false, (unsigned)rng(), rng) == loopback::kTagJit, "block call after the switch");
+                const float tag = w.call(true, (unsigned)rng(), rng);
+                if (attached_generic) CHECK(tag == loopback::kTagJit, "estimated call after the switch carried tag %g", tag);
+                CHECK(w.tuned_name(), "the name stays rowlane_jit");
+                (tag == loopback::kTagGeneric ? generic_calls : tuned_calls)++;
+            }
+        }
+        // (2) a handle that is on the tuned family before the estimator comes: the preamble-equalised kernels go to the pool (more than 16 timeslots, not cached),
+        //     the estimated calls run on the generic family until they are there and on the tuned kernels ever after; block calls are tuned throughout
+        {
+            (void)gfdm_hip_set_jit(1);
+            WalkRx w(Shape{ 23 + 2 * advanced, 16, 2, 2 }, advanced != 0);
+            CHECK(w.tuned_name(), "gfdm_hip_set_jit(1) builds in the constructor");
+            (void)gfdm_hip_set_jit(2);
+            CHECK(w.attach() == GFDM_HIP_OK, "set_channel_estimator with the part on the pool");
+            const auto t0 = std::chrono::steady_clock::now();
+            float tag = loopback::kTagGeneric;
+            while (tag != loopback::kTagJit) {
+                CHECK(w.call(false, (unsigned)rng(), rng) == loopback::kTagJit, "block call while the preamble-equalised kernels compile");
+                tag = w.call(true, (unsigned)rng(), rng);
+                (tag == loopback::kTagGeneric ? generic_calls : tuned_calls)++;
+                CHECK(w.tuned_name(), "the name stays rowlane_jit");
+                CHECK(since(t0) < limit, "preamble-equalised kernels of M%d K%d not ready after %g s", w.s.M, w.s.K, limit);
+            }
+            for (int i = 0; i < 3; ++i) CHECK(w.call(true, (unsigned)rng(), rng) == loopback::kTagJit, "estimated call after the part arrived");
+            CHECK(w.attach() == GFDM_HIP_OK, "attaching again");
+            CHECK(w.call(true, (unsigned)rng(), rng) == loopback::kTagJit, "estimated call after attaching again");
+        }
+        // (3) a background build that does not arrive (gfdm_hip_quiesce drops it): the handle stays on the generic family for good
+        {
+            (void)gfdm_hip_set_jit(2);
+            WalkRx w(Shape{ 27 + 2 * advanced, 16, 2, 2 }, advanced != 0);
+            gfdm_hip_quiesce();
+            CHECK(w.attach() == GFDM_HIP_OK, "set_channel_estimator on a handle whose build failed");
+            for (int i = 0; i < 3; ++i) {
+                CHECK(w.call(true, (unsigned)rng(), rng) == loopback::kTagGeneric, "estimated call after a failed build");
+                CHECK(w.call(false, (unsigned)rng(), rng) == loopback::kTagGeneric, "block call after a failed build");
+                CHECK(!w.tuned_name(), "a failed build leaves the generic family");
+            }
+        }
+    }
+    gfdm_hip_quiesce();
+    loopback::set_compile_ms(2, 25);
+    printf("part states: family, preamble-equalised part and dropped build walked on both receiver kinds: %ld estimated calls on the generic family while compiling, %ld tuned\n",
+           generic_calls, tuned_calls);
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -617,6 +755,7 @@ int main(int argc, char** argv)
     }
     failure_sweep(seed);
     edge_cases(seed + 3);
+    part_state_walk(seed + 4);
 
     gfdm_hip_quiesce();
     const loopback::Stats st = loopback::stats();
