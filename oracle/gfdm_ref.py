@@ -17,11 +17,15 @@ Pinning (DESIGN.md section 2 keeps the same two lists):
 
 FIXTURE-PINNED -- checked against golden vectors produced in the build container by the reference's own Python model
 `pygfdm` (tests/golden/make_golden*.py, tests/test_oracle.py):
-  * modulate (any overlap) and demodulate (overlap == 2): gfdm_modulate_block / gfdm_demodulate_block, exactly
-    the expectation the reference's C++ tests use (python/qa_python_bindings.py:254-440);
-  * the receiver's filter stage at any overlap: pygfdm's overlap-generic model gfdm_demodulate_fft_loop
-    (python/pygfdm/gfdm_receiver.py:190-199; fixtures rxl_*.npz), plus the exact transpose identity with the modulator
-    (tests/test_oracle.py::test_receiver_is_transpose_of_modulator);
+  * modulate (any even overlap; now also with complex asymmetric taps, rxl_ctaps_*) and demodulate (overlap == 2):
+    gfdm_modulate_block / gfdm_demodulate_block, exactly the expectation the reference's C++ tests use
+    (python/qa_python_bindings.py:254-440);
+  * the receiver's filter stage at any even overlap: pygfdm's overlap-generic model gfdm_demodulate_fft_loop
+    (python/pygfdm/gfdm_receiver.py:190-199; fixtures rxl_*.npz, with complex asymmetric taps rxl_ctaps_*.npz), plus the exact
+    transpose identity with the modulator (tests/test_oracle.py::test_receiver_is_transpose_of_modulator).
+    At odd overlap pygfdm is a different model (relative difference above 1, measured): the C++ lines are the authority
+    (lib/modulator_kernel_cc.cc:116-132, integer L/2), and the two oracles, this one and oracle/gfdm_oracle.c, are held
+    against each other (tests/test_taps.py::test_c_oracle_matches_numpy_oracle_at_odd_overlap);
   * ic_filter_taps, cancel_sc_interference and the IC loop (to_td -> 5 x (QPSK decision, cancel against the
     unchanged S, to_td)): gfdm_get_ic_f_taps, gfdm_remove_sc_interference, gfdm_transform_subcarriers_to_tdomain,
     map_qpsk_stream (python/pygfdm/gfdm_receiver.py:91-114, utils.py:80-82; tests/golden/make_golden_ic.py),

@@ -1,6 +1,33 @@
-"""Worst measured error per path from a GFDM_ERRLOG file (tests/conftest.py::check_err): python scratch/errlog_table.py <errlog>"""
+"""Worst measured error per path from a GFDM_ERRLOG file (tests/conftest.py::check_err): python scratch/errlog_table.py <errlog>
+With --taps: the taps_<route>_<family>_<entry> lines of tests/test_taps_gpu.py, worst per route and tap family."""
 import collections, re, sys
 worst = collections.defaultdict(lambda: (0.0, 0.0, 0))
+if "--taps" in sys.argv:
+    sys.argv.remove("--taps")
+    fams = ("rand", "real_asym", "cplx_icsym")
+    cell, other = collections.defaultdict(lambda: (0.0, "", 0)), collections.defaultdict(lambda: (0.0, 0.0, 0))
+    for line in open(sys.argv[1]):
+        tag, err, tol = line.split()
+        m = re.match(r"taps_(\w+?)_(%s)_(\w+)$" % "|".join(fams), tag)
+        if "taps_" not in tag:
+            continue
+        if m and float(tol) == 1e-5 and "_cross_" not in tag and not m.group(1).startswith(("tx_", "pybind_")) and not m.group(3).startswith("frames") and m.group(3) != "dem":
+            w, e, n = cell[m.group(1), m.group(2)]
+            cell[m.group(1), m.group(2)] = (max(w, float(err)), m.group(3) if float(err) > w else e, n + 1)
+        else:                                    # everything else, the route, family and input taken out of the tag
+            key = re.sub(r"rxl_ctaps_\w+_(qpsk|gauss)$", "fixtures", tag)
+            key = re.sub(r"^taps_(rowlane|generic|rader)_(jit_)?[a-z0-9]+?(_per_wave|_12|_dft)?_(%s|imag|above|frames)" % "|".join(fams), r"taps_<route>_\4", key)
+            key = re.sub(r"_(mf|zf|ts|sc)(_|$)", r"\2", re.sub(r"_(generic|rowlane)_rand", "_<family>_rand", re.sub(r"framed\d", "framed", key)))
+            key = re.sub(r"taps_(rowlane_7|rowlane_jit|generic_5_32)_rand_dem", "taps_<burst case>_rand_dem", key)
+            w, t, n = other[key]
+            other[key] = (max(w, float(err)), max(t, float(tol)), n + 1)
+    print("| route | comparisons per family | " + " | ".join("`%s`: worst error (entry point)" % f for f in fams) + " |\n|---|---|" + "---|" * len(fams))
+    for route in sorted({r for r, _ in cell}):
+        print("| `%s` | %d | " % (route, cell[route, fams[0]][2]) + " | ".join("%.2e (%s)" % cell[route, f][:2] for f in fams) + " |")
+    print("\n| other comparison | count | worst error | bound |\n|---|---|---|---|")
+    for key, (w, t, n) in sorted(other.items()):
+        print("| `%s` | %d | %.2e | %.0e |" % (key, n, w, t))
+    sys.exit(0)
 for line in open(sys.argv[1]):
     tag, err, tol = line.split()
     fam = re.sub(r"_(\d+_\d+_\d+.*|ic_.*|ref_.*|cfg.*|rxl_.*)$", "", tag)

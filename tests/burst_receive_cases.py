@@ -17,13 +17,17 @@ def active_bins(K, A):
 
 
 @functools.lru_cache(maxsize=None)
-def make_case(M, K, L, A, nb, seed=0, pre_off=0, cfo_max=0.25, gap=37):
-    """a capture of nb bursts `gap` samples apart (gap > 17, so a backoff of 17 stays inside the capture); the caller leaves it unchanged"""
+def make_case(M, K, L, A, nb, seed=0, pre_off=0, cfo_max=0.25, gap=37, taps_kind="rrc"):
+    """a capture of nb bursts `gap` samples apart (gap > 17, so a backoff of 17 stays inside the capture); the caller leaves it unchanged.
+    taps_kind: "rrc", or a tap family of tests/tap_cases.py (plain demodulation only: with random taps precondition (C) does not hold)"""
     rng = np.random.default_rng(1000 * seed + M * K + A + nb)
     N, cp = M * K, K // 4 + 1
     # roll-off 0.1: the self-interference in front of the first cancellation round is then small enough for precondition (C) at every shape
     # (smallest margin over seeds 0-9: 0.19 at M = 127, K = 16; with 0.3 it falls below 0.01 at the large shapes)
     taps = get_frequency_domain_filter("rrc", 0.1, M, K, L)
+    if taps_kind != "rrc":
+        import tap_cases
+        taps = tap_cases.make_taps(taps_kind, M, K, L)
     nt = R.normalize_taps(taps, M)
     smap = active_bins(K, A)
     pre = np.tile(np.fft.ifft(np.exp(2j * np.pi * rng.random(K))) * np.sqrt(K), 2)
