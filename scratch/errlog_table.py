@@ -1,7 +1,41 @@
 """Worst measured error per path from a GFDM_ERRLOG file (tests/conftest.py::check_err): python scratch/errlog_table.py <errlog>
-With --taps: the taps_<route>_<family>_<entry> lines of tests/test_taps_gpu.py, worst per route and tap family."""
+With --taps: the taps_<route>_<family>_<entry> lines of tests/test_taps_gpu.py, worst per route and tap family.
+With --accuracy: the acc_<route>_<taps>_<entry>_<figure> lines of tests/test_accuracy_gpu.py: per tag the measured figure, its bound, and the
+ratio of both to the figure of the plain-C float32 oracle on the same call (the accref_... line in front of each) and the margin
+of the bound (the accmargin_... line)."""
 import collections, re, sys
 worst = collections.defaultdict(lambda: (0.0, 0.0, 0))
+if "--accuracy" in sys.argv:
+    sys.argv.remove("--accuracy")
+    ref, margin, rows, cross = {}, {}, [], []
+    for line in open(sys.argv[1]):
+        tag, err, tol = line.split()
+        if tag.startswith("accref_"):
+            ref[tag[len("accref_"):]] = float(err)
+        elif tag.startswith("accmargin_"):
+            margin[tag[len("accmargin_"):]] = float(err)
+        elif tag.endswith("_mx_vs_valu"):
+            cross.append((tag, float(err), float(tol)))
+        elif tag.startswith("acc_"):
+            rows.append((tag, float(err), float(tol), ref[tag[len("acc_"):]], margin[tag[len("acc_"):]]))
+    worst = max(rows, key=lambda r: r[1] / r[3])
+    print("Measured figure of the HIP path, its bound, and both as multiples of the plain-C float32 oracle's figure on the same call")
+    print("(`GFDM_ERRLOG=<file> pytest tests/test_accuracy_gpu.py -m gpu`, `scratch/errlog_table.py --accuracy <file>`).")
+    print("%d comparisons; worst measured ratio %.2f (`%s`).\n" % (len(rows), worst[1] / worst[3], worst[0]))
+    print("| figure | margin (bound / reference) | measured / reference: least | median | largest |\n|---|---|---|---|---|")
+    for fig in ("l2", "peak", "pos"):
+        r = sorted(x[1] / x[3] for x in rows if x[0].endswith("_" + fig))
+        m = sorted({x[4] for x in rows if x[0].endswith("_" + fig)})
+        print("| `%s` | %s | %.2f | %.2f | %.2f |" % (fig, ", ".join("%g" % v for v in m), r[0], r[len(r) // 2], r[-1]))
+    if cross:
+        print("\nThe matrix-core cancellation rounds against the vector-ALU rounds on the same call (bits differ, asserted):\n\n| tag | relative L2 | bound |\n|---|---|---|")
+        for tag, err, tol in cross:
+            print("| `%s` | %.2e | %.0e |" % (tag, err, tol))
+    print("\nThe bound is the margin times the reference figure (the log keeps two digits of it).\n")
+    print("| tag | measured | bound | reference | measured / reference | margin |\n|---|---|---|---|---|---|")
+    for tag, err, tol, rf, mg in rows:
+        print("| `%s` | %.2e | %.1e | %.2e | %.2f | %g |" % (tag, err, tol, rf, err / rf, mg))
+    sys.exit(0)
 if "--taps" in sys.argv:
     sys.argv.remove("--taps")
     fams = ("rand", "real_asym", "cplx_icsym")
