@@ -134,33 +134,41 @@ def make_case(route, kind, seed=0):
     """inputs of one route with one tap family (all exactly representable in float32), the float64 result of every entry point on
     them, and the cancellation case with its guard; shared between tests, read-only"""
     r = ROUTES[route]
-    (M, K, L), B = r["shape"], r["B"]
+    return make_shape_case(route, r["shape"], r["B"], kind, seed, IC_SEED.get((route, kind), 0))
+
+
+@functools.lru_cache(maxsize=None)
+def make_shape_case(route, shape, B, kind, seed=0, ic_seed=0, ic=True):
+    """make_case for any shape (tests/codelet_cases.py has its own list); ic=False leaves the cancellation case out"""
+    M, K, L = shape
     N = M * K
     rng = np.random.default_rng(_seed("accuracy", M, K, L, B, seed))
     taps = c64(T.make_taps(kind, M, K, L))
     nt = R.normalize_taps(taps, M)
-    ic = R.ic_filter_taps(nt, M, L)
     sym = c64(T.qpsk(rng, (B, N)))
     x = c64(R.modulate(sym, nt, M, K, L))
     feq = c64(np.fft.fft(H, N)[None, :] * np.exp(0.01j * np.arange(B))[:, None])
     xe = c64(np.fft.ifft(np.fft.fft(x, axis=-1) * feq, axis=-1))
     S = c64(R.fft_filter_downsample(x, nt, M, K, L))
-    c = dict(route=route, M=M, K=K, L=L, B=B, N=N, kind=kind, taps=taps, nt=nt, sym=sym, x=x, feq=feq, xe=xe, S=S)
+    smap = T.subcarrier_map(K, M)
+    c = dict(route=route, M=M, K=K, L=L, B=B, N=N, kind=kind, taps=taps, nt=nt, sym=sym, x=x, feq=feq, xe=xe, S=S, smap=smap)
     c["ref_modulate"] = R.modulate(sym, nt, M, K, L)
     c["ref_fd"] = R.fft_filter_downsample(x, nt, M, K, L)
     c["ref_fdeq"] = R.fft_filter_downsample(xe, nt, M, K, L, feq)
     c["ref_demodulate"] = R.demodulate(x, nt, M, K, L)
     c["ref_demodulate_equalize"] = R.demodulate(xe, nt, M, K, L, feq)
     c["ref_to_td"] = R.transform_subcarriers_to_td(S, M, K)
-    c["ref_cancel"] = R.cancel_sc_interference(sym, S, ic, M, K)
+    if not ic:
+        return _freeze(c)
+    ict = R.ic_filter_taps(nt, M, L)
+    c["ref_cancel"] = R.cancel_sc_interference(sym, S, ict, M, K)
     # the cancellation case: a partial map, noisy blocks, matched-filter and zero-forcing input, QPSK sign decisions
-    rng = np.random.default_rng(_seed("accuracy_ic", M, K, L, B, seed) + IC_SEED.get((route, kind), 0))
-    smap = T.subcarrier_map(K, M)
+    rng = np.random.default_rng(_seed("accuracy_ic", M, K, L, B, seed) + ic_seed)
     d = np.zeros((B, K, M), complex)
     d[:, smap, :] = T.qpsk(rng, (B, len(smap), M))
     xi = c64(R.modulate(d.reshape(B, N), nt, M, K, L) + IC_NOISE * T._gauss(rng, (B, N)))
     xie = c64(np.fft.ifft(np.fft.fft(xi, axis=-1) * feq, axis=-1))
-    c.update(smap=smap, ic_x=xi, ic_xe=xie)
+    c.update(ic_x=xi, ic_xe=xie)
     for inp, src, eq in (("mf", xi, None), ("zf", xie, feq)):
         ref, st = R.advanced_receive(src, nt, M, K, L, smap, R.qpsk_points(), IC_ITER, f_eq=eq, kind="qpsk", return_stages=True)
         c["ref_ic_" + inp] = ref
@@ -247,9 +255,12 @@ def oracle_handles(c, taps=None):
 @functools.lru_cache(maxsize=None)
 def reference_figures(route, kind, seed=0):
     """{entry: figures of the C oracle on the case's inputs}: what float32 arithmetic needs on these sums"""
-    c = make_case(route, kind, seed)
+    return case_reference_figures(make_case(route, kind, seed), ROUTES[route]["entries"])
+
+
+def case_reference_figures(c, entries):
     h = oracle_handles(c)
-    return {e: h.figures(e, c)[0] for e in ROUTES[route]["entries"]}
+    return {e: h.figures(e, c)[0] for e in entries}
 
 
 # ---------------------------------------------------------------- mutations: what TOL lets through and the bounds must not

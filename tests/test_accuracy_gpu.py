@@ -41,10 +41,10 @@ def _require_gpu():
 
 
 @contextlib.contextmanager
-def _creating(route, **override):
+def _creating(route, routes=A.ROUTES, **override):
     """the context in which the handles of a route are created (as tests/test_poison_gpu.py, on the routes of accuracy_cases)"""
     import gfdm_amd
-    r = dict(A.ROUTES[route], **override)
+    r = dict(routes[route], **override)
     with contextlib.ExitStack() as es:
         if r.get("generic"):
             es.enter_context(gfdm_amd.generic_family_for_testing())
@@ -53,16 +53,18 @@ def _creating(route, **override):
         yield
 
 
-def _handles(route, c, ic_iter=A.IC_ITER, **override):
+def _handles(route, c, ic_iter=A.IC_ITER, routes=A.ROUTES, **override):
     """Modulator, Demodulator and AdvancedReceiver of a route behind the calls of accuracy_cases.Handles, kernel_name() asserted: a route
-    cannot silently change"""
+    cannot silently change.  A route of another list (routes) that says adv=False gets no AdvancedReceiver."""
     import gfdm_amd
     M, K, L = c["M"], c["K"], c["L"]
-    with _creating(route, **override):
+    with _creating(route, routes, **override):
         mod, dem = gfdm_amd.Modulator(M, K, L, c["taps"]), gfdm_amd.Demodulator(M, K, L, c["taps"])
-        adv = gfdm_amd.AdvancedReceiver(M, K, L, c["taps"], c["smap"], ic_iter, R.qpsk_points())
-    assert (mod.kernel_name(), dem.kernel_name(), adv.kernel_name()) == (A.ROUTES[route]["kernel"],) * 3
-    assert adv.decision_rule() == "qpsk" and adv.get_phase_compensation() == 0 and adv.get_ic() == ic_iter
+        adv = gfdm_amd.AdvancedReceiver(M, K, L, c["taps"], c["smap"], ic_iter, R.qpsk_points()) if routes[route].get("adv", True) else None
+    assert (mod.kernel_name(), dem.kernel_name()) == (routes[route]["kernel"],) * 2
+    if adv is not None:
+        assert adv.kernel_name() == routes[route]["kernel"]
+        assert adv.decision_rule() == "qpsk" and adv.get_phase_compensation() == 0 and adv.get_ic() == ic_iter
     return A.Handles(mod, dem, adv)
 
 
@@ -101,22 +103,27 @@ def _tx_kernels(route):
 
 # ---------------------------------------------------------------- budget
 
+def _budget(found, tag, kind, c, ref, h, entries, margin):
+    """every entry against its bound: check_err tags acc_<tag>_<taps>_<entry>_<figure>, accref_... the C oracle's figure, accmargin_... the margin"""
+    for e in entries:
+        assert 2 * A.keep(c, e).sum() >= c["B"]                          # as tests/test_accuracy.py
+        assert 0 < ref[e]["l2"] < A.REF_L2_CAP
+        bound = A.bounds(ref[e], margin)
+        figs, got, want = h.figures(e, c)
+        print("%s %s %-20s " % (tag, kind, e) + "  ".join("%s %.2e / %.2e (ref %.2e)" % (f, figs[f], bound[f], ref[e][f]) for f in A.FIGURES))
+        for f in A.FIGURES:
+            found.check("accref_%s_%s_%s_%s" % (tag, kind, e, f), ref[e][f], A.TOL)            # the C oracle's figure, for the ratio table
+            found.check("accmargin_%s_%s_%s_%s" % (tag, kind, e, f), margin[f], 4.0 + 1e-9)         # the cap of every margin
+            found.check("acc_%s_%s_%s_%s" % (tag, kind, e, f), figs[f], bound[f], A.where(got, want))
+
+
 @pytest.mark.parametrize("route,kind", A.CASES)
 def test_every_entry_point_within_the_float32_budget(route, kind):
     c = A.make_case(route, kind)
     ref = A.reference_figures(route, kind)
     h = _handles(route, c)
     found = _Findings()
-    for e in A.ROUTES[route]["entries"]:
-        assert 2 * A.keep(c, e).sum() >= c["B"]                          # as tests/test_accuracy.py
-        assert 0 < ref[e]["l2"] < A.REF_L2_CAP
-        bound = A.bounds(ref[e], A.ROUTES[route]["margin"])
-        figs, got, want = h.figures(e, c)
-        print("%s %s %-20s " % (route, kind, e) + "  ".join("%s %.2e / %.2e (ref %.2e)" % (f, figs[f], bound[f], ref[e][f]) for f in A.FIGURES))
-        for f in A.FIGURES:
-            found.check("accref_%s_%s_%s_%s" % (route, kind, e, f), ref[e][f], A.TOL)            # the C oracle's figure, for the ratio table
-            found.check("accmargin_%s_%s_%s_%s" % (route, kind, e, f), A.ROUTES[route]["margin"][f], 4.0 + 1e-9)         # the cap of every margin
-            found.check("acc_%s_%s_%s_%s" % (route, kind, e, f), figs[f], bound[f], A.where(got, want))
+    _budget(found, route, kind, c, ref, h, A.ROUTES[route]["entries"], A.ROUTES[route]["margin"])
     if A.ROUTES[route]["ic_mx"] == 2:
         # kernel_name() is the same for both forms of the rounds.  That this route runs another one than the vector-ALU routes shows in
         # the result: the same sums in another order (f16 operand terms, f32 sums) agree to rounding and differ in some bits.
