@@ -925,38 +925,13 @@ int gfdm_hip_advanced_receiver_create(gfdm_hip_advanced_receiver** out, int time
     if (rc != GFDM_HIP_OK) { delete a; return rc; }
 
     const cf* pts = reinterpret_cast<const cf*>(constellation_points);
-    // "is this GNU Radio's unit constellation": every component within 6 * FLT_EPSILON * |component| (5.1e-7 at 1 / sqrt 2 = 8.5 f32 ulps there) of the unit
-    // point's.  Points that went through a double -> float conversion or a product with 1 / sqrt 2 in float land within one ulp; gr::digital's
-    // constellation_qpsk is built from the LITERAL SQRT_TWO = 0.707107 (gr-digital/lib/constellation.cc), which as a float sits 2.3e-7 = 3.8 ulps
-    // away from 1 / sqrt 2 and must still get the sign tests (round-5 advisor; tests/test_parity_gpu.py test_decision_rule_a_handle_runs_is_reported).
-    // The sign-test kernels then cancel with 0.70710678f: 3.2e-7 relative to the literal's points, far inside the 1e-5 of the parity statement.
-    auto near = [](cf p, float re, float im) {
-        const float tr = 6.f * FLT_EPSILON * (std::fabs(re) > 0.f ? std::fabs(re) : 1.f), ti = 6.f * FLT_EPSILON * (std::fabs(im) > 0.f ? std::fabs(im) : 1.f);
-        return std::fabs(p.x - re) <= tr && std::fabs(p.y - im) <= ti;
-    };
-    if (decision == GFDM_HIP_DECIDE_AUTO) {
-        const float s = 0.70710678118654752f;
-        if (n_points == 4 && near(pts[0], -s, -s) && near(pts[1], s, -s) && near(pts[2], -s, s) && near(pts[3], s, s))
-            decision = GFDM_HIP_DECIDE_QPSK;
-        else if (n_points == 2 && near(pts[0], -1.f, 0.f) && near(pts[1], 1.f, 0.f))
-            decision = GFDM_HIP_DECIDE_BPSK;
-        else
-            decision = GFDM_HIP_DECIDE_NEAREST;
-    }
-    if ((decision == GFDM_HIP_DECIDE_QPSK && n_points != 4) || (decision == GFDM_HIP_DECIDE_BPSK && n_points != 2)) {
+    // AUTO, and an explicit QPSK / BPSK over other points than the unit constellations', are resolved by gfdm::resolve_decision (gfdm_hostcall.h): a demoted
+    // rule runs as the nearest-point rule on the points as given -- every kernel family reads ic.points for it, so a handle gives the same results on
+    // each of them.  The rule a handle really runs is reported by gfdm_hip_advanced_receiver_decision.
+    decision = gfdm::resolve_decision(pts, n_points, decision);
+    if (decision < 0) {
         delete a;
         return fail(GFDM_HIP_EINVAL, "decision rule does not match the number of constellation points");
-    }
-    // The sign-test kernels cancel with the unit constellations' own points (+-1/sqrt 2, +-1).  An explicit QPSK / BPSK rule over other
-    // points (scaled, rotated) keeps its decision REGIONS only if it is the nearest-point rule of those points; it is then run as that, on
-    // the points as given -- every kernel family reads ic.points for it, so a handle gives the same results on each of them.
-    // The rule a handle really runs is reported by gfdm_hip_advanced_receiver_decision.
-    {
-        const float s = 0.70710678118654752f;
-        if (decision == GFDM_HIP_DECIDE_QPSK && !(near(pts[0], -s, -s) && near(pts[1], s, -s) && near(pts[2], -s, s) && near(pts[3], s, s)))
-            decision = GFDM_HIP_DECIDE_NEAREST;
-        if (decision == GFDM_HIP_DECIDE_BPSK && !(near(pts[0], -1.f, 0.f) && near(pts[1], 1.f, 0.f)))
-            decision = GFDM_HIP_DECIDE_NEAREST;
     }
 
     const size_t pts_bytes = (size_t)n_points * sizeof(cf);

@@ -4,9 +4,36 @@
 #include "../../include/gfdm_hip.h"
 #include "gfdm_plan.h"
 
+#include <cfloat>
+#include <cmath>
 #include <string>
 
 namespace gfdm {
+
+// The decision rule a handle RUNS over `pts` (a gfdm_hip_decision, never AUTO) when the caller asked for `decision`, or -1 where the rule
+// asked for does not fit n_points.  Shared by every constructor that takes a constellation.
+// "Is this GNU Radio's unit constellation": every component within 6 * FLT_EPSILON * |component| (5.1e-7 at 1 / sqrt 2 = 8.5 f32 ulps there) of the unit
+// point's.  Points that went through a double -> float conversion or a product with 1 / sqrt 2 in float land within one ulp; gr::digital's
+// constellation_qpsk is built from the LITERAL SQRT_TWO = 0.707107 (gr-digital/lib/constellation.cc), which as a float sits 2.3e-7 = 3.8 ulps
+// away from 1 / sqrt 2 and must still get the sign tests (tests/test_parity_gpu.py test_decision_rule_a_handle_runs_is_reported).
+// The sign-test kernels of the receivers then cancel with 0.70710678f: 3.2e-7 relative to the literal's points, far inside the 1e-5 of the parity statement.
+// AUTO picks the sign tests for those points alone.  An explicit QPSK / BPSK rule over other points (scaled, rotated) keeps its decision REGIONS
+// only if it is the nearest-point rule of those points; it is then run as that, on the points as given.
+inline int resolve_decision(const cf* pts, int n_points, int decision)
+{
+    auto near = [](cf p, float re, float im) {
+        const float tr = 6.f * FLT_EPSILON * (std::fabs(re) > 0.f ? std::fabs(re) : 1.f), ti = 6.f * FLT_EPSILON * (std::fabs(im) > 0.f ? std::fabs(im) : 1.f);
+        return std::fabs(p.x - re) <= tr && std::fabs(p.y - im) <= ti;
+    };
+    const float s = 0.70710678118654752f;
+    const bool unit_qpsk = n_points == 4 && near(pts[0], -s, -s) && near(pts[1], s, -s) && near(pts[2], -s, s) && near(pts[3], s, s);
+    const bool unit_bpsk = n_points == 2 && near(pts[0], -1.f, 0.f) && near(pts[1], 1.f, 0.f);
+    if (decision == GFDM_HIP_DECIDE_AUTO) return unit_qpsk ? GFDM_HIP_DECIDE_QPSK : unit_bpsk ? GFDM_HIP_DECIDE_BPSK : GFDM_HIP_DECIDE_NEAREST;
+    if ((decision == GFDM_HIP_DECIDE_QPSK && n_points != 4) || (decision == GFDM_HIP_DECIDE_BPSK && n_points != 2)) return -1;
+    if (decision == GFDM_HIP_DECIDE_QPSK && !unit_qpsk) return GFDM_HIP_DECIDE_NEAREST;
+    if (decision == GFDM_HIP_DECIDE_BPSK && !unit_bpsk) return GFDM_HIP_DECIDE_NEAREST;
+    return decision;
+}
 
 // error reporting shared by the translation units of the C-ABI (thread-local message behind gfdm_hip_last_error; defined in gfdm_hip_api.hip)
 int api_fail(int code, const std::string& msg);

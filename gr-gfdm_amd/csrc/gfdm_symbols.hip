@@ -1,0 +1,536 @@
+// Symbol mapper at both ends of the chain: payload bytes -> constellation points in front of the transmitter, demapped symbols -> payload
+// bytes or max-log soft bits behind the receivers (GNU Radio's repack_bits_bb(8 -> k, MSB first) + chunks_to_symbols, and
+// constellation_decoder_cb + repack_bits_bb(k -> 8); pygfdm's bits2symbols / symbols2bits).  The contract is written out in
+// include/gfdm_hip.h.
+//
+// Three element-wise kernels, memory bound by design.  As in gfdm_shaper.hip the OUTPUT is tiled, never the rows: a workgroup takes a
+// fixed stretch of the flat output, so the grid depends on the total size alone and 32768 + 7 rows of 5 symbols spread as evenly as one
+// row of 2^20.  A tile finds the row of its first element by one division; every other element steps on from there.
+//   decode: a tile is 256 k packed bytes.  The symbols behind them are ONE contiguous stretch of the input (at most 2048 + 2: rows are
+//           contiguous on both sides); the lanes load it as 16-byte vectors aligned in memory (two symbols a lane, 1 KiB a wave; a head that
+//           is only 8-byte aligned and a ragged tail go element by element), decide at once and leave one index byte per symbol in LDS.
+//           Then lane t assembles output byte t from the (at most 8) index bytes it spans and stores it: 64 contiguous bytes a wave.
+//   soft:   a tile is 1024 aligned 16-byte vectors of LLRs.  The symbols behind them (at most 4096 / k + 2) are loaded as above, each
+//           lane leaves its symbols' k LLRs in LDS, and the tile goes out as 16 bytes a lane whatever k is.
+//   map:    a tile is 1024 aligned 16-byte vectors of two symbols; the packed input is 1/32 .. 1/4 of that and read through the cache.
+// The point table sits in LDS (none for the sign tests).  Rows from n_live on are written as zeros by the same kernel and their input
+// is never read; nothing is written outside the output and every element of it once.
+#include "../../include/gfdm_hip.h"
+#include "gfdm_hostcall.h"
+
+#include <algorithm>
+#include <climits>
+#include <new>
+
+using gfdm::cf;
+using gfdm::api_fail;
+using gfdm::DeviceGuard;
+using gfdm::DevBuf;
+
+namespace {
+
+constexpr int kLanes = 256;
+constexpr int kTileVec = 4 * kLanes;                 // map, soft: 16-byte vectors of output per tile (16 KiB)
+constexpr int kMaxTiles = 8192;                      // workgroups per launch; the tiles beyond are strided over
+constexpr int kDecodeSyms = 8 * kLanes;              // decode: a tile is kLanes * k bytes = 2048 symbols' worth of bits
+constexpr int kDecodeSlots = kDecodeSyms + 16;       // ... + 2 (rows begin on a byte) + 2 (vectors begin on 16 bytes), rounded up
+constexpr int kSoftSlots = 4 * kTileVec + 8 * 8;     // floats: (4096 / k + 2 + 2) symbols of k LLRs
+
+struct MapperArgs {
+    const cf* points;        // [1 << k] (device)
+    int64_t n_sym, n_rows;
+    int64_t row_bytes;       // ceil(n_sym k / 8)
+    const int64_t* count;    // optional (device): live rows = clamp(*count, 0, n_rows)
+    const float* scale;      // soft, optional (device): [n_rows]
+};
+
+__device__ __forceinline__ int64_t live_rows(const MapperArgs& a)
+{
+    if (!a.count) return a.n_rows;
+    return std::min(std::max(*a.count, (int64_t)0), a.n_rows);
+}
+
+// (row, index in the row) of the flat element d behind the one at (r0, i0); rows of n elements, i0 < n.  No 64-bit division: past the
+// first row what is left of d is below 2^32, and so is n where a quotient is needed at all.
+struct RowPos { int64_t r, i; };
+__device__ __forceinline__ RowPos advance(int64_t r0, int64_t i0, uint32_t d, int64_t n)
+{
+    RowPos p = { r0, i0 + (int64_t)d };
+    if (p.i >= n) {
+        p.i -= n;
+        ++p.r;
+        if (p.i >= n) {
+            const uint32_t q = (uint32_t)p.i / (uint32_t)n;
+            p.r += q;
+            p.i -= (int64_t)q * n;
+        }
+    }
+    return p;
+}
+
+// squared distance in the direct form: the contract's d_i
+__device__ __forceinline__ float dist2(cf x, cf p)
+{
+    const float dr = x.x - p.x, di = x.y - p.y;
+    return dr * dr + di * di;
+}
+
+// RULE: a gfdm_hip_decision (never AUTO).  NEAREST: the first strict minimum starting from +inf (decide_point of gfdm_rowlane_impl.h), so
+// NaN and infinite inputs give index 0; the sign tests are '> 0', so NaN gives 0 and an infinite component decides by its sign.
+template <int K, int RULE>
+__device__ __forceinline__ void decide2(cf x0, cf x1, const cf* pts, int& i0, int& i1)
+{
+    if constexpr (RULE == GFDM_HIP_DECIDE_QPSK) {
+        i0 = 2 * (x0.y > 0.f) + (x0.x > 0.f);
+        i1 = 2 * (x1.y > 0.f) + (x1.x > 0.f);
+    } else if constexpr (RULE == GFDM_HIP_DECIDE_BPSK) {
+        i0 = (x0.x > 0.f);
+        i1 = (x1.x > 0.f);
+    } else {
+        float b0 = __builtin_huge_valf(), b1 = __builtin_huge_valf();
+        i0 = i1 = 0;
+#pragma unroll 16
+        for (int i = 0; i < (1 << K); ++i) {
+            const cf p = pts[i];                    // the same LDS address in every lane: a broadcast
+            const float d0 = dist2(x0, p), d1 = dist2(x1, p);
+            if (d0 < b0) { b0 = d0; i0 = i; }
+            if (d1 < b1) { b1 = d1; i1 = i; }
+        }
+    }
+}
+
+// the 16-byte vector v of the symbol array (symbols 2 v - mis, 2 v - mis + 1 of the flat input; those outside [0, s_end) read as 0)
+__device__ __forceinline__ void load_pair(const cf* __restrict__ in, int64_t s, int64_t s_end, cf& x0, cf& x1)
+{
+    x0 = x1 = make_float2(0.f, 0.f);
+    if (s >= 0 && s + 1 < s_end) {                   // a whole vector: 16-byte aligned by construction
+        const float4 q = *reinterpret_cast<const float4*>(in + s);
+        x0 = make_float2(q.x, q.y);
+        x1 = make_float2(q.z, q.w);
+    } else {
+        if (s >= 0 && s < s_end) x0 = in[s];
+        if (s + 1 >= 0 && s + 1 < s_end) x1 = in[s + 1];
+    }
+}
+
+template <int K>
+__device__ __forceinline__ void load_points(cf* pts, const MapperArgs& a)
+{
+    for (int i = threadIdx.x; i < (1 << K); i += kLanes) pts[i] = a.points[i];
+    __syncthreads();
+}
+
+template <int K, int RULE>
+__global__ __launch_bounds__(kLanes) void k_symbols_decode(MapperArgs a, const cf* __restrict__ in, unsigned char* __restrict__ out)
+{
+    constexpr bool TABLE = RULE == GFDM_HIP_DECIDE_NEAREST;
+    constexpr int kTileBytes = kLanes * K;
+    constexpr int kLoads = (kDecodeSlots / 2 + kLanes - 1) / kLanes;         // vectors per lane (the last one is seldom there)
+    __shared__ cf pts[TABLE ? (1 << K) : 1];
+    __shared__ unsigned char idx[kDecodeSlots];
+    if constexpr (TABLE) load_points<K>(pts, a);
+    const int64_t n_live = live_rows(a), rb = a.row_bytes;
+    const int64_t total = a.n_rows * rb, live_bytes = n_live * rb, s_live = n_live * a.n_sym;
+    const int mis = (int)(((uintptr_t)in / sizeof(cf)) & 1);                 // symbols between the 16-byte boundary in front of `in` and `in`
+    const int64_t ntiles = (total + kTileBytes - 1) / kTileBytes;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t o0 = tile * kTileBytes, o1 = std::min(o0 + kTileBytes, total);
+        const int64_t o_live = std::min(o1, live_bytes);                     // the bytes [o0, o_live) hold symbols
+        const int64_t r0 = o0 / rb, b0 = o0 - r0 * rb;
+        int64_t s_base = 0;
+        if (o_live > o0) {
+            const RowPos last = advance(r0, b0, (uint32_t)(o_live - 1 - o0), rb);
+            const int64_t s_lo = r0 * a.n_sym + (8 * b0) / K;
+            const int64_t s_hi = last.r * a.n_sym + std::min(a.n_sym, (8 * last.i + 7) / K + 1);       // <= s_live: last.r < n_live
+            const int64_t v_lo = (s_lo + mis) >> 1, v_end = (s_hi + mis + 1) >> 1;
+            s_base = 2 * v_lo - mis;
+            cf x[kLoads][2];
+#pragma unroll
+            for (int u = 0; u < kLoads; ++u) {
+                const int64_t v = v_lo + u * kLanes + threadIdx.x;
+                if (v < v_end) load_pair(in, 2 * v - mis, s_live, x[u][0], x[u][1]);
+            }
+#pragma unroll
+            for (int u = 0; u < kLoads; ++u) {
+                const int64_t v = v_lo + u * kLanes + threadIdx.x;
+                const int slot = 2 * (u * kLanes + (int)threadIdx.x);
+                if (v < v_end && slot + 1 < kDecodeSlots) {
+                    int i0, i1;
+                    decide2<K, RULE>(x[u][0], x[u][1], pts, i0, i1);
+                    idx[slot] = (unsigned char)i0;
+                    idx[slot + 1] = (unsigned char)i1;
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < K; ++p) {
+            const int64_t o = o0 + p * kLanes + threadIdx.x;
+            if (o >= o1) continue;
+            unsigned byte = 0;
+            if (o < o_live) {
+                const RowPos pos = advance(r0, b0, (uint32_t)(o - o0), rb);
+                const int64_t q = 8 * pos.i, i = q / K;
+                const int j0 = (int)(q - i * K);
+                const int slot = (int)(pos.r * a.n_sym + i - s_base);
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    const int di = (j0 + t) / K, j = (j0 + t) % K;
+                    if (i + di < a.n_sym) byte |= ((idx[slot + di] >> (K - 1 - j)) & 1u) << (7 - t);
+                }
+            }
+            out[o] = (unsigned char)byte;
+        }
+        __syncthreads();                             // idx is rewritten for the next tile
+    }
+}
+
+// the 2 K minima of one symbol: m0[j] / m1[j] over the points whose bit j (MSB first) is 0 / 1.  The points go by in groups of 16: the low
+// four bits of the index are compile-time constants, the high ones are the same in every lane and take the group's minimum once.
+template <int K>
+__device__ __forceinline__ void soft_minima(cf x, const cf* pts, float* m0, float* m1)
+{
+    constexpr int LOW = K < 4 ? K : 4, HIGH = K - LOW;
+#pragma unroll
+    for (int j = 0; j < K; ++j) m0[j] = m1[j] = __builtin_huge_valf();
+    for (int hi = 0; hi < (1 << HIGH); ++hi) {
+        float c = __builtin_huge_valf();
+#pragma unroll
+        for (int lo = 0; lo < (1 << LOW); ++lo) {
+            const float d = dist2(x, pts[(hi << LOW) + lo]);
+            c = fminf(c, d);
+#pragma unroll
+            for (int j = 0; j < LOW; ++j) {
+                if ((lo >> (LOW - 1 - j)) & 1) m1[HIGH + j] = fminf(m1[HIGH + j], d);
+                else m0[HIGH + j] = fminf(m0[HIGH + j], d);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < HIGH; ++j) {
+            if ((hi >> (HIGH - 1 - j)) & 1) m1[j] = fminf(m1[j], c);
+            else m0[j] = fminf(m0[j], c);
+        }
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(kLanes) void k_symbols_soft(MapperArgs a, const cf* __restrict__ in, float* __restrict__ out)
+{
+    __shared__ cf pts[1 << K];
+    __shared__ float llr[kSoftSlots];
+    load_points<K>(pts, a);
+    const int64_t n_live = live_rows(a);
+    const int64_t total = a.n_rows * a.n_sym * K, s_live = n_live * a.n_sym, live_f = s_live * K;
+    const int mis = (int)(((uintptr_t)in / sizeof(cf)) & 1);
+    const int omis = (int)(((uintptr_t)out / sizeof(float)) & 3);            // floats between the 16-byte boundary in front of `out` and `out`
+    const int64_t nvec = (total + omis + 3) / 4;
+    const int64_t ntiles = (nvec + kTileVec - 1) / kTileVec;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t w0 = tile * kTileVec, w1 = std::min(w0 + kTileVec, nvec);
+        const int64_t f_lo = std::max(4 * w0 - omis, (int64_t)0), f_hi = std::min(4 * w1 - omis, total);
+        const int64_t f_live = std::min(f_hi, live_f);                       // the floats [f_lo, f_live) hold LLRs
+        int64_t s_base = 0;
+        if (f_live > f_lo) {
+            const int64_t s_lo = f_lo / K, s_hi = (f_live - 1) / K + 1;      // <= s_live
+            const int64_t r0 = s_lo / a.n_sym, i0 = s_lo - r0 * a.n_sym;
+            const int64_t v_lo = (s_lo + mis) >> 1, v_end = (s_hi + mis + 1) >> 1;
+            s_base = 2 * v_lo - mis;
+            for (int64_t v = v_lo + threadIdx.x; v < v_end; v += kLanes) {
+                cf x[2];
+                load_pair(in, 2 * v - mis, s_live, x[0], x[1]);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int64_t s = 2 * v - mis + e;
+                    const int slot = (int)(s - s_base) * K;
+                    if (s < s_lo || s >= s_hi || slot + K > kSoftSlots) continue;
+                    const float sc = a.scale ? a.scale[advance(r0, i0, (uint32_t)(s - s_lo), a.n_sym).r] : 1.f;
+                    float m0[K], m1[K];
+                    soft_minima<K>(x[e], pts, m0, m1);
+#pragma unroll
+                    for (int j = 0; j < K; ++j) llr[slot + j] = sc * (m1[j] - m0[j]);
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kTileVec / kLanes; ++u) {
+            const int64_t w = w0 + u * kLanes + threadIdx.x;
+            if (w >= w1) continue;
+            const int64_t f0 = 4 * w - omis;
+            float y[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t f = f0 + e;
+                y[e] = (f >= f_lo && f < f_live) ? llr[(int)(f - s_base * K)] : 0.f;
+            }
+            if (f0 >= 0 && f0 + 4 <= total) {        // a whole vector: 16-byte aligned by construction
+                *reinterpret_cast<float4*>(out + f0) = make_float4(y[0], y[1], y[2], y[3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (f0 + e >= 0 && f0 + e < total) out[f0 + e] = y[e];
+            }
+        }
+        __syncthreads();                             // llr is rewritten for the next tile
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(kLanes) void k_symbols_map(MapperArgs a, const unsigned char* __restrict__ in, cf* __restrict__ out)
+{
+    __shared__ uint2 pts[1 << K];                    // moved as bits: a point goes out as it came in
+    for (int i = threadIdx.x; i < (1 << K); i += kLanes) pts[i] = reinterpret_cast<const uint2*>(a.points)[i];
+    __syncthreads();
+    const int64_t n_live = live_rows(a);
+    const int64_t total = a.n_rows * a.n_sym, s_live = n_live * a.n_sym;
+    const int mis = (int)(((uintptr_t)out / sizeof(cf)) & 1);
+    const int64_t nvec = (total + mis + 1) / 2;
+    const int64_t ntiles = (nvec + kTileVec - 1) / kTileVec;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t w0 = tile * kTileVec, w1 = std::min(w0 + kTileVec, nvec);
+        const int64_t s_lo = std::max(2 * w0 - mis, (int64_t)0);
+        const int64_t r0 = s_lo / a.n_sym, i0 = s_lo - r0 * a.n_sym;
+        uint2 y[kTileVec / kLanes][2];               // all loads of a lane's vectors before its stores, so that their latencies overlap
+#pragma unroll
+        for (int u = 0; u < kTileVec / kLanes; ++u) {
+            const int64_t w = w0 + u * kLanes + threadIdx.x;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int64_t s = 2 * w - mis + e;
+                y[u][e] = make_uint2(0u, 0u);
+                if (w >= w1 || s < 0 || s >= s_live) continue;
+                const RowPos pos = advance(r0, i0, (uint32_t)(s - s_lo), a.n_sym);
+                const int64_t q = pos.i * K, at = pos.r * a.row_bytes + (q >> 3);
+                const int sh = (int)(q & 7);
+                unsigned bits = (unsigned)in[at] << 8;
+                if (sh + K > 8) bits |= in[at + 1];  // the symbol's own bits reach into that byte: it is inside the row
+                y[u][e] = pts[(bits >> (16 - sh - K)) & ((1u << K) - 1u)];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kTileVec / kLanes; ++u) {
+            const int64_t w = w0 + u * kLanes + threadIdx.x;
+            if (w >= w1) continue;
+            const int64_t s = 2 * w - mis;
+            if (s >= 0 && s + 2 <= total) {          // a whole vector: 16-byte aligned by construction
+                *reinterpret_cast<uint4*>(out + s) = make_uint4(y[u][0].x, y[u][0].y, y[u][1].x, y[u][1].y);
+            } else {
+                if (s >= 0 && s < total) *reinterpret_cast<uint2*>(out + s) = y[u][0];
+                if (s + 1 >= 0 && s + 1 < total) *reinterpret_cast<uint2*>(out + s + 1) = y[u][1];
+            }
+        }
+    }
+}
+
+int bits_of(int n_points)
+{
+    for (int k = 1; k <= 8; ++k)
+        if (n_points == (1 << k)) return k;
+    return 0;
+}
+
+// the argument table (include/gfdm_hip.h); needs no handle, so it is checked before any device is touched
+int mapper_check(int n_points, int64_t n_sym, int64_t n_rows)
+{
+    const int k = bits_of(n_points);
+    if (!k) return api_fail(GFDM_HIP_EINVAL, "a constellation needs 2, 4, 8, ..., 256 points");
+    if (n_sym < 1) return api_fail(GFDM_HIP_EINVAL, "n_sym must be >= 1");
+    if (n_rows < 0) return api_fail(GFDM_HIP_EINVAL, "n_rows must be >= 0");
+    const int64_t per = std::max<int64_t>((int64_t)sizeof(cf), (int64_t)sizeof(float) * k);      // bytes per symbol: as a sample, as k LLRs
+    if (n_sym > INT64_MAX / per || (n_rows > 0 && n_sym * per > INT64_MAX / n_rows))
+        return api_fail(GFDM_HIP_EINVAL, "the byte size of the symbols or of the soft bits overflows int64");
+    return GFDM_HIP_OK;
+}
+
+}  // namespace
+
+struct gfdm_hip_symbol_mapper {
+    gfdm::DeviceCtx ctx;
+    int k = 0, rule = GFDM_HIP_DECIDE_NEAREST;
+    cf points[256];
+    cf* d_points = nullptr;
+    ~gfdm_hip_symbol_mapper()
+    {
+        DeviceGuard guard(ctx.device);
+        if (d_points) (void)hipFree(d_points);
+    }
+};
+
+namespace {
+
+enum Op { OP_MAP, OP_DECODE, OP_SOFT };
+
+int64_t row_bytes_of(int k, int64_t n_sym) { return (n_sym * k + 7) / 8; }
+
+unsigned grid_for(int64_t ntiles) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, kMaxTiles)); }
+
+template <int K>
+void launch_k(const gfdm_hip_symbol_mapper* h, Op op, const MapperArgs& a, void* out, const void* in, hipStream_t s)
+{
+    const dim3 block(kLanes);
+    if (op == OP_MAP) {
+        const int64_t ntiles = ((a.n_rows * a.n_sym + 1) / 2 + 1 + kTileVec - 1) / kTileVec;            // + 1: an unaligned `out` adds a vector
+        hipLaunchKernelGGL(k_symbols_map<K>, dim3(grid_for(ntiles)), block, 0, s, a, static_cast<const unsigned char*>(in), static_cast<cf*>(out));
+    } else if (op == OP_SOFT) {
+        const int64_t ntiles = ((a.n_rows * a.n_sym * K + 3) / 4 + 1 + kTileVec - 1) / kTileVec;
+        hipLaunchKernelGGL(k_symbols_soft<K>, dim3(grid_for(ntiles)), block, 0, s, a, static_cast<const cf*>(in), static_cast<float*>(out));
+    } else {
+        const dim3 grid(grid_for((a.n_rows * a.row_bytes + kLanes * K - 1) / (kLanes * K)));
+        const cf* x = static_cast<const cf*>(in);
+        unsigned char* y = static_cast<unsigned char*>(out);
+        if (K == 2 && h->rule == GFDM_HIP_DECIDE_QPSK) hipLaunchKernelGGL((k_symbols_decode<2, GFDM_HIP_DECIDE_QPSK>), grid, block, 0, s, a, x, y);
+        else if (K == 1 && h->rule == GFDM_HIP_DECIDE_BPSK) hipLaunchKernelGGL((k_symbols_decode<1, GFDM_HIP_DECIDE_BPSK>), grid, block, 0, s, a, x, y);
+        else hipLaunchKernelGGL((k_symbols_decode<K, GFDM_HIP_DECIDE_NEAREST>), grid, block, 0, s, a, x, y);
+    }
+}
+
+// the one launch of a call.  Everything is a device pointer.
+int mapper_enqueue(const gfdm_hip_symbol_mapper* h, Op op, void* out, const void* in, const void* scale, const void* count, int64_t n_sym, int64_t n_rows,
+                   hipStream_t s)
+{
+    if (n_rows == 0) return GFDM_HIP_OK;
+    const void* syms = op == OP_MAP ? out : in;
+    if (((uintptr_t)syms % sizeof(cf)) || (op == OP_SOFT && (((uintptr_t)out % sizeof(float)) || ((uintptr_t)scale % sizeof(float)))) ||
+        ((uintptr_t)count % sizeof(int64_t)))
+        return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one element");
+    const MapperArgs a = { h->d_points, n_sym, n_rows, row_bytes_of(h->k, n_sym), static_cast<const int64_t*>(count), static_cast<const float*>(scale) };
+    switch (h->k) {
+    case 1: launch_k<1>(h, op, a, out, in, s); break;
+    case 2: launch_k<2>(h, op, a, out, in, s); break;
+    case 3: launch_k<3>(h, op, a, out, in, s); break;
+    case 4: launch_k<4>(h, op, a, out, in, s); break;
+    case 5: launch_k<5>(h, op, a, out, in, s); break;
+    case 6: launch_k<6>(h, op, a, out, in, s); break;
+    case 7: launch_k<7>(h, op, a, out, in, s); break;
+    default: launch_k<8>(h, op, a, out, in, s); break;
+    }
+    GFDM_TRY(hipGetLastError());
+    return GFDM_HIP_OK;
+}
+
+int check_call(const gfdm_hip_symbol_mapper* h, const void* out, const void* in, int64_t n_sym, int64_t n_rows)
+{
+    if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
+    const int rc = mapper_check(1 << h->k, n_sym, n_rows);
+    if (rc != GFDM_HIP_OK) return rc;
+    if (n_rows > 0 && (!out || !in)) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
+    return GFDM_HIP_OK;
+}
+
+int mapper_device(gfdm_hip_symbol_mapper* h, Op op, void* out, const void* in, const void* scale, const void* count, int64_t n_sym, int64_t n_rows, void* stream)
+{
+    const int rc = check_call(h, out, in, n_sym, n_rows);
+    if (rc != GFDM_HIP_OK) return rc;
+    DeviceGuard guard(h->ctx.device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    return mapper_enqueue(h, op, out, in, scale, count, n_sym, n_rows, (hipStream_t)stream);
+}
+
+// upload the rows (and the scale and the count), one enqueue on the handle's stream, download the result
+int mapper_host(gfdm_hip_symbol_mapper* h, Op op, void* out, const void* in, const float* scale, const int64_t* count, int64_t n_sym, int64_t n_rows)
+{
+    const int rc0 = check_call(h, out, in, n_sym, n_rows);
+    if (rc0 != GFDM_HIP_OK) return rc0;
+    if (n_rows == 0) return GFDM_HIP_OK;
+    DeviceGuard guard(h->ctx.device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    const size_t n = (size_t)n_rows, sym_bytes = n * (size_t)n_sym * sizeof(cf), packed = n * (size_t)row_bytes_of(h->k, n_sym),
+                 llr_bytes = n * (size_t)n_sym * h->k * sizeof(float);
+    const size_t ibytes = op == OP_MAP ? packed : sym_bytes, obytes = op == OP_MAP ? sym_bytes : op == OP_DECODE ? packed : llr_bytes;
+    DevBuf d_in, d_args, d_out;
+    GFDM_TRY(d_in.alloc(ibytes));
+    GFDM_TRY(d_args.alloc(sizeof(int64_t) + n * sizeof(float)));
+    GFDM_TRY(d_out.alloc(obytes));
+    int64_t* d_count = d_args.take<int64_t>(1);
+    float* d_scale = d_args.take<float>(n);
+    GFDM_TRY(gfdm::upload(d_in.p, in, ibytes, h->ctx.stream));
+    GFDM_TRY(gfdm::upload(d_count, count, sizeof(int64_t), h->ctx.stream));
+    GFDM_TRY(gfdm::upload(d_scale, scale, n * sizeof(float), h->ctx.stream));
+    const int rc = mapper_enqueue(h, op, d_out.p, d_in.p, scale ? d_scale : nullptr, count ? d_count : nullptr, n_sym, n_rows, h->ctx.stream);
+    if (rc != GFDM_HIP_OK) return rc;
+    GFDM_TRY(gfdm::download(out, d_out.p, obytes, h->ctx.stream));
+    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
+    return GFDM_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gfdm_hip_symbol_mapper_create(gfdm_hip_symbol_mapper** out, const float* points, int n_points, int decision, int device)
+{
+    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
+    *out = nullptr;
+    const int rc0 = mapper_check(n_points, 1, 0);
+    if (rc0 != GFDM_HIP_OK) return rc0;
+    if (!points) return api_fail(GFDM_HIP_EINVAL, "NULL constellation points");
+    if (decision < GFDM_HIP_DECIDE_AUTO || decision > GFDM_HIP_DECIDE_BPSK) return api_fail(GFDM_HIP_EINVAL, "bad decision rule");
+    const int rule = gfdm::resolve_decision(reinterpret_cast<const cf*>(points), n_points, decision);
+    if (rule < 0) return api_fail(GFDM_HIP_EINVAL, "decision rule does not match the number of constellation points");
+    gfdm_hip_symbol_mapper* h = new (std::nothrow) gfdm_hip_symbol_mapper();
+    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
+    h->k = bits_of(n_points);
+    h->rule = rule;
+    std::copy(reinterpret_cast<const cf*>(points), reinterpret_cast<const cf*>(points) + n_points, h->points);
+    int rc = h->ctx.open(device);
+    if (rc == GFDM_HIP_OK) {
+        DeviceGuard guard(device);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_points), (size_t)n_points * sizeof(cf));
+        if (e == hipSuccess) e = hipMemcpy(h->d_points, h->points, (size_t)n_points * sizeof(cf), hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = gfdm::api_fail_hip(e, "constellation upload");
+    }
+    if (rc != GFDM_HIP_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return GFDM_HIP_OK;
+}
+
+int gfdm_hip_symbol_mapper_destroy(gfdm_hip_symbol_mapper* m) { delete m; return GFDM_HIP_OK; }
+int gfdm_hip_symbol_mapper_bits_per_symbol(const gfdm_hip_symbol_mapper* m) { return m ? m->k : GFDM_HIP_EINVAL; }
+int gfdm_hip_symbol_mapper_n_points(const gfdm_hip_symbol_mapper* m) { return m ? 1 << m->k : GFDM_HIP_EINVAL; }
+int gfdm_hip_symbol_mapper_decision(const gfdm_hip_symbol_mapper* m) { return m ? m->rule : GFDM_HIP_EINVAL; }
+int gfdm_hip_symbol_mapper_points(const gfdm_hip_symbol_mapper* m, float* points)
+{
+    if (!m || !points) return api_fail(GFDM_HIP_EINVAL, "NULL handle or output");
+    std::copy(m->points, m->points + (1 << m->k), reinterpret_cast<cf*>(points));
+    return GFDM_HIP_OK;
+}
+int64_t gfdm_hip_symbol_mapper_row_bytes(const gfdm_hip_symbol_mapper* m, int64_t n_sym)
+{
+    if (!m) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
+    const int rc = mapper_check(1 << m->k, n_sym, 0);
+    return rc != GFDM_HIP_OK ? rc : row_bytes_of(m->k, n_sym);
+}
+int gfdm_hip_symbol_mapper_check(int n_points, int64_t n_sym, int64_t n_rows) { return mapper_check(n_points, n_sym, n_rows); }
+
+int gfdm_hip_symbol_mapper_map_device(gfdm_hip_symbol_mapper* m, void* out, const void* data, const void* count, int64_t n_sym, int64_t n_rows, void* stream)
+{
+    return mapper_device(m, OP_MAP, out, data, nullptr, count, n_sym, n_rows, stream);
+}
+int gfdm_hip_symbol_mapper_map_host(gfdm_hip_symbol_mapper* m, float* out, const uint8_t* data, const int64_t* count, int64_t n_sym, int64_t n_rows)
+{
+    return mapper_host(m, OP_MAP, out, data, nullptr, count, n_sym, n_rows);
+}
+int gfdm_hip_symbol_mapper_decode_device(gfdm_hip_symbol_mapper* m, void* out, const void* symbols, const void* count, int64_t n_sym, int64_t n_rows,
+                                         void* stream)
+{
+    return mapper_device(m, OP_DECODE, out, symbols, nullptr, count, n_sym, n_rows, stream);
+}
+int gfdm_hip_symbol_mapper_decode_host(gfdm_hip_symbol_mapper* m, uint8_t* out, const float* symbols, const int64_t* count, int64_t n_sym, int64_t n_rows)
+{
+    return mapper_host(m, OP_DECODE, out, symbols, nullptr, count, n_sym, n_rows);
+}
+int gfdm_hip_symbol_mapper_soft_device(gfdm_hip_symbol_mapper* m, void* out, const void* symbols, const void* scale, const void* count, int64_t n_sym,
+                                       int64_t n_rows, void* stream)
+{
+    return mapper_device(m, OP_SOFT, out, symbols, scale, count, n_sym, n_rows, stream);
+}
+int gfdm_hip_symbol_mapper_soft_host(gfdm_hip_symbol_mapper* m, float* out, const float* symbols, const float* scale, const int64_t* count, int64_t n_sym,
+                                     int64_t n_rows)
+{
+    return mapper_host(m, OP_SOFT, out, symbols, scale, count, n_sym, n_rows);
+}
+
+}  // extern "C"

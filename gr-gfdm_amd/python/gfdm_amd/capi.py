@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("GFDM_HIP_LIB") or os.path.join(LIB_DIR, "libgfdm_hip.
 
 OK, EINVAL_TAPS, EINVAL_OVERLAP, EINVAL, ENODEV, EHIP, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5, -6, -7
 DECIDE = {"auto": -1, "nearest": 0, "qpsk": 1, "bpsk": 2}
+DECIDE_AUTO, DECIDE_NEAREST, DECIDE_QPSK, DECIDE_BPSK = "auto", "nearest", "qpsk", "bpsk"      # the keys of DECIDE, as decision_rule() reports them
 
 _lib = None
 
@@ -226,6 +227,20 @@ def lib():
         "gfdm_hip_burst_shaper_place_device": (i32, [vp, vp, i64, vp, vp, vp, i64, vp, vp]),
         "gfdm_hip_burst_shaper_place_sc16_host": (i32, [vp, vp, i64, vp, vp, vp, i64, f64]),
         "gfdm_hip_burst_shaper_place_sc16_device": (i32, [vp, vp, i64, vp, vp, vp, i64, f64, vp, vp]),
+        "gfdm_hip_symbol_mapper_create": (i32, [ctypes.POINTER(vp), vp, i32, i32, i32]),
+        "gfdm_hip_symbol_mapper_destroy": (i32, [vp]),
+        "gfdm_hip_symbol_mapper_bits_per_symbol": (i32, [vp]),
+        "gfdm_hip_symbol_mapper_n_points": (i32, [vp]),
+        "gfdm_hip_symbol_mapper_decision": (i32, [vp]),
+        "gfdm_hip_symbol_mapper_points": (i32, [vp, vp]),
+        "gfdm_hip_symbol_mapper_row_bytes": (i64, [vp, i64]),
+        "gfdm_hip_symbol_mapper_check": (i32, [i32, i64, i64]),
+        "gfdm_hip_symbol_mapper_map_host": (i32, [vp, vp, vp, vp, i64, i64]),
+        "gfdm_hip_symbol_mapper_map_device": (i32, [vp, vp, vp, vp, i64, i64, vp]),
+        "gfdm_hip_symbol_mapper_decode_host": (i32, [vp, vp, vp, vp, i64, i64]),
+        "gfdm_hip_symbol_mapper_decode_device": (i32, [vp, vp, vp, vp, i64, i64, vp]),
+        "gfdm_hip_symbol_mapper_soft_host": (i32, [vp, vp, vp, vp, vp, i64, i64]),
+        "gfdm_hip_symbol_mapper_soft_device": (i32, [vp, vp, vp, vp, vp, i64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == the library does not export a declared symbol
@@ -1556,3 +1571,150 @@ class BurstShaper(_Kernel):
         else:
             _check(L.gfdm_hip_burst_shaper_place_host(self._h, optr, out_len, frames.ctypes.data, st.ctypes.data, cptr, n))
         return res
+
+
+class SymbolMapper(_Kernel):
+    """Payload bytes <-> constellation symbols, and max-log soft bits (contract in include/gfdm_hip.h, gfdm_hip_symbol_mapper): map() is
+    repack_bits_bb(8 -> k, MSB first) + chunks_to_symbols in front of Transmitter.transmit, decode() is constellation_decoder_cb +
+    repack_bits_bb(k -> 8) behind demodulate_frames / demodulate_estimated / demodulate_bursts, soft() feeds a decoder instead.  Rows are
+    frames or bursts: symbols are (n_rows, n_sym), packed bytes (n_rows, row_bytes(n_sym)), soft bits (n_rows, n_sym * k); a 1-D input is
+    one row and gives a 1-D result.  numpy arrays run the host flavour; torch device tensors (uint8 / complex64 / float32) the device
+    flavour on the current stream unless given.  count (an int, or on the device path a one-element int64 tensor such as detect's) limits
+    the call to the first count rows, the rest is written as zeros; it is clamped to [0, n_rows]."""
+    _destroy = "gfdm_hip_symbol_mapper_destroy"
+
+    def __init__(self, points, decision=DECIDE_AUTO, device=0):
+        pts = _c64(np.asarray(points).ravel())
+        h = ctypes.c_void_p()
+        _check(lib().gfdm_hip_symbol_mapper_create(ctypes.byref(h), pts.ctypes.data, pts.size, DECIDE.get(decision, decision), device))
+        self._h = h
+        self._dev = int(device)
+        self._k = lib().gfdm_hip_symbol_mapper_bits_per_symbol(h)
+
+    def bits_per_symbol(self):
+        return self._k
+
+    def points(self):
+        """the points as given to the constructor (complex64, bit for bit)"""
+        p = np.empty(lib().gfdm_hip_symbol_mapper_n_points(self._h), np.complex64)
+        _check(lib().gfdm_hip_symbol_mapper_points(self._h, p.ctypes.data))
+        return p
+
+    def decision_rule(self):
+        """'nearest' | 'qpsk' | 'bpsk': the rule decode() runs (gfdm_hip_symbol_mapper_decision)"""
+        code = lib().gfdm_hip_symbol_mapper_decision(self._h)
+        return {v: k for k, v in DECIDE.items() if k != "auto"}[code]
+
+    def row_bytes(self, n_sym):
+        """bytes of a packed row of n_sym symbols: ceil(n_sym * k / 8)"""
+        n = lib().gfdm_hip_symbol_mapper_row_bytes(self._h, int(n_sym))
+        if n < 0:
+            _check(n)
+        return n
+
+    def _rows(self, x, dtype, what, width=None):
+        """x as rows of `dtype` -> (x, n_rows, width, was 1-D); nothing touches the device"""
+        name = np.dtype(dtype).name
+        if _is_tensor(x):
+            if str(x.dtype).replace("torch.", "") != name or not x.is_cuda or not x.is_contiguous():
+                raise TypeError("%s must be a contiguous %s CUDA/HIP tensor" % (what, name))
+            if x.device.index != self._dev:
+                raise RuntimeError("%s lives on GPU %d, the handle on GPU %d" % (what, x.device.index, self._dev))
+        else:
+            x = np.asarray(x)
+            if dtype == np.uint8 and x.dtype != np.uint8:
+                raise TypeError("%s must be uint8 (packed bytes), not %s" % (what, x.dtype))
+            if dtype == np.complex64 and not (np.issubdtype(x.dtype, np.floating) or np.issubdtype(x.dtype, np.complexfloating)):
+                raise TypeError("%s must be complex symbols, not %s" % (what, x.dtype))
+            x = np.ascontiguousarray(x, dtype=dtype)
+        if x.ndim not in (1, 2):
+            raise ValueError("%s must be (n_rows, n) or one row (n,), not %s" % (what, tuple(x.shape)))
+        flat = x.ndim == 1
+        n_rows, w = (1, x.shape[0]) if flat else (x.shape[0], x.shape[1])
+        if width is not None and w != width:
+            raise RuntimeError("%s has rows of %d elements, expected %d" % (what, w, width))
+        return x, int(n_rows), int(w), flat
+
+    def _result(self, out, like, shape, dtype, flat):
+        name = np.dtype(dtype).name
+        shape = shape[1:] if flat else shape
+        if out is None:
+            if _is_tensor(like):
+                import torch
+                return torch.empty(shape, dtype=getattr(torch, name), device=like.device)
+            return np.empty(shape, dtype)
+        if _is_tensor(out) != _is_tensor(like) or (not _is_tensor(out) and not isinstance(out, np.ndarray)):
+            raise TypeError("out must be a %s, as the input is" % ("CUDA/HIP tensor" if _is_tensor(like) else "numpy array"))
+        if str(out.dtype).replace("torch.", "") != name or not (out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous):
+            raise TypeError("out must be contiguous %s" % name)
+        if _is_tensor(out) and (not out.is_cuda or out.device.index != self._dev):
+            raise RuntimeError("out must live on GPU %d, as the handle does" % self._dev)
+        if int(np.prod(out.shape)) != int(np.prod(shape)):
+            raise RuntimeError("out holds %d elements, expected %d" % (int(np.prod(out.shape)), int(np.prod(shape))))
+        return out
+
+    def _count(self, count, like, keep):
+        """pointer of the optional count (None: every row)"""
+        if count is None:
+            return None
+        if _is_tensor(like):
+            import torch
+            if not _is_tensor(count):
+                count = torch.full((1,), int(count), dtype=torch.int64, device=like.device)
+            keep.append(count)
+            return _dev_arg(count, torch.int64, 1, "count", self._dev)
+        if _is_tensor(count):
+            raise TypeError("count must be an int on the host path")
+        keep.append(np.array([int(count)], np.int64))
+        return keep[-1].ctypes.data
+
+    @staticmethod
+    def _ptr(a):
+        return a.data_ptr() if _is_tensor(a) else a.ctypes.data
+
+    def _run(self, name, res, x, extra, count, n_sym, n_rows, stream):
+        keep = []
+        cptr = self._count(count, x, keep)
+        L = lib()
+        _check(L.gfdm_hip_symbol_mapper_check(1 << self._k, n_sym, n_rows))
+        if _is_tensor(x):
+            _check(getattr(L, name + "_device")(self._h, self._ptr(res), self._ptr(x), *extra, cptr, n_sym, n_rows, self._sp(stream)))
+        else:
+            _check(getattr(L, name + "_host")(self._h, self._ptr(res), self._ptr(x), *extra, cptr, n_sym, n_rows))
+        return res
+
+    def map(self, data, n_sym, count=None, out=None, stream=None):
+        """packed bytes (n_rows, row_bytes(n_sym)) uint8 -> symbols (n_rows, n_sym) complex64: points[index], a bit copy"""
+        n_sym = int(n_sym)
+        data, n_rows, _, flat = self._rows(data, np.uint8, "data", self.row_bytes(n_sym))
+        res = self._result(out, data, (n_rows, n_sym), np.complex64, flat)
+        return self._run("gfdm_hip_symbol_mapper_map", res, data, (), count, n_sym, n_rows, stream)
+
+    def decode(self, symbols, count=None, out=None, stream=None):
+        """symbols (n_rows, n_sym) complex64 -> packed bytes (n_rows, row_bytes(n_sym)) uint8, by the rule of decision_rule()"""
+        symbols, n_rows, n_sym, flat = self._rows(symbols, np.complex64, "symbols")
+        _check(lib().gfdm_hip_symbol_mapper_check(1 << self._k, n_sym, n_rows))
+        res = self._result(out, symbols, (n_rows, self.row_bytes(n_sym)), np.uint8, flat)
+        return self._run("gfdm_hip_symbol_mapper_decode", res, symbols, (), count, n_sym, n_rows, stream)
+
+    def soft(self, symbols, scale=None, count=None, out=None, stream=None):
+        """symbols (n_rows, n_sym) complex64 -> max-log LLRs (n_rows, n_sym * k) float32, positive for bit 0; scale: float32 (n_rows,), one
+        factor per row (typically 1 / sigma^2), a device tensor when symbols is one"""
+        symbols, n_rows, n_sym, flat = self._rows(symbols, np.complex64, "symbols")
+        _check(lib().gfdm_hip_symbol_mapper_check(1 << self._k, n_sym, n_rows))
+        sptr = None
+        if scale is not None:
+            if _is_tensor(symbols):
+                import torch
+                if not _is_tensor(scale):
+                    raise TypeError("scale must be a float32 CUDA/HIP tensor, as symbols is a tensor")
+                sptr = _dev_arg(scale, torch.float32, n_rows, "scale", self._dev)
+            else:
+                if _is_tensor(scale):
+                    raise TypeError("scale must be a host array, as symbols is one")
+                scale = np.ascontiguousarray(scale, dtype=np.float32).ravel()
+                if scale.size != n_rows:
+                    raise RuntimeError("scale has %d elements, expected %d" % (scale.size, n_rows))
+                sptr = scale.ctypes.data
+        res = self._result(out, symbols, (n_rows, n_sym * self._k), np.float32, flat)
+        return self._run("gfdm_hip_symbol_mapper_soft", res, symbols, (sptr,), count, n_sym, n_rows, stream)

@@ -686,6 +686,70 @@ int gfdm_hip_burst_shaper_place_sc16_host(gfdm_hip_burst_shaper* s, int16_t* out
 int gfdm_hip_burst_shaper_place_sc16_device(gfdm_hip_burst_shaper* s, void* out, int64_t out_len, const void* frames, const void* starts,
                                             const void* count, int64_t n_bursts, double peak, void* workspace, void* stream);
 
+/* ---- gfdm_hip_symbol_mapper: payload bytes to symbols and back, and soft bits -------------------------------------------------------
+ * The two ends of the chain: in front of the transmitter GNU Radio's repack_bits_bb (8 -> k bits, GR_MSB_FIRST) + chunks_to_symbols
+ * (symbol_table = constellation.points()), behind the receivers constellation_decoder_cb (decision_maker) + repack_bits_bb (k -> 8,
+ * GR_MSB_FIRST); pygfdm's bits2symbols / symbols2bits (python/pygfdm/symbolmapping.py).  All calls are batched over ROWS: a row is one
+ * frame's or one burst's symbols -- the [n_frames][input_vector_size] the transmitter takes, the [n_bursts][noutput_size] the
+ * demodulate_frames / _estimated / _bursts calls return, with detect's count.
+ * Constellation: n_points = 2^k complex64 points, 1 <= k <= 8 (anything else is GFDM_HIP_EINVAL); duplicate points are allowed.
+ *   `decision` is a gfdm_hip_decision with the meaning it has for gfdm_hip_advanced_receiver_create: AUTO resolves to the sign tests only
+ *   for GNU Radio's unit QPSK / BPSK points (every component within 6 * FLT_EPSILON relative, the one rule both constructors share) and
+ *   to NEAREST otherwise; an explicit QPSK / BPSK over other points runs as NEAREST; a rule that does not fit n_points is EINVAL.
+ *   gfdm_hip_symbol_mapper_decision reports the rule the handle runs (never AUTO).
+ * Bit order: a symbol's value is its point index; bit j of a symbol is bit k-1-j of the index (j = 0 is the most significant).  A row of
+ *   n_sym symbols is n_sym k bits, packed MSB-first into row_bytes = ceil(n_sym k / 8) bytes; every row starts on a byte; the unused low
+ *   bits of a row's last byte are written as 0 by decode and ignored by map.  (repack_bits_bb(..., GR_MSB_FIRST) with align_output;
+ *   np.packbits / np.unpackbits; pygfdm's pack_bits.)
+ * map:    bytes [n_rows][row_bytes] -> symbols [n_rows][n_sym]:  out[r][i] = points[index], a bit copy of the point as given to create.
+ * decode: symbols [n_rows][n_sym] -> bytes [n_rows][row_bytes].  The index of a symbol x, in fp32:
+ *     QPSK     index = 2 * (im > 0) + (re > 0)
+ *     BPSK     index = (re > 0)
+ *     NEAREST  the first i that minimises d_i = (x.re - p_i.re)^2 + (x.im - p_i.im)^2; the comparison is strict and starts from +inf.
+ *   From these formulas: NaN decodes to index 0 under every rule; an infinite component decodes to index 0 under NEAREST (no d_i is
+ *   below +inf) and by its sign under the sign tests.
+ * soft:   symbols [n_rows][n_sym] -> float32 [n_rows][n_sym k], max-log: for bit j of a symbol of row r
+ *     llr = s_r * (min over i with bit_j(i) = 1 of d_i  -  min over i with bit_j(i) = 0 of d_i),
+ *   d_i the squared distance in the direct form above (never the expanded |x|^2 - 2 Re(x conj p) + |p|^2, which cancels), all in fp32:
+ *   positive means bit 0.  `scale` is an optional float32 [n_rows] holding s_r, typically 1 / sigma^2 per burst (NULL: 1; a device array
+ *   in the device flavour).  The rule of `decision` plays no part.  A non-finite input symbol makes that symbol's k values unspecified,
+ *   and only those.  Against the same formula in float64 a value differs by at most 8 * 2^-24 |s_r| (d0 + d1), d0 and d1 the two minima.
+ * count: an optional int64 (on the device in the device flavour; NULL = n_rows -- detect's count as it is).  With
+ *   n_live = clamp(*count, 0, n_rows) the rows from n_live on are written as zeros (decode: zero bytes, soft: 0.0f, map: 0 + 0j) and
+ *   their input is never read.  Every output element of the n_rows rows is written exactly once whatever count is, by the one kernel of
+ *   the call: there is no memset in front, so a graph replay with a changed count is correct.
+ * *_device: every array is a device array.  The call neither allocates nor synchronises, needs no workspace and is hipGraph-capturable
+ *   (one kernel).  Buffers need the alignment of one element and no more -- 8 bytes for symbols, 1 byte for packed bytes, 4 bytes for LLRs
+ *   and scale -- so a block of rows may start anywhere inside a larger buffer; byte offsets are 64-bit.  The grid depends on the total
+ *   size, never on n_rows: many short rows and one long row spread alike.
+ * *_host: a convenience, not a pipeline: uploads the rows (and scale, count), runs the device call, downloads the result.
+ * GFDM_HIP_EINVAL from check (the argument table alone, without a handle or a device) and from every call: n_points not 2^1 .. 2^8;
+ *   n_sym < 1; n_rows < 0; byte sizes (8 n_rows n_sym, 4 k n_rows n_sym) that overflow int64.  Also: a NULL buffer that the call would
+ *   touch.  n_rows == 0 returns GFDM_HIP_OK without a launch.
+ * Tested range (against a numpy restatement of the above in float64 on the float32 inputs, and pygfdm's own bits2symbols / symbols2bits):
+ *   k = 1, 2, 3, 4, 6, 8; n_sym 1, 3, 5, 7, 8, 63, 64, 65, 257, 468, 4097; 1, 7, 5000 (of 3 symbols) and 32768 + 7 (of 5 symbols) rows per
+ *   call; buffers at every alignment of one element; count below, at and beyond n_rows. */
+typedef struct gfdm_hip_symbol_mapper gfdm_hip_symbol_mapper;
+int gfdm_hip_symbol_mapper_create(gfdm_hip_symbol_mapper** out, const float* points, int n_points, int decision, int device);
+int gfdm_hip_symbol_mapper_destroy(gfdm_hip_symbol_mapper* m);
+int gfdm_hip_symbol_mapper_bits_per_symbol(const gfdm_hip_symbol_mapper* m);
+int gfdm_hip_symbol_mapper_n_points(const gfdm_hip_symbol_mapper* m);
+int gfdm_hip_symbol_mapper_decision(const gfdm_hip_symbol_mapper* m);
+int gfdm_hip_symbol_mapper_points(const gfdm_hip_symbol_mapper* m, float* points);          /* 2 n_points floats: re, im */
+int64_t gfdm_hip_symbol_mapper_row_bytes(const gfdm_hip_symbol_mapper* m, int64_t n_sym);
+int gfdm_hip_symbol_mapper_check(int n_points, int64_t n_sym, int64_t n_rows);
+int gfdm_hip_symbol_mapper_map_host(gfdm_hip_symbol_mapper* m, float* out, const uint8_t* data, const int64_t* count, int64_t n_sym, int64_t n_rows);
+int gfdm_hip_symbol_mapper_map_device(gfdm_hip_symbol_mapper* m, void* out, const void* data, const void* count, int64_t n_sym, int64_t n_rows,
+                                      void* stream);
+int gfdm_hip_symbol_mapper_decode_host(gfdm_hip_symbol_mapper* m, uint8_t* out, const float* symbols, const int64_t* count, int64_t n_sym,
+                                       int64_t n_rows);
+int gfdm_hip_symbol_mapper_decode_device(gfdm_hip_symbol_mapper* m, void* out, const void* symbols, const void* count, int64_t n_sym, int64_t n_rows,
+                                         void* stream);
+int gfdm_hip_symbol_mapper_soft_host(gfdm_hip_symbol_mapper* m, float* out, const float* symbols, const float* scale, const int64_t* count,
+                                     int64_t n_sym, int64_t n_rows);
+int gfdm_hip_symbol_mapper_soft_device(gfdm_hip_symbol_mapper* m, void* out, const void* symbols, const void* scale, const void* count,
+                                       int64_t n_sym, int64_t n_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
