@@ -19,6 +19,7 @@
 // independent of order.
 #include "../../include/gfdm_hip.h"
 #include "gfdm_hostcall.h"
+#include "gfdm_sc16out.h"
 
 #include <algorithm>
 #include <climits>
@@ -31,6 +32,7 @@ using gfdm::cf;
 using gfdm::api_fail;
 using gfdm::DeviceGuard;
 using gfdm::DevBuf;
+using gfdm::pack_sc16;          // the sc16 output rule: gfdm_sc16out.h
 
 namespace {
 
@@ -142,17 +144,6 @@ __device__ __forceinline__ void vector_from_window(const ShapeArgs& a, int64_t i
         const uint64_t k = (uint64_t)i - (uint64_t)st;
         if (k < (uint64_t)a.F) y[j] = scaled(a, a.frames[(c0 - 1 + idx) * a.F + (int64_t)k]);
     }
-}
-
-// truncation toward zero, saturated to int16; NaN gives 0
-__device__ __forceinline__ int q16(float v)
-{
-    if (v != v) return 0;
-    return (int)fminf(fmaxf(v, -32768.f), 32767.f);
-}
-__device__ __forceinline__ unsigned pack_sc16(cf y, float g)
-{
-    return ((unsigned)q16(y.x * g) & 0xFFFFu) | ((unsigned)q16(y.y * g) << 16);
 }
 
 template <int SC16>

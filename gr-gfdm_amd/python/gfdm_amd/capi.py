@@ -46,6 +46,7 @@ def lib():
         pass
     L = ctypes.CDLL(LIB_PATH)
     vp, i32, i64, cp, f32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_float, ctypes.c_double
+    u64 = ctypes.c_uint64
     sig = {
         "gfdm_hip_strerror": (cp, [i32]),
         "gfdm_hip_last_error": (cp, []),
@@ -241,6 +242,21 @@ def lib():
         "gfdm_hip_symbol_mapper_decode_device": (i32, [vp, vp, vp, vp, i64, i64, vp]),
         "gfdm_hip_symbol_mapper_soft_host": (i32, [vp, vp, vp, vp, vp, i64, i64]),
         "gfdm_hip_symbol_mapper_soft_device": (i32, [vp, vp, vp, vp, vp, i64, i64, vp]),
+        "gfdm_hip_channel_model_create": (i32, [ctypes.POINTER(vp), vp, i32, f64, f64, u64, i32]),
+        "gfdm_hip_channel_model_destroy": (i32, [vp]),
+        "gfdm_hip_channel_model_n_taps": (i32, [vp]),
+        "gfdm_hip_channel_model_taps": (i32, [vp, vp]),
+        "gfdm_hip_channel_model_frequency_offset": (i32, [vp, ctypes.POINTER(f64)]),
+        "gfdm_hip_channel_model_noise_voltage": (i32, [vp, ctypes.POINTER(f64)]),
+        "gfdm_hip_channel_model_seed": (i32, [vp, ctypes.POINTER(u64)]),
+        "gfdm_hip_channel_model_set_frequency_offset": (i32, [vp, f64]),
+        "gfdm_hip_channel_model_set_noise_voltage": (i32, [vp, f64]),
+        "gfdm_hip_channel_model_set_seed": (i32, [vp, u64]),
+        "gfdm_hip_channel_model_check": (i32, [i32, f64, f64, i64, i64, i64, f64]),
+        "gfdm_hip_channel_model_apply_host": (i32, [vp, vp, vp, i64, i64, i64]),
+        "gfdm_hip_channel_model_apply_device": (i32, [vp, vp, vp, i64, i64, i64, vp]),
+        "gfdm_hip_channel_model_apply_sc16_host": (i32, [vp, vp, vp, i64, i64, i64, f64]),
+        "gfdm_hip_channel_model_apply_sc16_device": (i32, [vp, vp, vp, i64, i64, i64, f64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == the library does not export a declared symbol
@@ -1439,20 +1455,20 @@ class BurstShaper(_Kernel):
         return float(peak)
 
     @staticmethod
-    def _kinds(frames, out, sc16):
+    def _kinds(frames, out, sc16, what="frames"):
         """what can be said of frames and out without the handle (kind, dtype, layout): raised before the library is asked"""
         if _is_tensor(frames):
             import torch
             if frames.dtype != torch.complex64 or not frames.is_cuda or not frames.is_contiguous():
-                raise TypeError("frames must be a contiguous complex64 CUDA/HIP tensor")
+                raise TypeError("%s must be a contiguous complex64 CUDA/HIP tensor" % what)
         else:
             a = np.asarray(frames)
             if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.complexfloating)):
-                raise TypeError("frames must be complex samples, not %s" % a.dtype)
+                raise TypeError("%s must be complex samples, not %s" % (what, a.dtype))
             frames = _c64(a).ravel()
         if out is not None:
             if _is_tensor(out) != _is_tensor(frames):
-                raise TypeError("out must be a %s, as frames is" % ("CUDA/HIP tensor" if _is_tensor(frames) else "numpy array"))
+                raise TypeError("out must be a %s, as %s is" % ("CUDA/HIP tensor" if _is_tensor(frames) else "numpy array", what))
             if not _is_tensor(out) and not isinstance(out, np.ndarray):
                 raise TypeError("out must be a numpy array")
             have = str(out.dtype).replace("torch.", "")
@@ -1718,3 +1734,107 @@ class SymbolMapper(_Kernel):
                 sptr = scale.ctypes.data
         res = self._result(out, symbols, (n_rows, n_sym * self._k), np.float32, flat)
         return self._run("gfdm_hip_symbol_mapper_soft", res, symbols, (sptr,), count, n_sym, n_rows, stream)
+
+
+def awgn_noise_voltage(signal, snr_db, rate=1.0):
+    """ChannelModel's noise_voltage for `snr_db` on `signal`: sqrt(2 * v), v pygfdm's calculate_awgn_noise_variance (python/pygfdm/utils.py:
+    106-110, the variance PER COMPONENT: average sample energy / (2 * rate * 10^(snr_db / 10))) -- the noise power of the channel model is
+    noise_voltage^2 = 2 v.  `signal` is a numpy array or a torch tensor; the energy of a tensor is summed on its device."""
+    if _is_tensor(signal):
+        flat = signal.reshape(-1)
+        energy, n = float((flat.real.double() ** 2 + flat.imag.double() ** 2).sum().item()) if flat.is_complex() else float((flat.double() ** 2).sum().item()), flat.numel()
+    else:
+        flat = np.asarray(signal).ravel()
+        energy, n = float(np.sum(flat.real.astype(np.float64) ** 2 + flat.imag.astype(np.float64) ** 2)), flat.size
+    if n == 0:
+        raise ValueError("signal is empty")
+    if not rate > 0:
+        raise ValueError("rate must be > 0")
+    variance = (energy / n) / (2 * rate * 10.0 ** (snr_db / 10.0))
+    return float(np.sqrt(2.0 * variance))
+
+
+class ChannelModel(_Kernel):
+    """Multipath, frequency offset and noise on a stream, on the device (contract in include/gfdm_hip.h, gfdm_hip_channel_model): GNU
+    Radio's channels.channel_model in its argument order, between BurstShaper.place and BurstSync.detect.  y = FIR(taps) of x, times
+    exp(j 2 pi frequency_offset n), plus white Gaussian noise of power noise_voltage^2 that is a pure function of (noise_seed, absolute
+    sample index).  epsilon (the timing offset) must be 1.0: resampling is not part of this.  The taps are fixed; frequency_offset,
+    noise_voltage and seed have setters, and a captured graph keeps the values it was captured with."""
+    _destroy = "gfdm_hip_channel_model_destroy"
+
+    def __init__(self, noise_voltage=0.0, frequency_offset=0.0, epsilon=1.0, taps=(1,), noise_seed=0, device=None):
+        if float(epsilon) != 1.0:
+            raise ValueError("epsilon must be 1.0: the timing offset (resampling) of channel_model is not part of this")
+        t = _c64(np.asarray(taps).ravel())
+        h = ctypes.c_void_p()
+        dev = 0 if device is None else int(device)
+        _check(lib().gfdm_hip_channel_model_create(ctypes.byref(h), t.ctypes.data, t.size, float(frequency_offset), float(noise_voltage),
+                                                   int(noise_seed) & 0xFFFFFFFFFFFFFFFF, dev))
+        self._h = h
+        self._dev = dev
+
+    def n_taps(self):
+        return lib().gfdm_hip_channel_model_n_taps(self._h)
+
+    def taps(self):
+        """the taps as given to the constructor (complex64, bit for bit)"""
+        t = np.empty(self.n_taps(), np.complex64)
+        _check(lib().gfdm_hip_channel_model_taps(self._h, t.ctypes.data))
+        return t
+
+    def frequency_offset(self):
+        v = ctypes.c_double()
+        _check(lib().gfdm_hip_channel_model_frequency_offset(self._h, ctypes.byref(v)))
+        return v.value
+
+    def noise_voltage(self):
+        v = ctypes.c_double()
+        _check(lib().gfdm_hip_channel_model_noise_voltage(self._h, ctypes.byref(v)))
+        return v.value
+
+    def seed(self):
+        v = ctypes.c_uint64()
+        _check(lib().gfdm_hip_channel_model_seed(self._h, ctypes.byref(v)))
+        return v.value
+
+    def set_frequency_offset(self, frequency_offset):
+        _check(lib().gfdm_hip_channel_model_set_frequency_offset(self._h, float(frequency_offset)))
+
+    def set_noise_voltage(self, noise_voltage):
+        _check(lib().gfdm_hip_channel_model_set_noise_voltage(self._h, float(noise_voltage)))
+
+    def set_seed(self, noise_seed):
+        _check(lib().gfdm_hip_channel_model_set_seed(self._h, int(noise_seed) & 0xFFFFFFFFFFFFFFFF))
+
+    _kinds = staticmethod(BurstShaper._kinds)
+    _out = BurstShaper._out
+
+    def apply(self, x, history=0, offset=0, sc16=False, gain=1.0, out=None, stream=None):
+        """x holds history + n samples, the result has n: sample i of the result is the channel's output for x[history + i], whose absolute
+        index is offset + i; the first `history` samples are the FIR's past (GNU Radio's history; what lies before them is zeros).  A stream
+        cut into calls gives the samples of one call when each piece passes history = min(n_taps - 1, samples before it) and its offset.
+        numpy x -> numpy result (host path); a torch complex64 device tensor -> a tensor on its device (device path, current stream unless
+        given).  sc16=True writes int16 I/Q of shape (n, 2), truncated and saturated, of y * gain."""
+        if not sc16 and float(gain) != 1.0:
+            raise ValueError("gain scales sc16 output: pass sc16=True (complex64 output is not scaled)")
+        x = self._kinds(x, out, sc16, "x")
+        history, offset = int(history), int(offset)
+        size = x.numel() if _is_tensor(x) else x.size
+        if history < 0 or history > size:
+            raise ValueError("history(%d) must lie in 0 .. the size of x(%d)" % (history, size))
+        n = size - history
+        res, optr = self._out(out, n, sc16, x)
+        L = lib()
+        if _is_tensor(x):
+            xptr = self._dp(x, size, "x") + 8 * history
+            if sc16:
+                _check(L.gfdm_hip_channel_model_apply_sc16_device(self._h, optr, xptr, n, history, offset, float(gain), self._sp(stream)))
+            else:
+                _check(L.gfdm_hip_channel_model_apply_device(self._h, optr, xptr, n, history, offset, self._sp(stream)))
+            return res
+        xptr = x.ctypes.data + 8 * history
+        if sc16:
+            _check(L.gfdm_hip_channel_model_apply_sc16_host(self._h, optr, xptr, n, history, offset, float(gain)))
+        else:
+            _check(L.gfdm_hip_channel_model_apply_host(self._h, optr, xptr, n, history, offset))
+        return res
