@@ -16,6 +16,7 @@
 // The point table sits in LDS (none for the sign tests).  Rows from n_live on are written as zeros by the same kernel and their input
 // is never read; nothing is written outside the output and every element of it once.
 #include "../../include/gfdm_hip.h"
+#include "gfdm_decide.h"
 #include "gfdm_hostcall.h"
 
 #include <algorithm>
@@ -23,6 +24,10 @@
 #include <new>
 
 using gfdm::cf;
+using gfdm::RowPos;
+using gfdm::advance;
+using gfdm::dist2;
+using gfdm::decide2;                 // gfdm_decide.h: shared with the link meter
 using gfdm::api_fail;
 using gfdm::DeviceGuard;
 using gfdm::DevBuf;
@@ -48,55 +53,6 @@ __device__ __forceinline__ int64_t live_rows(const MapperArgs& a)
 {
     if (!a.count) return a.n_rows;
     return std::min(std::max(*a.count, (int64_t)0), a.n_rows);
-}
-
-// (row, index in the row) of the flat element d behind the one at (r0, i0); rows of n elements, i0 < n.  No 64-bit division: past the
-// first row what is left of d is below 2^32, and so is n where a quotient is needed at all.
-struct RowPos { int64_t r, i; };
-__device__ __forceinline__ RowPos advance(int64_t r0, int64_t i0, uint32_t d, int64_t n)
-{
-    RowPos p = { r0, i0 + (int64_t)d };
-    if (p.i >= n) {
-        p.i -= n;
-        ++p.r;
-        if (p.i >= n) {
-            const uint32_t q = (uint32_t)p.i / (uint32_t)n;
-            p.r += q;
-            p.i -= (int64_t)q * n;
-        }
-    }
-    return p;
-}
-
-// squared distance in the direct form: the contract's d_i
-__device__ __forceinline__ float dist2(cf x, cf p)
-{
-    const float dr = x.x - p.x, di = x.y - p.y;
-    return dr * dr + di * di;
-}
-
-// RULE: a gfdm_hip_decision (never AUTO).  NEAREST: the first strict minimum starting from +inf (decide_point of gfdm_rowlane_impl.h), so
-// NaN and infinite inputs give index 0; the sign tests are '> 0', so NaN gives 0 and an infinite component decides by its sign.
-template <int K, int RULE>
-__device__ __forceinline__ void decide2(cf x0, cf x1, const cf* pts, int& i0, int& i1)
-{
-    if constexpr (RULE == GFDM_HIP_DECIDE_QPSK) {
-        i0 = 2 * (x0.y > 0.f) + (x0.x > 0.f);
-        i1 = 2 * (x1.y > 0.f) + (x1.x > 0.f);
-    } else if constexpr (RULE == GFDM_HIP_DECIDE_BPSK) {
-        i0 = (x0.x > 0.f);
-        i1 = (x1.x > 0.f);
-    } else {
-        float b0 = __builtin_huge_valf(), b1 = __builtin_huge_valf();
-        i0 = i1 = 0;
-#pragma unroll 16
-        for (int i = 0; i < (1 << K); ++i) {
-            const cf p = pts[i];                    // the same LDS address in every lane: a broadcast
-            const float d0 = dist2(x0, p), d1 = dist2(x1, p);
-            if (d0 < b0) { b0 = d0; i0 = i; }
-            if (d1 < b1) { b1 = d1; i1 = i; }
-        }
-    }
 }
 
 // the 16-byte vector v of the symbol array (symbols 2 v - mis, 2 v - mis + 1 of the flat input; those outside [0, s_end) read as 0)

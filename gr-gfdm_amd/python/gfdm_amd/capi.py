@@ -257,6 +257,21 @@ def lib():
         "gfdm_hip_channel_model_apply_device": (i32, [vp, vp, vp, i64, i64, i64, vp]),
         "gfdm_hip_channel_model_apply_sc16_host": (i32, [vp, vp, vp, i64, i64, i64, f64]),
         "gfdm_hip_channel_model_apply_sc16_device": (i32, [vp, vp, vp, i64, i64, i64, f64, vp]),
+        "gfdm_hip_link_meter_create": (i32, [ctypes.POINTER(vp), vp, i32, i32, i32]),
+        "gfdm_hip_link_meter_destroy": (i32, [vp]),
+        "gfdm_hip_link_meter_bits_per_symbol": (i32, [vp]),
+        "gfdm_hip_link_meter_n_points": (i32, [vp]),
+        "gfdm_hip_link_meter_decision": (i32, [vp]),
+        "gfdm_hip_link_meter_row_bytes": (i64, [vp, i64]),
+        "gfdm_hip_link_meter_totals_device": (vp, [vp]),
+        "gfdm_hip_link_meter_reset": (i32, [vp, vp]),
+        "gfdm_hip_link_meter_totals": (i32, [vp, vp, vp]),
+        "gfdm_hip_link_meter_match_workspace_bytes": (i64, [i64]),
+        "gfdm_hip_link_meter_measure_workspace_bytes": (i64, [i64, i64]),
+        "gfdm_hip_link_meter_match_host": (i32, [vp, vp, vp, vp, vp, i64, vp, i64, i64, i64]),
+        "gfdm_hip_link_meter_match_device": (i32, [vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, vp]),
+        "gfdm_hip_link_meter_measure_host": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64]),
+        "gfdm_hip_link_meter_measure_device": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == the library does not export a declared symbol
@@ -1837,4 +1852,194 @@ class ChannelModel(_Kernel):
             _check(L.gfdm_hip_channel_model_apply_sc16_host(self._h, optr, xptr, n, history, offset, float(gain)))
         else:
             _check(L.gfdm_hip_channel_model_apply_host(self._h, optr, xptr, n, history, offset))
+        return res
+
+
+class LinkMeter(_Kernel):
+    """Closing the loop on the device (contract in include/gfdm_hip.h, gfdm_hip_link_meter): match() pairs BurstSync.detect's detections
+    with the bursts that were sent, measure() counts bit / symbol / row errors of demodulated rows against the sent payload with the
+    decisions SymbolMapper.decode makes and gives every row's error-vector power (data-aided: the EVM; without a payload: the
+    decision-directed noise estimate SymbolMapper.soft's scale asks for), and every call adds to twelve counters that stay on the device
+    until totals() reads them -- the one read of a curve point.  Constructor arguments as SymbolMapper's.  numpy arrays run the host
+    flavour; torch device tensors the device flavour on the current stream unless given.  count is an int or (device path) detect's
+    one-element int64 tensor.  out: a dict with any of the result's keys, to write into existing arrays; workspace: a uint8 device
+    tensor of match_workspace_bytes() / measure_workspace_bytes() to use instead of a new one."""
+    _destroy = "gfdm_hip_link_meter_destroy"
+    FIELDS = ("rows", "symbols", "bits", "bit_errors", "symbol_errors", "row_errors", "detections", "matched", "missed", "false_alarms")
+
+    def __init__(self, points, decision=DECIDE_AUTO, device=0):
+        pts = _c64(np.asarray(points).ravel())
+        h = ctypes.c_void_p()
+        _check(lib().gfdm_hip_link_meter_create(ctypes.byref(h), pts.ctypes.data, pts.size, DECIDE.get(decision, decision), device))
+        self._h = h
+        self._dev = int(device)
+        self._k = lib().gfdm_hip_link_meter_bits_per_symbol(h)
+
+    def bits_per_symbol(self):
+        return self._k
+
+    def decision_rule(self):
+        """'nearest' | 'qpsk' | 'bpsk': the rule measure() decides by (SymbolMapper.decode's for the same points)"""
+        code = lib().gfdm_hip_link_meter_decision(self._h)
+        return {v: k for k, v in DECIDE.items() if k != "auto"}[code]
+
+    def row_bytes(self, n_sym):
+        n = lib().gfdm_hip_link_meter_row_bytes(self._h, int(n_sym))
+        if n < 0:
+            _check(n)
+        return n
+
+    @staticmethod
+    def match_workspace_bytes(n_sent):
+        n = lib().gfdm_hip_link_meter_match_workspace_bytes(int(n_sent))
+        if n < 0:
+            _check(n)
+        return n
+
+    @staticmethod
+    def measure_workspace_bytes(n_sym, n_rows):
+        n = lib().gfdm_hip_link_meter_measure_workspace_bytes(int(n_sym), int(n_rows))
+        if n < 0:
+            _check(n)
+        return n
+
+    _rows = SymbolMapper._rows
+    _count = SymbolMapper._count
+    _ptr = staticmethod(SymbolMapper._ptr)
+
+    def _vector(self, x, dtype, n, what, like):
+        """an input of n elements of `dtype`, of `like`'s kind (device tensor or host array)"""
+        name = np.dtype(dtype).name
+        if _is_tensor(like):
+            import torch
+            if not _is_tensor(x):
+                raise TypeError("%s must be a torch.%s CUDA/HIP tensor, as the other arrays are" % (what, name))
+            _dev_arg(x, getattr(torch, name), n, what, self._dev)
+            return x
+        if _is_tensor(x):
+            raise TypeError("%s must be a host array, as the other arrays are" % what)
+        x = np.ascontiguousarray(x, dtype=dtype).ravel()
+        if x.size != n:
+            raise RuntimeError("%s has %d elements, expected %d" % (what, x.size, n))
+        return x
+
+    def _result(self, out, key, like, n, dtype):
+        """the output `key` of n elements: out[key] where given, else a new array of `like`'s kind"""
+        name = np.dtype(dtype).name
+        res = None if out is None else out.get(key)
+        if res is None:
+            if _is_tensor(like):
+                import torch
+                return torch.empty((n,), dtype=getattr(torch, name), device=like.device)
+            return np.empty((n,), dtype)
+        if _is_tensor(res) != _is_tensor(like) or (not _is_tensor(res) and not isinstance(res, np.ndarray)):
+            raise TypeError("out[%r] must be a %s, as the input is" % (key, "CUDA/HIP tensor" if _is_tensor(like) else "numpy array"))
+        if str(res.dtype).replace("torch.", "") != name or not (res.is_contiguous() if _is_tensor(res) else res.flags.c_contiguous):
+            raise TypeError("out[%r] must be contiguous %s" % (key, name))
+        if _is_tensor(res) and (not res.is_cuda or res.device.index != self._dev):
+            raise RuntimeError("out[%r] must live on GPU %d, as the handle does" % (key, self._dev))
+        if int(np.prod(res.shape)) != n:
+            raise RuntimeError("out[%r] holds %d elements, expected %d" % (key, int(np.prod(res.shape)), n))
+        return res
+
+    def _workspace(self, ws, like, need):
+        import torch
+        if ws is None:
+            return torch.empty(need, dtype=torch.uint8, device=like.device)
+        if not _is_tensor(ws) or ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < need or ws.device.index != self._dev:
+            raise TypeError("workspace must be a contiguous uint8 CUDA/HIP tensor of at least %d bytes on GPU %d" % (need, self._dev))
+        return ws
+
+    def _settle(self):
+        """the host flavours run on the handle's own stream: what torch's current stream still holds for this handle (a reset) goes first"""
+        try:
+            import torch
+        except ImportError:
+            return
+        torch.cuda.current_stream(self._dev).synchronize()
+
+    def reset(self, stream=None):
+        """enqueue the zeroing of the totals"""
+        _check(lib().gfdm_hip_link_meter_reset(self._h, self._sp(stream)))
+
+    def totals_ptr(self):
+        """device pointer of the int64[12] totals (gfdm_hip_link_meter_totals_device)"""
+        return lib().gfdm_hip_link_meter_totals_device(self._h)
+
+    def totals(self, stream=None):
+        """dict of Python ints: synchronises the stream and reads the 96 bytes"""
+        t = np.zeros(12, np.int64)
+        _check(lib().gfdm_hip_link_meter_totals(self._h, t.ctypes.data, self._sp(stream)))
+        return {name: int(t[i]) for i, name in enumerate(self.FIELDS)}
+
+    def ber(self, stream=None):
+        """bit_errors / bits of totals(); nan where no bit was counted"""
+        t = self.totals(stream)
+        return t["bit_errors"] / t["bits"] if t["bits"] else float("nan")
+
+    def fer(self, stream=None):
+        """(row_errors + missed) / (rows + missed) of totals(): a burst that was not found is a frame in error; nan where both are 0"""
+        t = self.totals(stream)
+        den = t["rows"] + t["missed"]
+        return (t["row_errors"] + t["missed"]) / den if den else float("nan")
+
+    def match(self, frame_start, sent_pos, tol, offset=0, count=None, out=None, stream=None, workspace=None):
+        """{"ref_row": int64 (n_rows,), "sent_row": int64 (n_sent,)}: ref_row[d] is the sent burst detection d is (or -1), sent_row[j] the
+        detection that is sent burst j (or -1); sent_pos ascending, a detection matches within |frame_start - (sent_pos + offset)| <= tol"""
+        if not _is_tensor(frame_start):
+            frame_start = np.ascontiguousarray(frame_start, dtype=np.int64).ravel()
+        n_rows = int(frame_start.numel() if _is_tensor(frame_start) else frame_start.size)
+        frame_start = self._vector(frame_start, np.int64, n_rows, "frame_start", frame_start)
+        n_sent = int(sent_pos.numel() if _is_tensor(sent_pos) else np.asarray(sent_pos).size)
+        sent_pos = self._vector(sent_pos, np.int64, n_sent, "sent_pos", frame_start)
+        tol, offset = int(tol), int(offset)
+        res = {"ref_row": self._result(out, "ref_row", frame_start, n_rows, np.int64), "sent_row": self._result(out, "sent_row", frame_start, n_sent, np.int64)}
+        keep = []
+        cptr = self._count(count, frame_start, keep)
+        L = lib()
+        if _is_tensor(frame_start):
+            ws = self._workspace(workspace, frame_start, self.match_workspace_bytes(n_sent))
+            _check(L.gfdm_hip_link_meter_match_device(self._h, self._ptr(res["ref_row"]), self._ptr(res["sent_row"]), self._ptr(frame_start), cptr, n_rows,
+                                                      self._ptr(sent_pos), n_sent, offset, tol, ws.data_ptr(), self._sp(stream)))
+        else:
+            self._settle()
+            _check(L.gfdm_hip_link_meter_match_host(self._h, self._ptr(res["ref_row"]), self._ptr(res["sent_row"]), self._ptr(frame_start), cptr, n_rows,
+                                                    self._ptr(sent_pos), n_sent, offset, tol))
+        return res
+
+    def measure(self, symbols, payload=None, ref_row=None, count=None, out=None, stream=None, workspace=None):
+        """symbols (n_rows, n_sym) complex64 against payload (n_ref, row_bytes(n_sym)) uint8 -> {"bit_errors": int32, "err_power": float32,
+        "ref_power": float32}, each (n_rows,); row r is compared with payload row ref_row[r] (None: r), a row whose ref_row is negative or
+        beyond the payload gives -1 / 0 / 0 and is not read.  payload None: decision-directed, err_power against the decided points, no
+        bit_errors."""
+        symbols, n_rows, n_sym, _ = self._rows(symbols, np.complex64, "symbols")
+        n_ref = 0
+        if payload is not None:
+            if _is_tensor(payload) != _is_tensor(symbols):
+                raise TypeError("payload must be a %s, as symbols is" % ("CUDA/HIP tensor" if _is_tensor(symbols) else "numpy array"))
+            payload, n_ref, _, _ = self._rows(payload, np.uint8, "payload", self.row_bytes(n_sym))
+        if ref_row is not None:
+            ref_row = self._vector(ref_row, np.int64, n_rows, "ref_row", symbols)
+        res = {}
+        if payload is not None:
+            res["bit_errors"] = self._result(out, "bit_errors", symbols, n_rows, np.int32)
+        elif out is not None and out.get("bit_errors") is not None:
+            raise ValueError("bit_errors needs a payload: a decision-directed call counts no errors")
+        res["err_power"] = self._result(out, "err_power", symbols, n_rows, np.float32)
+        res["ref_power"] = self._result(out, "ref_power", symbols, n_rows, np.float32)
+        keep = []
+        cptr = self._count(count, symbols, keep)
+        ptr = lambda a: None if a is None else self._ptr(a)
+        L = lib()
+        if _is_tensor(symbols):
+            if payload is not None and n_ref == 0:                           # an empty tensor has no pointer, and NULL would mean decision-directed
+                import torch
+                payload = torch.empty(16, dtype=torch.uint8, device=symbols.device)
+            ws = self._workspace(workspace, symbols, self.measure_workspace_bytes(n_sym, n_rows))
+            _check(L.gfdm_hip_link_meter_measure_device(self._h, ptr(res.get("bit_errors")), ptr(res["err_power"]), ptr(res["ref_power"]), self._ptr(symbols),
+                                                        ptr(payload), n_ref, ptr(ref_row), cptr, n_sym, n_rows, ws.data_ptr(), self._sp(stream)))
+        else:
+            self._settle()
+            _check(L.gfdm_hip_link_meter_measure_host(self._h, ptr(res.get("bit_errors")), ptr(res["err_power"]), ptr(res["ref_power"]), self._ptr(symbols),
+                                                      ptr(payload), n_ref, ptr(ref_row), cptr, n_sym, n_rows))
         return res
