@@ -92,6 +92,16 @@ __device__ __forceinline__ void st_stream(cf* base, int64_t idx, cf v)
 {
     __builtin_nontemporal_store(v2f_io{ v.x, v.y }, reinterpret_cast<v2f_io*>(base + idx));
 }
+// Two neighbouring samples in one 16-byte access (global_load_dwordx4 / global_store_dwordx4, `nt`): p resp. base + idx must be 16-byte aligned
+typedef float v4f_io __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ v4f_io ld_stream2(const cf* p)
+{
+    return __builtin_nontemporal_load(reinterpret_cast<const v4f_io*>(p));
+}
+__device__ __forceinline__ void st_stream2(cf* base, int64_t idx, v4f_io v)
+{
+    __builtin_nontemporal_store(v, reinterpret_cast<v4f_io*>(base + idx));
+}
 
 template <bool INV> __device__ __forceinline__ cf mul_mj(cf a) { return INV ? mk(-a.y, a.x) : mk(a.y, -a.x); }     // * (-j) forward, * (+j) inverse
 template <bool INV> __device__ __forceinline__ cf cmul_dir(cf a, cf w) { return INV ? cmulc(a, w) : cmul(a, w); }   // w is a FORWARD root

@@ -5,6 +5,7 @@
 #include "gfdm_hostcall.h"
 #include "gfdm_rowgeom.h"
 #include "gfdm_tx.h"
+#include "gfdm_rowvariants.h"
 #include "gfdm_hostpipe.h"
 
 #include <cfloat>
@@ -706,6 +707,11 @@ int gfdm_hip_set_ic_matrix_cores(int mode)
 int gfdm_hip_set_dft_matrix_cores(int mode)
 {
     return g_dft_mfma.exchange(mode < 0 ? 0 : mode > 2 ? 2 : mode);
+}
+
+int gfdm_hip_set_wide_access(int enable)
+{
+    return gfdm::rowvar::wide_access().exchange(enable ? 1 : 0);
 }
 
 int gfdm_hip_jit_build_for_testing(int timeslots, int subcarriers, int overlap, int part)

@@ -22,6 +22,7 @@ struct DevicePlan {
     int part_len;   // min(M*L/2, M): bins of each tap part the modulator accumulates (modulator_kernel_cc.cc:101)
     const cf* taps;     // [L*M] normalised filter taps
     int taps_real;      // 1 when every tap is real (RRC / RC and every other real, even prototype filter): two multiply-adds per tap product
+                        // (PLAN_TAPS_REAL; the K = 64 row-lane launches carry PLAN_WIDE_IO beside it in their copy of the plan)
     const cf* ictaps;   // [M]   ic[m] = t[m] * t[(L-1)M + m]
     const cf* ictaps_m; // [M]   ic[m] / M (IC taps with the inverse-DFT scale folded in)
     const cf* icg;      // [M]   g = IDFT_M(ic) / M: circular-convolution form of one cancellation round
@@ -41,6 +42,12 @@ struct DevicePlan {
     // order the kernels read it; nullptr = dense transforms (generic kernels)
     const cf* raderB;
 };
+
+// Bits of DevicePlan::taps_real as a row-lane kernel of K = 64 reads it.  PLAN_WIDE_IO is launch-uniform and set per launch by
+// rowvar::wide_io (gfdm_rowvariants.h) in the launch's own copy of the plan, never in a handle's: every pointer of the call is 16-byte
+// aligned and the blocks are packed, so the kernel may move its samples two at a time (gfdm_rowlane_impl.h, "16-byte sample accesses").
+// A flag in an existing field instead of a new argument or new instantiations: the argument layout of every kernel stays what it was.
+enum PlanFlags { PLAN_TAPS_REAL = 1, PLAN_WIDE_IO = 2 };
 
 // Where the receiver finds its samples and how it emits its symbols: the cyclic-prefix removal
 // of add_cyclic_prefix_cc::remove_cyclic_prefix (lib/add_cyclic_prefix_cc.cc:100-104) is an input offset + stride, the

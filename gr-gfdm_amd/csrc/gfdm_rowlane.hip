@@ -62,6 +62,7 @@ hipError_t launch_rowlane_modulate(const DevicePlan& p, const TxParams& tx, cons
     if (nblocks <= 0) return hipSuccess;
     DevicePlan a_p = p;
     TxParams a_tx = tx;
+    a_p.taps_real = rowvar::plan_flags_modulate(p, tx, out, in);
     void* args[] = { &a_p, &a_tx, &twT, &out, &in, &nblocks };
     return launch(compiled_part(p.K, p.M, p.L, JIT_PART_MOD), rowvar::select_modulate(p, tx), p.K, p.M, nblocks, s, args);
 }
@@ -74,6 +75,7 @@ hipError_t launch_rowlane_receive(const DevicePlan& p, const IcParams& ic, const
     static const EstPlan kNoEst = {};
     DevicePlan a_p = p;
     IcParams a_ic = ic;
+    a_p.taps_real = rowvar::plan_flags_receive(p, ic, est, out, in, f_eq);
     EstPlan a_est = est ? *est : kNoEst;
     BurstIo a_bio = burst_io(est) ? *burst_io(est) : BurstIo{};
     void* args8[] = { &a_p, &a_ic, &a_est, &twT, &out, &in, &f_eq, &nblocks };

@@ -485,6 +485,98 @@ __device__ __forceinline__ float dpp_wave_rol1(float x)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x134, 0xF, 0xF, true));
 }
 
+// ---- K = 64: 16-byte sample accesses ----------------------------------------------------------------------------------------
+// A wave of the K = 64 kernels moves every sample in an 8-byte access per lane (512 bytes per instruction): M loads and M stores.  Where
+// the launch carries PLAN_WIDE_IO (gfdm_plan.h: every pointer of the call 16-byte aligned, plain packed blocks) four stages move two
+// samples per lane and access instead, each behind a knob of its own (0 = the stage is compiled out):
+//   GFDM_WIDE_MOD_IN   modulator input: the linear copy of the [k][m] symbols into the tile as M / 2 dwordx4 loads + ds_write_b128
+//                      (+ one 8-byte access for the last 64 elements of an odd M); M = 9: 9 + 9 instructions -> 5 + 5
+//   GFDM_WIDE_RX_OUT   receiver output (plain linear store): ds_read_b128 + dwordx4 stores, the same counts
+//   GFDM_WIDE_RX_IN    receiver input: lane l loads elements l & ~1 and l | 1 of row p + (l & 1) for the row pairs (p, p + 1); the lanes
+//                      of a pair exchange one sample (DPP quad_perm:[1,0,3,2]) so that lane l ends with element l of both rows:
+//                      M / 2 dwordx4 loads (+ one 8-byte load for an odd M) and 8 vector instructions per row pair
+//   GFDM_WIDE_MOD_OUT  modulator output: the mirror image, exchange first, then one dwordx4 store per row pair
+// Results are bit-identical: only the data movement differs (tests/test_wide_access_gpu.py).
+// Measured defaults (profiles/r12/wide_access_ab.csv, profiles/EXPERIMENTS.md "16-byte sample accesses"; K=64 M=9 L=2, 4096 blocks, builds in
+// alternating processes on one MI355X, two boxes; kernel = steady-state duration alone on its stream, step = modulate + MF demodulate pipelined over
+// three streams as bench.py runs it; the repeats of one build spread by 0.02 us resp. 0.3 % sustained and 2-3 % over the 200-step burst):
+//   MOD_IN  = 1   modulate 9.30 -> 8.91 us (box 1: 9.41 -> 9.02), sustained step rate +3.0 % (+4.6 %), 200-step burst +1.2 % (+2.2 %)
+#ifndef GFDM_WIDE_MOD_IN
+#define GFDM_WIDE_MOD_IN 1
+#endif
+//   RX_OUT  = 0   alone: demodulate 9.20 -> 9.14 us, sustained step rate +0.3 %: inside the noise
+#ifndef GFDM_WIDE_RX_OUT
+#define GFDM_WIDE_RX_OUT 0
+#endif
+//   RX_IN   = 0   the kernel alone gains (demodulate 9.27 -> 8.95 us) but the pipelined step LOSES against MOD_IN alone (sustained 3.143 -> 3.118e8 blocks/s, the
+//                 burst 2.99 -> 2.93e8): its 32 extra vector instructions per wave sit on the critical path of a wave that shares its SIMD with the other kernel's
+#ifndef GFDM_WIDE_RX_IN
+#define GFDM_WIDE_RX_IN 0
+#endif
+//   MOD_OUT = 0   alone: modulate 9.41 -> 9.39 us; on top of MOD_IN 8.91 -> 8.82 us, but the sustained step rate ties (3.143 / 3.142e8) and the burst differs by
+//                 less than its spread
+#ifndef GFDM_WIDE_MOD_OUT
+#define GFDM_WIDE_MOD_OUT 0
+#endif
+constexpr bool kWideModIn = GFDM_WIDE_MOD_IN != 0, kWideRxOut = GFDM_WIDE_RX_OUT != 0, kWideRxIn = GFDM_WIDE_RX_IN != 0, kWideModOut = GFDM_WIDE_MOD_OUT != 0;
+
+// lane l <- lane l ^ 1 (DPP quad_perm:[1,0,3,2] = 0xB1)
+__device__ __forceinline__ float dpp_pair_swap(float x)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
+}
+__device__ __forceinline__ cf dpp_pair_swap(cf x) { return mk(dpp_pair_swap(x.x), dpp_pair_swap(x.y)); }
+
+// linear copy of a block between global memory and its tile, two elements per lane and access (src, dst and the tile 16-byte aligned)
+template <int M>
+__device__ __forceinline__ void wide_block_to_tile(cf* X, const cf* __restrict__ src, int l)
+{
+    v4f_io w[M / 2 > 0 ? M / 2 : 1];
+    cf tail = mk(0.f, 0.f);
+    static_for<0, M / 2>([&](auto ii) { constexpr int i = decltype(ii)::value; w[i] = ld_stream2(src + 2 * (l + 64 * i)); });
+    if constexpr (M % 2) tail = ld_stream(src + 64 * (M - 1) + l);
+    static_for<0, M / 2>([&](auto ii) { constexpr int i = decltype(ii)::value; reinterpret_cast<v4f_io*>(X)[l + 64 * i] = w[i]; });
+    if constexpr (M % 2) X[64 * (M - 1) + l] = tail;
+}
+template <int M>
+__device__ __forceinline__ void wide_tile_to_block(cf* __restrict__ dst, int64_t base, const cf* X, int l)
+{
+    static_for<0, M / 2>([&](auto ii) { constexpr int i = decltype(ii)::value; st_stream2(dst, base + 2 * (l + 64 * i), reinterpret_cast<const v4f_io*>(X)[l + 64 * i]); });
+    if constexpr (M % 2) st_stream(dst, base + 64 * (M - 1) + l, X[64 * (M - 1) + l]);
+}
+
+// v[r] = src[64 r + l], r < M (lane l gets element l of every row of the block), from M / 2 16-byte loads per lane
+template <int M>
+__device__ __forceinline__ void wide_load_rows(cf (&v)[M], const cf* __restrict__ src, int l)
+{
+    const bool odd = (l & 1) != 0;
+    const cf* p = src + 64 * (l & 1) + (l & ~1);
+    v4f_io w[M / 2 > 0 ? M / 2 : 1];
+    static_for<0, M / 2>([&](auto ii) { constexpr int i = decltype(ii)::value; w[i] = ld_stream2(p + 128 * i); });
+    if constexpr (M % 2) v[M - 1] = ld_stream(src + 64 * (M - 1) + l);
+    static_for<0, M / 2>([&](auto ii) {
+        constexpr int i = decltype(ii)::value;
+        const cf a = mk(w[i].x, w[i].y), b = mk(w[i].z, w[i].w);          // elements l & ~1, l | 1 of row 2 i + (l & 1)
+        const cf got = dpp_pair_swap(odd ? a : b);                        // the partner's sample of this lane's column
+        v[2 * i] = odd ? got : a;
+        v[2 * i + 1] = odd ? b : got;
+    });
+}
+// dst[base + 64 r + l] = v[r]: the mirror image, one 16-byte store per row pair
+template <int M>
+__device__ __forceinline__ void wide_store_rows(cf* __restrict__ dst, int64_t base, const cf (&v)[M], int l)
+{
+    const bool odd = (l & 1) != 0;
+    const int64_t at = base + 64 * (l & 1) + (l & ~1);
+    static_for<0, M / 2>([&](auto ii) {
+        constexpr int i = decltype(ii)::value;
+        const cf got = dpp_pair_swap(odd ? v[2 * i] : v[2 * i + 1]);
+        const cf a = odd ? got : v[2 * i], b = odd ? v[2 * i + 1] : got;
+        st_stream2(dst, at + 128 * i, v4f_io{ a.x, a.y, b.x, b.y });
+    });
+    if constexpr (M % 2) st_stream(dst, base + 64 * (M - 1) + l, v[M - 1]);
+}
+
 // c + t x for a filter tap t: prototype filters such as RRC / RC have REAL frequency-domain taps (DevicePlan::taps_real, decided once per
 // handle), and then the product is two multiply-adds instead of four -- the branch is uniform for the whole launch
 template <bool TREAL>
@@ -805,11 +897,18 @@ __global__ __launch_bounds__(RowShape<K>::WG) void k_row_modulate(DevicePlan p, 
     if constexpr (PRE_TW) static_for<1, M>([&](auto mi) { constexpr int m = decltype(mi)::value; twv[m] = twT[m * K + q]; });
     if constexpr (PRE_TAPS) static_for<0, L * M>([&](auto ii) { constexpr int i = decltype(ii)::value; tapv[i] = p.taps[i]; });
     auto tap = [&](auto ii) { constexpr int i = decltype(ii)::value; if constexpr (PRE_TAPS) return tapv[i]; else return p.taps[i]; };
-    const bool treal = p.taps_real != 0;
+    constexpr bool WIDE_IN = (K == 64 && TXMODE == 0 && kWideModIn), WIDE_OUT = (K == 64 && TXMODE == 0 && kWideModOut);
+    const bool treal = (K == 64) ? (p.taps_real & PLAN_TAPS_REAL) != 0 : p.taps_real != 0;
+    const bool wide = (K == 64) && (p.taps_real & PLAN_WIDE_IO) != 0;      // launch-uniform: 16-byte sample accesses
+    (void)wide;
     cf v[M];
     if constexpr (TXMODE == 0) {
         // symbols [k][p], copied linearly (coalesced) into the tile; lane k then owns row k
-        static_for<0, M>([&](auto ii) { constexpr int i = decltype(ii)::value; X[q + K * i] = ld_stream(in + base + q + K * i); });
+        bool copied = false;
+        if constexpr (WIDE_IN) {
+            if (wide) { wide_block_to_tile<M>(X, in + base, q); copied = true; }
+        }
+        if (!copied) static_for<0, M>([&](auto ii) { constexpr int i = decltype(ii)::value; X[q + K * i] = ld_stream(in + base + q + K * i); });
         block_sync<K>();
         static_for<0, M>([&](auto mi) { constexpr int m = decltype(mi)::value; v[m] = X[q * M + m]; });
     } else {
@@ -876,7 +975,11 @@ __global__ __launch_bounds__(RowShape<K>::WG) void k_row_modulate(DevicePlan p, 
             static_for<0, M>([&](auto pi) { constexpr int pp = decltype(pi)::value; tx_store_sample(tx, blk, N, K * pp + q, v[pp]); });
             tx_store_preamble(tx, blk, q, K);
         } else {
-            static_for<0, M>([&](auto pi) { constexpr int pp = decltype(pi)::value; st_stream(out, base + K * pp + q, v[pp]); });
+            bool stored = false;
+            if constexpr (WIDE_OUT) {
+                if (wide) { wide_store_rows<M>(out, base, v, q); stored = true; }
+            }
+            if (!stored) static_for<0, M>([&](auto pi) { constexpr int pp = decltype(pi)::value; st_stream(out, base + K * pp + q, v[pp]); });
         }
     }
 }

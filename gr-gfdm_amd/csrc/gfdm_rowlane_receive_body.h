@@ -42,7 +42,17 @@
     }
     // ---- phase A: timeslot DFT of row q, twiddle W_N^{q m}
     cf v[M];
-    if constexpr (!BURST) static_for<0, M>([&](auto pi) { constexpr int pp = decltype(pi)::value; v[pp] = ld_stream(in + in_base + K * pp + q); });
+    // K = 64 with PLAN_WIDE_IO (launch-uniform; packed blocks, in_base == base): 16-byte sample accesses, gfdm_rowlane_impl.h
+    constexpr bool WIDE_IN = (K == 64 && !BURST && kWideRxIn), WIDE_OUT = (K == 64 && !BURST && !ICMX && kWideRxOut);
+    const bool wide = (K == 64) && (p.taps_real & PLAN_WIDE_IO) != 0;
+    (void)wide;
+    if constexpr (!BURST) {
+        bool loaded = false;
+        if constexpr (WIDE_IN) {
+            if (wide) { wide_load_rows<M>(v, in + in_base, q); loaded = true; }
+        }
+        if (!loaded) static_for<0, M>([&](auto pi) { constexpr int pp = decltype(pi)::value; v[pp] = ld_stream(in + in_base + K * pp + q); });
+    }
     FftTwiddles<K> twd;
     load_fft_twiddles<K>(twd, q, p.wK);
     // Everything else the later phases read from global memory is requested here as well: behind an ordering point a load can
@@ -55,7 +65,7 @@
         if constexpr (MODE == RX_IC) static_for<0, M>([&](auto ii) { constexpr int i = decltype(ii)::value; icgv[i] = p.icg[i]; });
     }
     auto tap = [&](auto ii) { constexpr int i = decltype(ii)::value; if constexpr (PRE_TAPS) return tapv[i]; else return p.taps[i]; };
-    const bool treal = p.taps_real != 0;
+    const bool treal = (K == 64) ? (p.taps_real & PLAN_TAPS_REAL) != 0 : p.taps_real != 0;
     auto icg = [&](auto ii) { constexpr int i = decltype(ii)::value; if constexpr (PRE_TAPS && MODE == RX_IC) return icgv[i]; else return p.icg[i]; };
     const int wgt = (MODE == RX_IC && !ICMX) ? ic.active[q] : 0;      // multiplicity of subcarrier k in subcarrier_map (0 = inactive)
     typename IcMfma<ICMX ? K : 16, ICMX ? M : 4>::Pre icpre;
@@ -349,7 +359,13 @@
             });
         } else if (valid) {
             if constexpr (ICMX) static_for<0, M>([&](auto ii) { constexpr int i = decltype(ii)::value; st_stream(out, base + q + K * i, X[IcMfma<ICMX ? K : 16, ICMX ? M : 4>::pa_linear(q + K * i)]); });
-            else static_for<0, M>([&](auto ii) { constexpr int i = decltype(ii)::value; st_stream(out, base + q + K * i, X[q + K * i]); });
+            else {
+                bool stored = false;
+                if constexpr (WIDE_OUT) {
+                    if (wide) { wide_tile_to_block<M>(out, base, X, q); stored = true; }
+                }
+                if (!stored) static_for<0, M>([&](auto ii) { constexpr int i = decltype(ii)::value; st_stream(out, base + q + K * i, X[q + K * i]); });
+            }
         }
     }
     GFDM_STAMP(5);

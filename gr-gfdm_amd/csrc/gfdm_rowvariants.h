@@ -6,6 +6,10 @@
 #include "gfdm_tx.h"
 #include "gfdm_rowgeom.h"
 
+#include <atomic>
+#include <cstdint>
+#include <cstdlib>
+
 namespace gfdm {
 namespace rowvar {
 
@@ -84,6 +88,32 @@ inline Choice select_receive(const DevicePlan& p, const IcParams& ic, const EstP
 inline Choice select_modulate(const DevicePlan& p, const TxParams& tx)
 {
     return find(p.K, p.M, Variant{ JIT_PART_MOD, 0, EQ_NONE, ICK_GENERAL, (tx.mapped && tx.framed) ? 2 : tx.mapped ? 1 : 0 });
+}
+
+// 16-byte sample accesses of the K = 64 kernels (gfdm_rowlane_impl.h): the launch-uniform flag PLAN_WIDE_IO a launch carries in its own
+// copy of the plan.  complex64 pointers may be only 8-byte aligned, so the wide form is chosen per call: every pointer of the call on a
+// 16-byte boundary (a block is 8 K M bytes, a multiple of 16 at K = 64) and plain packed blocks on both sides -- the mapper, frame,
+// demapper-with-offset and burst paths keep the 8-byte code.  wide_access(): process-wide switch (gfdm_hip_set_wide_access; tests and
+// A/B runs turn it off to get the 8-byte route on the same input); GFDM_HIP_WIDE_ACCESS=0 in the environment starts a process with it off.
+inline std::atomic<int>& wide_access()
+{
+    static std::atomic<int> on{ [] { const char* e = getenv("GFDM_HIP_WIDE_ACCESS"); return (e && e[0] == '0' && !e[1]) ? 0 : 1; }() };
+    return on;
+}
+
+inline bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15u) == 0; }       // (a null pointer is not an operand of the call)
+
+inline int plan_flags_modulate(const DevicePlan& p, const TxParams& tx, const cf* out, const cf* in)
+{
+    const bool wide = p.K == 64 && !tx.mapped && !tx.framed && aligned16(out) && aligned16(in) && wide_access().load(std::memory_order_relaxed) != 0;
+    return p.taps_real | (wide ? (int)PLAN_WIDE_IO : 0);
+}
+
+inline int plan_flags_receive(const DevicePlan& p, const IcParams& ic, const EstPlan* est, const cf* out, const cf* in, const cf* f_eq)
+{
+    const bool wide = p.K == 64 && !burst_io(est) && ic.io.in_stride == 0 && ic.io.in_offset == 0 && aligned16(out) && aligned16(in) && aligned16(f_eq) &&
+                      wide_access().load(std::memory_order_relaxed) != 0;
+    return p.taps_real | (wide ? (int)PLAN_WIDE_IO : 0);
 }
 
 inline Choice select_estimate(const EstPlan& e) { return find(e.K, e.M, Variant{ JIT_PART_EST, 0, EQ_NONE, ICK_GENERAL, 0 }); }

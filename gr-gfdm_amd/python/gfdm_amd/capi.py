@@ -55,6 +55,7 @@ def lib():
         "gfdm_hip_set_jit": (i32, [i32]),
         "gfdm_hip_precompile": (i32, [i32, i32, i32, ctypes.c_uint]),
         "gfdm_hip_set_ic_matrix_cores": (i32, [i32]),
+        "gfdm_hip_set_wide_access": (i32, [i32]),
         "gfdm_hip_quiesce": (None, []),
         "gfdm_hip_set_dft_matrix_cores": (i32, [i32]),
         "gfdm_hip_jit_build_for_testing": (i32, [i32, i32, i32, i32]),
@@ -433,6 +434,13 @@ def set_ic_matrix_cores(mode):
     only, 1 / True (default) matrix cores where they are the faster form (subcarriers >= 128), 2 matrix cores wherever the form applies.
     Returns the previous mode."""
     return lib().gfdm_hip_set_ic_matrix_cores(int(mode))
+
+
+def set_wide_access(enable):
+    """gfdm_hip_set_wide_access: False keeps every later call of the 64-subcarrier row-lane kernels on 8-byte sample accesses; True (default)
+    lets a call whose device pointers all lie on 16-byte boundaries move two samples per access.  Same results either way.  Returns the
+    previous setting."""
+    return lib().gfdm_hip_set_wide_access(int(bool(enable)))
 
 
 def quiesce():

@@ -115,6 +115,12 @@ int gfdm_hip_set_ic_matrix_cores(int mode);
  * (csrc/gfdm_rader.hip; kernel_name "generic_rader"); frames / demapper and the self-estimating receivers of that shape stay on the generic
  * kernels.  Modes 0 and 2 keep the dense forms for that shape too (A/B, tests). */
 int gfdm_hip_set_dft_matrix_cores(int mode);
+/* The row-lane kernels of 64 subcarriers move the samples of plain, packed blocks (modulator_work, the receivers without frame offset) two at a
+ * time -- 16-byte accesses -- when every device pointer of the call lies on a 16-byte boundary; a call with any pointer that is only 8-byte
+ * aligned runs the 8-byte form, with bit-identical results.  enable = 0 keeps every later call on the 8-byte form (tests, A/B runs),
+ * 1 (default) restores the choice per call.  Process-wide, takes effect at the next launch; returns the previous setting.  A process started
+ * with GFDM_HIP_WIDE_ACCESS=0 in its environment begins with 0. */
+int gfdm_hip_set_wide_access(int enable);
 /* TEST HOOK: compile (or find in the disk cache) part 0..4 (receive, receive + IC, preamble-equalised receive, modulate, estimator; the
  * sixth part, the receive kernels of demodulate_bursts, builds through gfdm_hip_precompile, bit 5) of
  * the row-lane kernels for a shape through hiprtc WITHOUT loading it --
