@@ -950,18 +950,25 @@ class Transmitter(_Kernel):
             raise RuntimeError("input size(%d) MUST be a multiple of ninput_size(%d)!" % (size, n))
         return n, size // n
 
-    def transmit(self, symbols, ninput_size=None, n_ports=None, stream=None):
-        """All ports (or the first n_ports): list of (nblocks, output_vector_size) arrays / tensors, one per cyclic shift."""
+    def transmit(self, symbols, ninput_size=None, n_ports=None, stream=None, outs=None):
+        """All ports (or the first n_ports): list of (nblocks, output_vector_size) arrays / tensors, one per cyclic shift.
+        `outs` (device path only): one tensor of nblocks * output_vector_size elements per port to write into."""
         L = lib()
         n, nb = self._split(symbols, ninput_size)
         ports = len(self._shifts) if n_ports is None else n_ports
         F = self.output_vector_size()
         if _is_tensor(symbols):
             import torch
-            outs = [torch.empty(nb, F, dtype=torch.complex64, device=symbols.device) for _ in range(ports)]
-            arr = (ctypes.c_void_p * ports)(*[o.data_ptr() for o in outs])
+            if outs is None:
+                outs = [torch.empty(nb, F, dtype=torch.complex64, device=symbols.device) for _ in range(ports)]
+            elif len(outs) != ports:
+                raise RuntimeError("outs has %d tensors, expected one per port (%d)" % (len(outs), ports))
+            outs = list(outs)
+            arr = (ctypes.c_void_p * ports)(*[self._dp(o, nb * F, "outs[%d]" % i) for i, o in enumerate(outs)])
             _check(L.gfdm_hip_transmitter_work_device(self._h, arr, ports, self._dp(symbols, nb * n, "in"), n, nb, self._sp(stream)))
             return outs
+        if outs is not None:
+            raise TypeError("outs is for device tensors; the numpy path returns new arrays")
         x = _c64(symbols)
         outs = [np.empty((nb, F), np.complex64) for _ in range(ports)]
         arr = (ctypes.c_void_p * ports)(*[o.ctypes.data for o in outs])
@@ -972,29 +979,33 @@ class Transmitter(_Kernel):
         """transmitter_kernel::generic_work: the frame of cyclic_shifts[0]."""
         return self.transmit(symbols, ninput_size, 1)[0]
 
-    def modulate(self, symbols, ninput_size=None, stream=None):
+    def modulate(self, symbols, ninput_size=None, stream=None, out=None):
         L = lib()
         n, nb = self._split(symbols, ninput_size)
         N = self.block_size()
         if _is_tensor(symbols):
             import torch
-            out = torch.empty(nb, N, dtype=torch.complex64, device=symbols.device)
-            _check(L.gfdm_hip_transmitter_modulate_device(self._h, out.data_ptr(), self._dp(symbols, nb * n, "in"), n, nb, self._sp(stream)))
+            out = torch.empty(nb, N, dtype=torch.complex64, device=symbols.device) if out is None else out
+            _check(L.gfdm_hip_transmitter_modulate_device(self._h, self._dp(out, nb * N, "out"), self._dp(symbols, nb * n, "in"), n, nb, self._sp(stream)))
             return out
+        if out is not None:
+            raise TypeError("out is for device tensors; the numpy path returns a new array")
         x = _c64(symbols)
         out = np.empty((nb, N), np.complex64)
         _check(L.gfdm_hip_transmitter_modulate_host(self._h, out.ctypes.data, x.ctypes.data, n, nb))
         return out
 
-    def add_frame(self, blocks, cyclic_shift, stream=None):
+    def add_frame(self, blocks, cyclic_shift, stream=None, out=None):
         L = lib()
         N, F = self.block_size(), self.output_vector_size()
         if _is_tensor(blocks):
             import torch
             nb = blocks.numel() // N
-            out = torch.empty(nb, F, dtype=torch.complex64, device=blocks.device)
-            _check(L.gfdm_hip_transmitter_add_frame_device(self._h, out.data_ptr(), self._dp(blocks, nb * N, "in"), int(cyclic_shift), nb, self._sp(stream)))
+            out = torch.empty(nb, F, dtype=torch.complex64, device=blocks.device) if out is None else out
+            _check(L.gfdm_hip_transmitter_add_frame_device(self._h, self._dp(out, nb * F, "out"), self._dp(blocks, nb * N, "in"), int(cyclic_shift), nb, self._sp(stream)))
             return out
+        if out is not None:
+            raise TypeError("out is for device tensors; the numpy path returns a new array")
         x = _c64(blocks)
         nb = x.size // N
         out = np.empty((nb, F), np.complex64)
