@@ -4,6 +4,7 @@
 #include "../../include/gfdm_hip.h"
 #include "gfdm_hostcall.h"
 #include "gfdm_rowgeom.h"
+#include "gfdm_packed_tables.h"
 #include "gfdm_tx.h"
 #include "gfdm_rowvariants.h"
 #include "gfdm_hostpipe.h"
@@ -113,7 +114,7 @@ struct Plan {
     hipStream_t stream = nullptr;    // private stream for the *_host entry points
     gfdm::HostPipe pipe;             // the host-buffer batch path: pinned staging sets, completion ticket (gfdm_hostpipe.h)
     std::string kernel_name;
-    const cf* d_twT = nullptr;       // [M][K] twiddles W_N^{q m}, transposed so that lane q reads them coalesced (row-lane family)
+    const cf* d_twT = nullptr;       // [M][K] twiddles W_N^{q m}, transposed so that lane q reads them coalesced, or their pair-packed form; the packed roots behind (row-lane family)
     int family = gfdm::FAMILY_GENERIC;
     gfdm::JitCache jit;              // FAMILY_ROWLANE_JIT: this handle's pointers to the loaded kernel parts (no lock on the launch path)
     // run-time instantiation in the background (gfdm_hip_set_jit modes 2 / 3): while COMPILING the handle runs on the generic family, the first
@@ -177,9 +178,9 @@ void unit_roots(std::vector<cf>& dst, int n)
 
 // the host-side tables of a plan in upload order, and where the optional ones start (0 = absent: none of them comes first)
 struct PlanTables {
-    std::vector<cf> tables;          // taps | ictaps | ictaps / M | g | wM | wK | wN | twT | [icA] | [dftA] | [raderB]
+    std::vector<cf> tables;          // taps | ictaps | ictaps / M | g | wM | wK | wN | twT | [packed twT] | [packed roots] | [icA] | [dftA] | [raderB]
     bool taps_real = false, ic_real_sym = true;
-    size_t twT_off = 0, icA_off = 0, dftA_off = 0, rader_off = 0;
+    size_t twT_off = 0, rowlane_off = 0, icA_off = 0, dftA_off = 0, rader_off = 0;
     unsigned ic_sig = 0;
     int dft_mt = 0, dft_ks = 0;
 };
@@ -237,8 +238,10 @@ int plan_tables(Plan& pl, PlanTables& pt, int M, int K, int L, const float* taps
         }
     }
     unit_roots(tables, M);
+    const size_t wK_off = tables.size();
     unit_roots(tables, K);
     unit_roots(tables, N);
+    if (tables.size() & 1) tables.push_back(make_float2(0.f, 0.f));            // 16-byte alignment of the row-lane tables
     pt.twT_off = tables.size();
     {
         for (int m = 0; m < M; ++m)
@@ -246,6 +249,19 @@ int plan_tables(Plan& pl, PlanTables& pt, int M, int K, int L, const float* taps
                 const double a = -two_pi * (double)(((int64_t)q * m) % N) / (double)N;
                 tables.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
             }
+    }
+    // Row-lane family: the same twiddles and the subcarrier-FFT roots pair-packed per lane (gfdm_packed_tables.h), where the stage is compiled
+    // in for the shape (gfdm_rowgeom.h).  The launches get rowlane_off as their twT; the roots lie packed_roots_offset behind it either way.
+    pt.rowlane_off = pt.twT_off;
+    if (tables.size() & 1) tables.push_back(make_float2(0.f, 0.f));
+    if (gfdm::rowgeom::supported(K) && gfdm::rowgeom::packed_twt(K, M)) {
+        const std::vector<cf> plain(tables.begin() + pt.twT_off, tables.begin() + pt.twT_off + N);
+        pt.rowlane_off = tables.size();
+        gfdm::packed::append_twiddles(tables, plain.data(), M, K);
+    }
+    if (gfdm::rowgeom::supported(K) && gfdm::rowgeom::packed_roots(K, M)) {
+        const std::vector<cf> roots(tables.begin() + wK_off, tables.begin() + wK_off + K);
+        gfdm::packed::append_roots(tables, roots.data(), K);
     }
 
     // Matrix-core form of the cancellation rounds (IcMfma, gfdm_rowlane_impl.h): the A operand of v_mfma_f32_16x16x32_f16, lane l holds
@@ -416,7 +432,7 @@ int plan_create(Plan& pl, int M, int K, int L, const float* taps, int ntaps, int
     dp.wM = dp.icg + M;
     dp.wK = dp.wM + M;
     dp.wN = dp.wK + K;
-    pl.d_twT = pl.d_tables + pt.twT_off;
+    pl.d_twT = pl.d_tables + pt.rowlane_off;
     dp.dftA = pt.dft_mt ? reinterpret_cast<const float*>(pl.d_tables + pt.dftA_off) : nullptr;
     dp.dft_mt = pt.dft_mt;
     dp.dft_ks = pt.dft_ks;

@@ -63,6 +63,7 @@ hipError_t launch_rowlane_modulate(const DevicePlan& p, const TxParams& tx, cons
     DevicePlan a_p = p;
     TxParams a_tx = tx;
     a_p.taps_real = rowvar::plan_flags_modulate(p, tx, out, in);
+    a_p.wK = rowvar::plan_roots(p, twT);
     void* args[] = { &a_p, &a_tx, &twT, &out, &in, &nblocks };
     return launch(compiled_part(p.K, p.M, p.L, JIT_PART_MOD), rowvar::select_modulate(p, tx), p.K, p.M, nblocks, s, args);
 }
@@ -76,6 +77,7 @@ hipError_t launch_rowlane_receive(const DevicePlan& p, const IcParams& ic, const
     DevicePlan a_p = p;
     IcParams a_ic = ic;
     a_p.taps_real = rowvar::plan_flags_receive(p, ic, est, out, in, f_eq);
+    a_p.wK = rowvar::plan_roots(p, twT);
     EstPlan a_est = est ? *est : kNoEst;
     BurstIo a_bio = burst_io(est) ? *burst_io(est) : BurstIo{};
     void* args8[] = { &a_p, &a_ic, &a_est, &twT, &out, &in, &f_eq, &nblocks };

@@ -179,10 +179,52 @@ template <int K> struct FftTwiddles {
     cf wmid[RowShape<K>::WIDE3 ? RowShape<K>::WIDE_R1 - 1 : 1];            // three-pass plans, middle pass: W_K^{qq R0 u}, u = 1 .. R1 - 1
 };
 
-template <int K>
+// ---- Per-lane tables in 16-byte pairs ---------------------------------------------------------------------------------------
+// Most global loads a wave issues before its first transform are not samples but per-lane table entries that depend only on the handle:
+// the M - 1 twiddles twT[m K + q] and the subcarrier-FFT roots (K=64 M=9 receive: 9 sample loads, 8 + 3 table loads; K=256 M=31: 31 + 31
+// and 30 + 15).  Pair-packed on the host (gfdm_packed_tables.h) a lane fetches two entries with one dwordx4 load: the same bits, no vector
+// instruction added, n / 2 (+ 1) loads instead of n.  One knob per table (gfdm_rowgeom.h; 0 = the stage is compiled out, host side too):
+//   GFDM_PACKED_TWT     tw[1 .. M - 1] of k_row_receive, k_row_receive_burst and k_row_modulate
+//   GFDM_PACKED_ROOTS   FftTwiddles of the same kernels, through the wK slot of the launch's copy of the plan (rowvar::plan_roots); the
+//                       estimator kernel and the generic family keep the plain wK
+// Results are bit-identical (tests/test_packed_tables.py, tests/test_packed_tables_gpu.py).
+// entry i of lane q -> put(integral_constant<i>, value), i < N
+template <int K, int N, class F>
+__device__ __forceinline__ void load_lane_packed(const cf* __restrict__ tab, int q, F&& put)
+{
+    static_for<0, N / 2>([&](auto ji) {
+        constexpr int j = decltype(ji)::value;
+        const v4f_io w = *reinterpret_cast<const v4f_io*>(tab + 2 * (j * K + q));
+        put(std::integral_constant<int, 2 * j>{}, mk(w.x, w.y));
+        put(std::integral_constant<int, 2 * j + 1>{}, mk(w.z, w.w));
+    });
+    if constexpr (N % 2 != 0) put(std::integral_constant<int, N - 1>{}, tab[(N / 2) * 2 * K + q]);
+}
+
+// tw[m] = W_N^{q m}, m = 1 .. M - 1, from the [m][K] table or its pair-packed form
+template <int K, int M>
+__device__ __forceinline__ void load_row_twiddles(cf (&tw)[M], const cf* __restrict__ twT, int q)
+{
+    if constexpr (rowgeom::packed_twt(K, M)) load_lane_packed<K, M - 1>(twT, q, [&](auto ii, cf w) { tw[decltype(ii)::value + 1] = w; });
+    else static_for<1, M>([&](auto mi) { constexpr int m = decltype(mi)::value; tw[m] = twT[m * K + q]; });
+}
+
+// PACKED: wK is the pair-packed per-lane table of rowgeom::root_index (the modulate / receive launches); else the plain [K] roots
+template <int K, bool PACKED = false>
 __device__ __forceinline__ void load_fft_twiddles(FftTwiddles<K>& t, int lane, const cf* __restrict__ wK)
 {
     using S = RowShape<K>;
+    if constexpr (PACKED) {
+        static_assert(S::WIDE == rowgeom::wide(K) && S::WIDE3 == rowgeom::wide3(K) && (!S::WIDE || (S::WIDE_R0 == rowgeom::wide_r0(K) && S::WIDE_R1 == rowgeom::wide_r1(K))),
+                      "rowgeom::root_index follows the plan of RowShape");
+        load_lane_packed<K, rowgeom::root_count(K)>(wK, lane, [&](auto ii, cf w) {
+            constexpr int i = decltype(ii)::value;
+            if constexpr (!S::WIDE) t.w[i / 3][i % 3] = w;
+            else if constexpr (i < S::WIDE_R0 - 1) t.w16[i] = w;
+            else t.wmid[i - (S::WIDE_R0 - 1)] = w;
+        });
+        return;
+    }
     if constexpr (S::WIDE) {
         const int tq0 = lane % (K / S::WIDE_R0);
         static_for<1, S::WIDE_R0>([&](auto ui) { constexpr int u = decltype(ui)::value; t.w16[u - 1] = wK[wrap_k<K>(tq0 * u)]; });
@@ -430,6 +472,7 @@ __device__ __forceinline__ void lds_subcarrier_fft(cf* tile, int lane, const Fft
 // the butterfly of column 4 c + rr: the pass needs neither the row store to the tile nor the 12 LDS reads nor the ordering
 // point between them, and all 64 lanes work (the LDS form leaves the lanes of the fourth column group idle).
 constexpr bool kRegFirstPass = true;
+static_assert(kRegFirstPass || !rowgeom::packed_roots(64, 9), "K = 64: only the roots of pass 0 are packed (rowgeom::root_count)");
 
 // register i of lane row rr  <-  register rr of lane row i.  v_permlane32_swap(a, b): rows 2,3 of a <-> rows 0,1 of b;
 // v_permlane16_swap(a, b): rows 1,3 of a <-> rows 0,2 of b (checked on hardware, scratch/probe/permlane.hip).
@@ -890,11 +933,11 @@ __global__ __launch_bounds__(RowShape<K>::WG) void k_row_modulate(DevicePlan p, 
     cf* X = reinterpret_cast<cf*>(smem) + g * T::TS;
 
     FftTwiddles<K> twd;
-    load_fft_twiddles<K>(twd, q, p.wK);
+    load_fft_twiddles<K, rowgeom::packed_roots(K, M)>(twd, q, p.wK);
     // the twiddles of the last stage and the (uniform) filter taps are requested up front as well, see k_row_receive
     constexpr bool PRE_TW = (M <= 16), PRE_TAPS = (L * M <= 24);
-    cf twv[PRE_TW ? M : 1], tapv[PRE_TAPS ? L * M : 1];
-    if constexpr (PRE_TW) static_for<1, M>([&](auto mi) { constexpr int m = decltype(mi)::value; twv[m] = twT[m * K + q]; });
+    cf twv[M], tapv[PRE_TAPS ? L * M : 1];
+    if constexpr (PRE_TW) load_row_twiddles<K, M>(twv, twT, q);
     if constexpr (PRE_TAPS) static_for<0, L * M>([&](auto ii) { constexpr int i = decltype(ii)::value; tapv[i] = p.taps[i]; });
     auto tap = [&](auto ii) { constexpr int i = decltype(ii)::value; if constexpr (PRE_TAPS) return tapv[i]; else return p.taps[i]; };
     constexpr bool WIDE_IN = (K == 64 && TXMODE == 0 && kWideModIn), WIDE_OUT = (K == 64 && TXMODE == 0 && kWideModOut);
@@ -963,10 +1006,11 @@ __global__ __launch_bounds__(RowShape<K>::WG) void k_row_modulate(DevicePlan p, 
     }
     lds_subcarrier_fft<K, M, true, REGPASS ? 1 : 0>(X, q, twd);                                         // inverse over j
     v[0] = X[q * M];
+    if constexpr (!PRE_TW && rowgeom::packed_twt(K, M)) load_row_twiddles<K, M>(twv, twT, q);
     static_for<1, M>([&](auto mi) {
         constexpr int m = decltype(mi)::value;
         cf w;
-        if constexpr (PRE_TW) w = twv[m]; else w = twT[m * K + q];
+        if constexpr (PRE_TW || rowgeom::packed_twt(K, M)) w = twv[m]; else w = twT[m * K + q];
         v[m] = cmulc(X[q * M + m], w);
     });
     dft_inplace<M, true>(v);                                                                           // mod:137-140

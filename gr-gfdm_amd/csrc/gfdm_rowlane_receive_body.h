@@ -54,7 +54,7 @@
         if (!loaded) static_for<0, M>([&](auto pi) { constexpr int pp = decltype(pi)::value; v[pp] = ld_stream(in + in_base + K * pp + q); });
     }
     FftTwiddles<K> twd;
-    load_fft_twiddles<K>(twd, q, p.wK);
+    load_fft_twiddles<K, rowgeom::packed_roots(K, M)>(twd, q, p.wK);
     // Everything else the later phases read from global memory is requested here as well: behind an ordering point a load can
     // only be issued where it is needed, and its round trip (scalar cache for the uniform tables, L1 / L2 for the per-lane
     // ones) lands on the wave's critical path.  Filter and IC taps are uniform (SGPRs) and only preloaded while they fit.
@@ -92,7 +92,7 @@
         inv1 = est.inv1[q];
     }
     cf tw[M];
-    static_for<1, M>([&](auto mi) { constexpr int m = decltype(mi)::value; tw[m] = twT[m * K + q]; });
+    load_row_twiddles<K, M>(tw, twT, q);
     dft_inplace<M, false>(v);
     constexpr bool REGPASS = (K == 64) && kRegFirstPass;
     if constexpr (REGPASS) {

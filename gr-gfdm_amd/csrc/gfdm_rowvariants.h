@@ -116,6 +116,14 @@ inline int plan_flags_receive(const DevicePlan& p, const IcParams& ic, const Est
     return p.taps_real | (wide ? (int)PLAN_WIDE_IO : 0);
 }
 
+// The subcarrier-FFT roots of a modulate / receive launch: pair-packed per lane behind the table twT points at (gfdm_packed_tables.h)
+// where that stage is compiled in for the shape, else the plan's plain wK.  Set in the launch's own copy of the plan, as the flags above;
+// the handle's plan keeps the plain table, which the generic family and the estimator kernel read.
+inline const cf* plan_roots(const DevicePlan& p, const cf* twT)
+{
+    return rowgeom::packed_roots(p.K, p.M) ? twT + rowgeom::packed_roots_offset(p.K, p.M) : p.wK;
+}
+
 inline Choice select_estimate(const EstPlan& e) { return find(e.K, e.M, Variant{ JIT_PART_EST, 0, EQ_NONE, ICK_GENERAL, 0 }); }
 
 struct Geometry { unsigned grid, block; size_t lds; };       // lds: dynamic LDS bytes
