@@ -8,315 +8,23 @@ forwards pointers.  There is no CPU fallback: a missing library or GPU raises.
 """
 import ctypes
 import mmap
-import os
 
 import numpy as np
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_DIR = os.path.normpath(os.path.join(_PKG, "..", "..", "lib"))
-LIB_PATH = os.environ.get("GFDM_HIP_LIB") or os.path.join(LIB_DIR, "libgfdm_hip.so")   # override: A/B builds of the kernels
+from . import _abi
+from . import _operands as ops
+from ._abi import (EHIP, EINVAL, EINVAL_OVERLAP, EINVAL_TAPS, ENODEV, ENOMEM, EUNSUPPORTED, LIB_DIR, LIB_PATH, OK, GfdmHipError, _check,  # noqa: F401
+                   exported_symbols, lib)
 
-OK, EINVAL_TAPS, EINVAL_OVERLAP, EINVAL, ENODEV, EHIP, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5, -6, -7
 DECIDE = {"auto": -1, "nearest": 0, "qpsk": 1, "bpsk": 2}
 DECIDE_AUTO, DECIDE_NEAREST, DECIDE_QPSK, DECIDE_BPSK = "auto", "nearest", "qpsk", "bpsk"      # the keys of DECIDE, as decision_rule() reports them
-
-_lib = None
-
-
-class GfdmHipError(RuntimeError):
-    def __init__(self, status, message):
-        super().__init__("gfdm_hip error %d: %s" % (status, message))
-        self.status = status
-
-
-def lib():
-    """Load libgfdm_hip.so (built by `make -C gr-gfdm_amd` / __graft_entry__.build())."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError("%s not found: build it with `make -C gr-gfdm_amd` (no CPU fallback exists)" % LIB_PATH)
-    # PyTorch-ROCm ships its own copy of the HIP runtime (torch/lib/libamdhip64.so).  A process can only work with ONE runtime:
-    # if /opt/rocm's gets initialised first (through this library), torch later reports "No HIP GPUs are available".  The device
-    # path of this package hands torch tensors to the library, so when torch is installed its runtime is loaded first and
-    # libgfdm_hip.so binds to it (same SONAME); without torch the library uses /opt/rocm's.
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64, cp, f32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_char_p, ctypes.c_float, ctypes.c_double
-    u64 = ctypes.c_uint64
-    sig = {
-        "gfdm_hip_strerror": (cp, [i32]),
-        "gfdm_hip_last_error": (cp, []),
-        "gfdm_hip_device_count": (i32, []),
-        "gfdm_hip_force_generic_family_for_testing": (i32, [i32]),
-        "gfdm_hip_set_jit": (i32, [i32]),
-        "gfdm_hip_precompile": (i32, [i32, i32, i32, ctypes.c_uint]),
-        "gfdm_hip_set_ic_matrix_cores": (i32, [i32]),
-        "gfdm_hip_set_wide_access": (i32, [i32]),
-        "gfdm_hip_quiesce": (None, []),
-        "gfdm_hip_set_dft_matrix_cores": (i32, [i32]),
-        "gfdm_hip_jit_build_for_testing": (i32, [i32, i32, i32, i32]),
-        "gfdm_hip_version": (cp, []),
-        "gfdm_hip_build_id": (cp, []),
-        "gfdm_hip_register_host": (i32, [vp, ctypes.c_size_t]),
-        "gfdm_hip_unregister_host": (i32, [vp]),
-        "gfdm_hip_set_host_pipeline": (i32, [i32, i64, i32, i32, i32]),
-        "gfdm_hip_get_host_pipeline": (i32, [vp, vp, vp, vp, vp]),
-        "gfdm_hip_host_call_stats": (i32, [vp, vp, vp, vp, vp, vp]),
-        "gfdm_hip_host_call_times": (i32, [vp]),
-        "gfdm_hip_set_host_streaming_copies_for_testing": (i32, [i32]),
-        "gfdm_hip_modulator_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, vp, i32, i32]),
-        "gfdm_hip_modulator_destroy": (i32, [vp]),
-        "gfdm_hip_modulator_block_size": (i32, [vp]),
-        "gfdm_hip_modulator_filter_taps": (i32, [vp, vp]),
-        "gfdm_hip_modulator_kernel_name": (cp, [vp]),
-        "gfdm_hip_modulator_work_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_modulator_work_device": (i32, [vp, vp, vp, i64, vp]),
-        "gfdm_hip_receiver_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, vp, i32, i32]),
-        "gfdm_hip_receiver_destroy": (i32, [vp]),
-        "gfdm_hip_receiver_block_size": (i32, [vp]),
-        "gfdm_hip_receiver_timeslots": (i32, [vp]),
-        "gfdm_hip_receiver_subcarriers": (i32, [vp]),
-        "gfdm_hip_receiver_overlap": (i32, [vp]),
-        "gfdm_hip_receiver_filter_taps": (i32, [vp, vp]),
-        "gfdm_hip_receiver_ic_filter_taps": (i32, [vp, vp]),
-        "gfdm_hip_receiver_kernel_name": (cp, [vp]),
-        "gfdm_hip_receiver_demodulate_host": (i32, [vp, vp, vp, vp, i64]),
-        "gfdm_hip_receiver_demodulate_device": (i32, [vp, vp, vp, vp, i64, vp]),
-        "gfdm_hip_receiver_fft_filter_downsample_host": (i32, [vp, vp, vp, vp, i64]),
-        "gfdm_hip_receiver_fft_filter_downsample_device": (i32, [vp, vp, vp, vp, i64, vp]),
-        "gfdm_hip_receiver_transform_subcarriers_to_td_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_receiver_transform_subcarriers_to_td_device": (i32, [vp, vp, vp, i64, vp]),
-        "gfdm_hip_receiver_cancel_sc_interference_host": (i32, [vp, vp, vp, vp, i64]),
-        "gfdm_hip_receiver_cancel_sc_interference_device": (i32, [vp, vp, vp, vp, i64, vp]),
-        "gfdm_hip_advanced_receiver_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32]),
-        "gfdm_hip_advanced_receiver_destroy": (i32, [vp]),
-        "gfdm_hip_advanced_receiver_block_size": (i32, [vp]),
-        "gfdm_hip_advanced_receiver_set_ic": (i32, [vp, i32]),
-        "gfdm_hip_advanced_receiver_get_ic": (i32, [vp]),
-        "gfdm_hip_advanced_receiver_set_phase_compensation": (i32, [vp, i32]),
-        "gfdm_hip_advanced_receiver_get_phase_compensation": (i32, [vp]),
-        "gfdm_hip_advanced_receiver_decision": (i32, [vp]),
-        "gfdm_hip_advanced_receiver_kernel_name": (cp, [vp]),
-        "gfdm_hip_advanced_receiver_work_host": (i32, [vp, vp, vp, vp, i64]),
-        "gfdm_hip_advanced_receiver_work_device": (i32, [vp, vp, vp, vp, i64, vp]),
-        "gfdm_hip_receiver_configure_frames": (i32, [vp, i32, i32, vp, i32, i32]),
-        "gfdm_hip_receiver_demodulate_frames_host": (i32, [vp, vp, vp, vp, i32, i64]),
-        "gfdm_hip_receiver_demodulate_frames_device": (i32, [vp, vp, vp, vp, i32, i64, vp]),
-        "gfdm_hip_advanced_receiver_configure_frames": (i32, [vp, i32, i32, vp, i32, i32]),
-        "gfdm_hip_advanced_receiver_work_frames_host": (i32, [vp, vp, vp, vp, i32, i64]),
-        "gfdm_hip_advanced_receiver_work_frames_device": (i32, [vp, vp, vp, vp, i32, i64, vp]),
-        "gfdm_hip_transmitter_create": (i32, [ctypes.POINTER(vp)] + [i32] * 6 + [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32]),
-        "gfdm_hip_transmitter_destroy": (i32, [vp]),
-        "gfdm_hip_transmitter_input_vector_size": (i32, [vp]),
-        "gfdm_hip_transmitter_output_vector_size": (i32, [vp]),
-        "gfdm_hip_transmitter_block_size": (i32, [vp]),
-        "gfdm_hip_transmitter_n_cyclic_shifts": (i32, [vp]),
-        "gfdm_hip_transmitter_cyclic_shift": (i32, [vp, i32]),
-        "gfdm_hip_transmitter_kernel_name": (cp, [vp]),
-        "gfdm_hip_transmitter_work_host": (i32, [vp, vp, i32, vp, i32, i64]),
-        "gfdm_hip_transmitter_work_device": (i32, [vp, vp, i32, vp, i32, i64, vp]),
-        "gfdm_hip_transmitter_modulate_host": (i32, [vp, vp, vp, i32, i64]),
-        "gfdm_hip_transmitter_modulate_device": (i32, [vp, vp, vp, i32, i64, vp]),
-        "gfdm_hip_transmitter_add_frame_host": (i32, [vp, vp, vp, i32, i64]),
-        "gfdm_hip_transmitter_add_frame_device": (i32, [vp, vp, vp, i32, i64, vp]),
-        "gfdm_hip_resource_mapper_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, vp, i32, i32, i32]),
-        "gfdm_hip_resource_mapper_destroy": (i32, [vp]),
-        "gfdm_hip_resource_mapper_block_size": (i32, [vp]),
-        "gfdm_hip_resource_mapper_frame_size": (i32, [vp]),
-        "gfdm_hip_resource_mapper_map_host": (i32, [vp, vp, vp, i32, i64]),
-        "gfdm_hip_resource_mapper_map_device": (i32, [vp, vp, vp, i32, i64, vp]),
-        "gfdm_hip_resource_mapper_demap_host": (i32, [vp, vp, vp, i32, i64]),
-        "gfdm_hip_resource_mapper_demap_device": (i32, [vp, vp, vp, i32, i64, vp]),
-        "gfdm_hip_cyclic_prefixer_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, i32, vp, i32, i32, i32]),
-        "gfdm_hip_cyclic_prefixer_destroy": (i32, [vp]),
-        "gfdm_hip_cyclic_prefixer_block_size": (i32, [vp]),
-        "gfdm_hip_cyclic_prefixer_frame_size": (i32, [vp]),
-        "gfdm_hip_cyclic_prefixer_cyclic_shift": (i32, [vp]),
-        "gfdm_hip_cyclic_prefixer_add_host": (i32, [vp, vp, vp, i32, i64]),
-        "gfdm_hip_cyclic_prefixer_add_device": (i32, [vp, vp, vp, i32, i64, vp]),
-        "gfdm_hip_cyclic_prefixer_remove_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_cyclic_prefixer_remove_device": (i32, [vp, vp, vp, i64, vp]),
-        "gfdm_hip_channel_estimator_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, i32, i32, vp, i32, i32]),
-        "gfdm_hip_channel_estimator_destroy": (i32, [vp]),
-        "gfdm_hip_channel_estimator_timeslots": (i32, [vp]),
-        "gfdm_hip_channel_estimator_fft_len": (i32, [vp]),
-        "gfdm_hip_channel_estimator_active_subcarriers": (i32, [vp]),
-        "gfdm_hip_channel_estimator_frame_len": (i32, [vp]),
-        "gfdm_hip_channel_estimator_is_dc_free": (i32, [vp]),
-        "gfdm_hip_channel_estimator_filtered_len": (i32, [vp]),
-        "gfdm_hip_channel_estimator_kernel_name": (cp, [vp]),
-        "gfdm_hip_channel_estimator_preamble_filter_taps": (i32, [vp, vp]),
-        "gfdm_hip_channel_estimator_estimate_frame_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_channel_estimator_estimate_frame_device": (i32, [vp, vp, vp, i64, vp]),
-        "gfdm_hip_channel_estimator_estimate_preamble_channel_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_channel_estimator_estimate_preamble_channel_device": (i32, [vp, vp, vp, i64, vp]),
-        "gfdm_hip_channel_estimator_filter_preamble_estimate_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_channel_estimator_filter_preamble_estimate_device": (i32, [vp, vp, vp, i64, vp]),
-        "gfdm_hip_channel_estimator_interpolate_frame_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_channel_estimator_interpolate_frame_device": (i32, [vp, vp, vp, i64, vp]),
-        "gfdm_hip_channel_estimator_prepare_for_zf_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_channel_estimator_prepare_for_zf_device": (i32, [vp, vp, vp, i64, vp]),
-        "gfdm_hip_channel_estimator_estimate_snr_host": (i32, [vp, vp, vp, vp, i64]),
-        "gfdm_hip_channel_estimator_estimate_snr_device": (i32, [vp, vp, vp, vp, i64, vp]),
-        "gfdm_hip_receiver_set_channel_estimator": (i32, [vp, vp]),
-        "gfdm_hip_advanced_receiver_set_channel_estimator": (i32, [vp, vp]),
-        "gfdm_hip_receiver_io_layout": (i32, [vp, i32, i32, vp, vp, vp]),
-        "gfdm_hip_advanced_receiver_io_layout": (i32, [vp, i32, i32, vp, vp, vp]),
-        "gfdm_hip_receiver_demodulate_estimated_host": (i32, [vp, vp, vp, vp, i32, i32, i64]),
-        "gfdm_hip_receiver_demodulate_estimated_device": (i32, [vp, vp, vp, vp, i32, i32, i64, vp]),
-        "gfdm_hip_advanced_receiver_work_estimated_host": (i32, [vp, vp, vp, vp, i32, i32, i64]),
-        "gfdm_hip_advanced_receiver_work_estimated_device": (i32, [vp, vp, vp, vp, i32, i32, i64, vp]),
-        "gfdm_hip_receiver_demodulate_bursts_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64]),
-        "gfdm_hip_receiver_demodulate_bursts_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
-        "gfdm_hip_advanced_receiver_work_bursts_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64]),
-        "gfdm_hip_advanced_receiver_work_bursts_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
-        "gfdm_hip_burst_sync_create": (i32, [ctypes.POINTER(vp), i32, i32, vp, i32, i64, i32]),
-        "gfdm_hip_burst_sync_destroy": (i32, [vp]),
-        "gfdm_hip_burst_sync_fft_len": (i32, [vp]),
-        "gfdm_hip_burst_sync_cp_len": (i32, [vp]),
-        "gfdm_hip_burst_sync_window_len": (i64, [vp]),
-        "gfdm_hip_burst_sync_corr_len": (i64, [vp]),
-        "gfdm_hip_burst_sync_find_frame_start_host": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64]),
-        "gfdm_hip_burst_sync_find_frame_start_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-        "gfdm_hip_burst_sync_auto_correlate_host": (i32, [vp, vp, vp, vp, i64, i64, i64, i64]),
-        "gfdm_hip_burst_sync_auto_correlate_device": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-        "gfdm_hip_burst_sync_find_frame_start_at_host": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64]),
-        "gfdm_hip_burst_sync_find_frame_start_at_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]),
-        "gfdm_hip_burst_sync_detect_check": (i32, [i32, i32, i64, i64, f32, i64, i64, i64]),
-        "gfdm_hip_burst_sync_detect_workspace_bytes": (i64, [vp, i64]),
-        "gfdm_hip_burst_sync_detect_host": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64]),
-        "gfdm_hip_burst_sync_detect_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64, vp, vp]),
-        "gfdm_hip_burst_extractor_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, i32]),
-        "gfdm_hip_burst_extractor_destroy": (i32, [vp]),
-        "gfdm_hip_burst_extractor_burst_len": (i32, [vp]),
-        "gfdm_hip_burst_extractor_tag_backoff": (i32, [vp]),
-        "gfdm_hip_burst_extractor_set_cfo_correction": (i32, [vp, i32]),
-        "gfdm_hip_burst_extractor_get_cfo_correction": (i32, [vp]),
-        "gfdm_hip_burst_extractor_extract_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i64]),
-        "gfdm_hip_burst_extractor_extract_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i64, vp]),
-        # the sc16 twins: the same signatures, `samples` interleaved int16 I/Q
-        "gfdm_hip_receiver_demodulate_bursts_sc16_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64]),
-        "gfdm_hip_receiver_demodulate_bursts_sc16_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
-        "gfdm_hip_advanced_receiver_work_bursts_sc16_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64]),
-        "gfdm_hip_advanced_receiver_work_bursts_sc16_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
-        "gfdm_hip_burst_sync_find_frame_start_sc16_host": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64]),
-        "gfdm_hip_burst_sync_find_frame_start_sc16_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-        "gfdm_hip_burst_sync_auto_correlate_sc16_host": (i32, [vp, vp, vp, vp, i64, i64, i64, i64]),
-        "gfdm_hip_burst_sync_auto_correlate_sc16_device": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-        "gfdm_hip_burst_sync_find_frame_start_at_sc16_host": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64]),
-        "gfdm_hip_burst_sync_find_frame_start_at_sc16_device": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]),
-        "gfdm_hip_burst_sync_detect_sc16_host": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64]),
-        "gfdm_hip_burst_sync_detect_sc16_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, f32, i64, i64, i64, vp, vp]),
-        "gfdm_hip_burst_extractor_extract_sc16_host": (i32, [vp, vp, vp, i64, vp, vp, vp, i64]),
-        "gfdm_hip_burst_extractor_extract_sc16_device": (i32, [vp, vp, vp, i64, vp, vp, vp, i64, vp]),
-        "gfdm_hip_burst_shaper_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, f32, f32, i32]),
-        "gfdm_hip_burst_shaper_destroy": (i32, [vp]),
-        "gfdm_hip_burst_shaper_frame_len": (i32, [vp]),
-        "gfdm_hip_burst_shaper_pre_padding": (i32, [vp]),
-        "gfdm_hip_burst_shaper_post_padding": (i32, [vp]),
-        "gfdm_hip_burst_shaper_scale": (i32, [vp, vp]),
-        "gfdm_hip_burst_shaper_check": (i32, [i32, i32, i32, f64, i64, i64]),
-        "gfdm_hip_burst_shaper_workspace_bytes": (i64, [vp, i64, i64]),
-        "gfdm_hip_burst_shaper_shape_host": (i32, [vp, vp, vp, i64]),
-        "gfdm_hip_burst_shaper_shape_device": (i32, [vp, vp, vp, i64, vp, vp]),
-        "gfdm_hip_burst_shaper_shape_sc16_host": (i32, [vp, vp, vp, i64, f64]),
-        "gfdm_hip_burst_shaper_shape_sc16_device": (i32, [vp, vp, vp, i64, f64, vp, vp]),
-        "gfdm_hip_burst_shaper_place_host": (i32, [vp, vp, i64, vp, vp, vp, i64]),
-        "gfdm_hip_burst_shaper_place_device": (i32, [vp, vp, i64, vp, vp, vp, i64, vp, vp]),
-        "gfdm_hip_burst_shaper_place_sc16_host": (i32, [vp, vp, i64, vp, vp, vp, i64, f64]),
-        "gfdm_hip_burst_shaper_place_sc16_device": (i32, [vp, vp, i64, vp, vp, vp, i64, f64, vp, vp]),
-        "gfdm_hip_symbol_mapper_create": (i32, [ctypes.POINTER(vp), vp, i32, i32, i32]),
-        "gfdm_hip_symbol_mapper_destroy": (i32, [vp]),
-        "gfdm_hip_symbol_mapper_bits_per_symbol": (i32, [vp]),
-        "gfdm_hip_symbol_mapper_n_points": (i32, [vp]),
-        "gfdm_hip_symbol_mapper_decision": (i32, [vp]),
-        "gfdm_hip_symbol_mapper_points": (i32, [vp, vp]),
-        "gfdm_hip_symbol_mapper_row_bytes": (i64, [vp, i64]),
-        "gfdm_hip_symbol_mapper_check": (i32, [i32, i64, i64]),
-        "gfdm_hip_symbol_mapper_map_host": (i32, [vp, vp, vp, vp, i64, i64]),
-        "gfdm_hip_symbol_mapper_map_device": (i32, [vp, vp, vp, vp, i64, i64, vp]),
-        "gfdm_hip_symbol_mapper_decode_host": (i32, [vp, vp, vp, vp, i64, i64]),
-        "gfdm_hip_symbol_mapper_decode_device": (i32, [vp, vp, vp, vp, i64, i64, vp]),
-        "gfdm_hip_symbol_mapper_soft_host": (i32, [vp, vp, vp, vp, vp, i64, i64]),
-        "gfdm_hip_symbol_mapper_soft_device": (i32, [vp, vp, vp, vp, vp, i64, i64, vp]),
-        "gfdm_hip_channel_model_create": (i32, [ctypes.POINTER(vp), vp, i32, f64, f64, u64, i32]),
-        "gfdm_hip_channel_model_destroy": (i32, [vp]),
-        "gfdm_hip_channel_model_n_taps": (i32, [vp]),
-        "gfdm_hip_channel_model_taps": (i32, [vp, vp]),
-        "gfdm_hip_channel_model_frequency_offset": (i32, [vp, ctypes.POINTER(f64)]),
-        "gfdm_hip_channel_model_noise_voltage": (i32, [vp, ctypes.POINTER(f64)]),
-        "gfdm_hip_channel_model_seed": (i32, [vp, ctypes.POINTER(u64)]),
-        "gfdm_hip_channel_model_set_frequency_offset": (i32, [vp, f64]),
-        "gfdm_hip_channel_model_set_noise_voltage": (i32, [vp, f64]),
-        "gfdm_hip_channel_model_set_seed": (i32, [vp, u64]),
-        "gfdm_hip_channel_model_check": (i32, [i32, f64, f64, i64, i64, i64, f64]),
-        "gfdm_hip_channel_model_apply_host": (i32, [vp, vp, vp, i64, i64, i64]),
-        "gfdm_hip_channel_model_apply_device": (i32, [vp, vp, vp, i64, i64, i64, vp]),
-        "gfdm_hip_channel_model_apply_sc16_host": (i32, [vp, vp, vp, i64, i64, i64, f64]),
-        "gfdm_hip_channel_model_apply_sc16_device": (i32, [vp, vp, vp, i64, i64, i64, f64, vp]),
-        "gfdm_hip_link_meter_create": (i32, [ctypes.POINTER(vp), vp, i32, i32, i32]),
-        "gfdm_hip_link_meter_destroy": (i32, [vp]),
-        "gfdm_hip_link_meter_bits_per_symbol": (i32, [vp]),
-        "gfdm_hip_link_meter_n_points": (i32, [vp]),
-        "gfdm_hip_link_meter_decision": (i32, [vp]),
-        "gfdm_hip_link_meter_row_bytes": (i64, [vp, i64]),
-        "gfdm_hip_link_meter_totals_device": (vp, [vp]),
-        "gfdm_hip_link_meter_reset": (i32, [vp, vp]),
-        "gfdm_hip_link_meter_totals": (i32, [vp, vp, vp]),
-        "gfdm_hip_link_meter_match_workspace_bytes": (i64, [i64]),
-        "gfdm_hip_link_meter_measure_workspace_bytes": (i64, [i64, i64]),
-        "gfdm_hip_link_meter_match_host": (i32, [vp, vp, vp, vp, vp, i64, vp, i64, i64, i64]),
-        "gfdm_hip_link_meter_match_device": (i32, [vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, vp]),
-        "gfdm_hip_link_meter_measure_host": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64]),
-        "gfdm_hip_link_meter_measure_device": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, vp, vp]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)          # AttributeError here == the library does not export a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    L._gfdm_symbols = sorted(sig)
-    # background builds must not outlive the interpreter's tear-down of the HIP runtime (gfdm_hip_quiesce: include/gfdm_hip.h)
-    import atexit
-    atexit.register(L.gfdm_hip_quiesce)
-    _lib = L
-    return L
-
-
-def exported_symbols():
-    return list(lib()._gfdm_symbols)
-
-
-def _check(status):
-    if status == OK:
-        return
-    L = lib()
-    msg = (L.gfdm_hip_last_error() or b"").decode() or L.gfdm_hip_strerror(status).decode()
-    if status in (EINVAL_TAPS, EINVAL_OVERLAP, EINVAL):
-        raise ValueError(msg)            # std::invalid_argument in the reference (pybind11 maps it to ValueError)
-    raise GfdmHipError(status, msg)
+PAGE = mmap.PAGESIZE
+C64, F32, I64, I32, I16, U8 = np.complex64, np.float32, np.int64, np.int32, np.int16, np.uint8
 
 
 def _c64(a):
+    """a host-side configuration array (taps, points, preambles) as C-contiguous complex64"""
     return np.ascontiguousarray(a, dtype=np.complex64)
-
-
-def _is_tensor(x):
-    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
-
-
-def _dev_ptr(t, n_elems, what, device=None):
-    import torch
-    if not t.is_cuda or t.dtype != torch.complex64 or not t.is_contiguous():
-        raise TypeError("%s must be a contiguous complex64 CUDA/HIP tensor" % what)
-    if device is not None and t.device.index != device:
-        raise RuntimeError("%s lives on GPU %d, the kernel handle on GPU %d" % (what, t.device.index, device))
-    if t.numel() != n_elems:
-        raise RuntimeError("%s has %d elements, expected %d" % (what, t.numel(), n_elems))
-    return t.data_ptr()
 
 
 def to_sc16(signal, peak=0.9 * 2048):
@@ -337,62 +45,11 @@ def from_sc16(iq):
     a = np.asarray(iq)
     if a.dtype != np.int16:
         raise TypeError("from_sc16 takes int16 I/Q values, not %s" % a.dtype)
-    a = _sc16_pairs(a.shape, "iq", a.reshape)
+    a = ops.sc16_pairs(a.shape, "iq", a.reshape)
     out = np.empty(a.shape[0], np.complex64)
     out.real = a[:, 0]
     out.imag = a[:, 1]
     return out
-
-
-def _sc16_pairs(shape, what, reshape=None):
-    """number of samples of an sc16 array of `shape` -- (n, 2) or flat (2n,) -- or, with `reshape`, the array as (n, 2)"""
-    shape = tuple(shape)
-    if len(shape) == 2 and shape[1] == 2:
-        n = shape[0]
-    elif len(shape) == 1:
-        if shape[0] % 2:
-            raise ValueError("%s: a flat sc16 array holds I, Q pairs, its length(%d) is odd" % (what, shape[0]))
-        n = shape[0] // 2
-    else:
-        raise ValueError("%s: an sc16 array has shape (n, 2) or (2n,), not %s" % (what, shape))
-    return n if reshape is None else reshape(n, 2)
-
-
-def _capture(samples, device, what="samples"):
-    """A capture argument -> (pointer, n_samples, name infix, keep-alive): complex64 (anything _c64 takes on the host path, a contiguous
-    complex64 tensor on the device path: infix "") or sc16 (a contiguous int16 array / tensor of shape (n, 2) or (2n,): infix "_sc16",
-    passed on as it is, never widened).  Any other integer dtype is a TypeError.  Checks come before anything touches the device."""
-    if _is_tensor(samples):
-        import torch
-        if samples.dtype == torch.int16:
-            n = _sc16_pairs(samples.shape, what)
-            if not samples.is_cuda or not samples.is_contiguous():
-                raise TypeError("%s must be a contiguous int16 CUDA/HIP tensor" % what)
-            if samples.device.index != device:
-                raise RuntimeError("%s lives on GPU %d, the kernel handle on GPU %d" % (what, samples.device.index, device))
-            return samples.data_ptr(), n, "_sc16", samples
-        if not (samples.dtype.is_floating_point or samples.dtype.is_complex):
-            raise TypeError("%s: integer captures must be int16 (sc16), not %s" % (what, samples.dtype))
-        return _dev_ptr(samples, samples.numel(), what, device), samples.numel(), "", samples
-    a = np.asarray(samples)
-    if a.dtype == np.int16:
-        n = _sc16_pairs(a.shape, what)
-        if not a.flags.c_contiguous:
-            raise TypeError("%s must be a C-contiguous int16 array" % what)
-        return a.ctypes.data, n, "_sc16", a
-    if np.issubdtype(a.dtype, np.integer):
-        raise TypeError("%s: integer captures must be int16 (sc16), not %s" % (what, a.dtype))
-    a = _c64(a).ravel()
-    return a.ctypes.data, a.size, "", a
-
-
-def _stream_ptr(stream, device=None):
-    if stream is None:
-        import torch
-        return torch.cuda.current_stream(device).cuda_stream      # the current stream of the HANDLE's GPU, not of torch's current one
-    if hasattr(stream, "cuda_stream"):
-        return stream.cuda_stream
-    return int(stream)
 
 
 class generic_family_for_testing:
@@ -507,13 +164,9 @@ class registered_host:
         return False
 
 
-PAGE = mmap.PAGESIZE
-
-
 def aligned_empty(shape, dtype=np.complex64):
     """An uninitialised C-contiguous array that starts on a page boundary and owns its pages to the end of the last one: what register_host takes
     (gfdm_hip_register_host pins whole pages).  The backing buffer stays alive with the array."""
-    import mmap
     n = int(np.prod(shape)) * np.dtype(dtype).itemsize
     size = max(PAGE, -(-n // PAGE) * PAGE)
     buf = mmap.mmap(-1, size)                          # anonymous, page aligned, page granular
@@ -544,22 +197,49 @@ def set_dft_matrix_cores(mode):
     return lib().gfdm_hip_set_dft_matrix_cores(int(mode))
 
 
+def _device_out(out, lead, refuse=False):
+    """`out` of a call whose host flavour takes none: there it returns a new array whatever `out` is (refuse: it raises a TypeError)"""
+    if ops.on_device(lead):
+        return out
+    if refuse and out is not None:
+        raise TypeError("out is for device tensors; the numpy path returns a new array")
+    return None
+
+
+_ABSENT = object()                 # _blockwise: the entry point takes no second input
+
+
 class _Kernel:
-    """Shared plumbing: host (numpy) and device (torch) batched calls."""
+    """Shared plumbing: one handle on one GPU, and the one way a batched call reaches its host (numpy) or device (torch) entry point.
+    A method checks and sizes its operands with _operands (ops), then hands their pointers to _run."""
     _destroy = None
     _dev = 0                       # GPU the handle was created on: every tensor and the stream of a call must belong to it
 
-    def _dp(self, t, n_elems, what):
-        return _dev_ptr(t, n_elems, what, self._dev)
-
     def _sp(self, stream):
-        return _stream_ptr(stream, self._dev)
+        """the stream of a device call as the C-ABI takes it: a torch stream, a raw hipStream_t, or None for the current one"""
+        if stream is None:
+            import torch
+            return torch.cuda.current_stream(self._dev).cuda_stream      # the current stream of the HANDLE's GPU, not of torch's current one
+        if hasattr(stream, "cuda_stream"):
+            return stream.cuda_stream
+        return int(stream)
 
-    def __del__(self):
+    def __del__(self, loaded=_abi.loaded):              # (bound here: module globals may be gone when the interpreter shuts down)
         h = getattr(self, "_h", None)
-        if h and _lib is not None and self._destroy:
-            getattr(_lib, self._destroy)(h)
+        L = loaded()
+        if h and L is not None and self._destroy:
+            getattr(L, self._destroy)(h)
             self._h = None
+
+    def _run(self, stem, lead, args, stream=None, scratch=None):
+        """<stem>_device(handle, *args, [workspace,] stream) where the leading operand is a device tensor, else <stem>_host(handle, *args).
+        Entry points with a device workspace give `scratch`: a callable that returns the workspace tensor of this call, or None for NULL."""
+        if not ops.on_device(lead):
+            return _check(getattr(lib(), stem + "_host")(self._h, *args))
+        if scratch is not None:
+            ws = scratch()                                     # alive until the call has returned
+            args += (ops.ptr(ws),)
+        _check(getattr(lib(), stem + "_device")(self._h, *args, self._sp(stream)))
 
     def _nblocks(self, size, what="Input"):
         n = self.block_size()
@@ -567,37 +247,41 @@ class _Kernel:
             raise RuntimeError("%s vector size(%d) MUST be a multiple of block_size(%d)!" % (what, size, n))
         return size // n
 
-    def _host(self, fn, x, extra=(), extra_ok_none=False, out=None):
-        """numpy path: the *_host entry point on the arrays' memory.  `out`: an existing complex64 array to write into (e.g. one registered with
-        register_host, so that the call runs in place on it)."""
-        x = _c64(x)
-        nb = self._nblocks(x.size)
-        ptrs = []
-        keep = []
-        for e in extra:
-            if e is None:
-                if not extra_ok_none:
-                    raise RuntimeError("missing input vector")
-                ptrs.append(None)
-            else:
-                e = _c64(e)
-                if e.size != x.size:
-                    raise RuntimeError("Channel vector size(%d) MUST be equal to input size(%d)!" % (e.size, x.size))
-                keep.append(e)
-                ptrs.append(e.ctypes.data)
+    def _blockwise(self, stem, x, out, stream, vector=_ABSENT, vector_ok_none=False):
+        """out = f(x[, vector]), all of x's size, any whole number of blocks: numpy in -> numpy out, a torch device tensor in -> `out` tensor,
+        asynchronous on `stream`.  `out` may be an existing array (e.g. one registered with register_host: the call runs in place on it).
+        vector: the second input of the entry points that have one (an equaliser, the other domain's symbols), None for NULL."""
+        x, px, n = ops.bound(x, C64, "in", self._dev)
+        host = not ops.on_device(x)
+        nb = self._nblocks(n)
+        pv = None
+        if vector is not None and vector is not _ABSENT:
+            vector, pv, nv = ops.bound(vector, C64, "extra input", self._dev, x)
+            if nv != n:
+                raise RuntimeError("Channel vector size(%d) MUST be equal to input size(%d)!" % (nv, n))
+        elif vector is None and host and not vector_ok_none:   # (the device flavour reads a missing vector as "none")
+            raise RuntimeError("missing input vector")
         if out is None:
-            out = np.empty(x.shape, np.complex64)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.complex64 and out.flags.c_contiguous and out.size == x.size):
-            raise TypeError("out must be a C-contiguous complex64 numpy array of the input's size")
-        _check(fn(self._h, out.ctypes.data, x.ctypes.data, *ptrs, nb))
+            out = ops.result(x, x.shape, C64, self._dev)
+            po = ops.ptr(out)
+        else:
+            if host and not isinstance(out, np.ndarray):
+                raise TypeError("out must be a C-contiguous complex64 numpy array of the input's size")
+            checked, po, n_out = ops.bound(out, C64, "out", self._dev, x)
+            if host and (checked is not out or n_out != n):    # a host result is written in place: nothing bound() had to convert
+                raise TypeError("out must be a C-contiguous complex64 numpy array of the input's size")
+            if n_out != n:
+                raise RuntimeError("out has %d elements, expected %d" % (n_out, n))
+        self._run(stem, x, (po, px, nb) if vector is _ABSENT else (po, px, pv, nb), stream)
         return out
 
-    def _device(self, fn, out, x, extra=(), stream=None):
-        n = x.numel()
-        nb = self._nblocks(n)
-        ptrs = [None if e is None else self._dp(e, n, "extra input") for e in extra]
-        _check(fn(self._h, self._dp(out, n, "out"), self._dp(x, n, "in"), *ptrs, nb, self._sp(stream)))
-        return out
+    def _batched(self, stem, x, n_in, n_out, args, stream, out):
+        """(nblocks, n_out) = f(x of nblocks * n_in, *args); the host flavour gives one block that came 1-D back 1-D"""
+        nb = ops.batches(x, n_in, "input size(%d) MUST be a multiple of %d!")
+        x = ops.operand(x, C64, "in", self._dev)
+        res = ops.result(x, (nb, n_out), C64, self._dev, _device_out(out, x))
+        self._run(stem, x, (ops.ptr(res), ops.ptr(x), *args, nb), stream)
+        return res[0] if (not ops.on_device(x) and x.ndim == 1 and nb == 1) else res
 
 
 class _Receiver(_Kernel):
@@ -609,9 +293,12 @@ class _Receiver(_Kernel):
     def _fn(self, name):
         return getattr(lib(), self._stem + "_" + name)
 
+    def _call_stem(self, kind):
+        return "%s_%s_%s" % (self._stem, self._verb, kind)
+
     @property
     def _bursts_prefix(self):
-        return "%s_%s_bursts" % (self._stem, self._verb)
+        return self._call_stem("bursts")
 
     def _layout(self, estimated, nout_arg):
         """(n_in, n_out, estimator fft_len) of one frames / estimated call, asked from the library (gfdm_hip_*_io_layout): it alone
@@ -633,25 +320,13 @@ class _Receiver(_Kernel):
         nout_arg = -1 if noutput_size is None else int(noutput_size)
         frame_len, nout, _ = self._layout(False, nout_arg)
         N = self.block_size()
-        if _is_tensor(frames):
-            import torch
-            if frames.numel() % frame_len:
-                raise RuntimeError("frames size(%d) MUST be a multiple of frame_len(%d)!" % (frames.numel(), frame_len))
-            nb = frames.numel() // frame_len
-            out = torch.empty(nb, nout, dtype=torch.complex64, device=frames.device) if out is None else out
-            feq = None if f_eq is None else self._dp(f_eq, nb * N, "f_eq")
-            _check(self._fn(self._verb + "_frames_device")(self._h, self._dp(out, nb * nout, "out"), self._dp(frames, nb * frame_len, "frames"),
-                                                        feq, nout_arg, nb, self._sp(stream)))
-            return out
-        x = _c64(frames)
-        if x.size % frame_len:
-            raise RuntimeError("frames size(%d) MUST be a multiple of frame_len(%d)!" % (x.size, frame_len))
-        nb = x.size // frame_len
-        e = None if f_eq is None else _c64(f_eq)
-        if e is not None and e.size != nb * N:
-            raise RuntimeError("Channel vector size(%d) MUST be equal to nframes * block_size(%d)!" % (e.size, nb * N))
-        res = np.empty((nb, nout), np.complex64)
-        _check(self._fn(self._verb + "_frames_host")(self._h, res.ctypes.data, x.ctypes.data, None if e is None else e.ctypes.data, nout_arg, nb))
+        x = ops.operand(frames, C64, "frames", self._dev)
+        nb = ops.batches(x, frame_len, "frames size(%d) MUST be a multiple of frame_len(%d)!")
+        e = None if f_eq is None else ops.operand(f_eq, C64, "f_eq", self._dev, x, "frames")
+        if e is not None and ops.size(e) != nb * N:
+            raise RuntimeError("Channel vector size(%d) MUST be equal to nframes * block_size(%d)!" % (ops.size(e), nb * N))
+        res = ops.result(x, (nb, nout), C64, self._dev, _device_out(out, x))
+        self._run(self._call_stem("frames"), x, (ops.ptr(res), ops.ptr(x), ops.ptr(e), nout_arg, nb), stream)
         return res
 
     # ---- channel estimator fused in front of the receiver ----
@@ -668,29 +343,12 @@ class _Receiver(_Kernel):
         nout_arg = -1 if noutput_size is None else int(noutput_size)
         n_in, nout, fft_len = self._layout(True, nout_arg)
         stride = int(preamble_stride) if preamble_stride else 2 * fft_len
-        if _is_tensor(x):
-            import torch
-            if x.numel() % n_in:
-                raise RuntimeError("Input size(%d) MUST be a multiple of %d!" % (x.numel(), n_in))
-            nb = x.numel() // n_in
-            out = torch.empty(nb, nout, dtype=torch.complex64, device=x.device) if out is None else out
-            need = (nb - 1) * stride + 2 * fft_len if nb else 0
-            if rx_preamble.numel() < need:
-                raise RuntimeError("rx_preamble has %d elements, at least %d are needed" % (rx_preamble.numel(), need))
-            self._dp(rx_preamble, rx_preamble.numel(), "rx_preamble")
-            _check(self._fn(self._verb + "_estimated_device")(self._h, self._dp(out, nb * nout, "out"), self._dp(x, nb * n_in, "in"),
-                                                              rx_preamble.data_ptr(), int(preamble_stride), nout_arg, nb, self._sp(stream)))
-            return out
-        a = _c64(x)
-        if a.size % n_in:
-            raise RuntimeError("Input size(%d) MUST be a multiple of %d!" % (a.size, n_in))
-        nb = a.size // n_in
-        pre = _c64(rx_preamble)
-        need = (nb - 1) * stride + 2 * fft_len if nb else 0
-        if pre.size < need:
-            raise RuntimeError("rx_preamble size(%d) MUST be at least %d!" % (pre.size, need))
-        res = np.empty((nb, nout), np.complex64)
-        _check(self._fn(self._verb + "_estimated_host")(self._h, res.ctypes.data, a.ctypes.data, pre.ctypes.data, int(preamble_stride), nout_arg, nb))
+        x = ops.operand(x, C64, "in", self._dev)
+        nb = ops.batches(x, n_in, "Input size(%d) MUST be a multiple of %d!")
+        pre = ops.operand(rx_preamble, C64, "rx_preamble", self._dev, x)
+        ops.at_least(pre, (nb - 1) * stride + 2 * fft_len if nb else 0, "rx_preamble")
+        res = ops.result(x, (nb, nout), C64, self._dev, _device_out(out, x))
+        self._run(self._call_stem("estimated"), x, (ops.ptr(res), ops.ptr(x), ops.ptr(pre), int(preamble_stride), nout_arg, nb), stream)
         return res
 
     def demodulate_bursts(self, samples, offsets, sc_rot=None, count=None, backoff=0, preamble_offset=0, cfo_correction=True, noutput_size=None,
@@ -701,34 +359,18 @@ class _Receiver(_Kernel):
         r = sync.detect(...) feeds it as demodulate_bursts(samples, r["frame_start"], r["sc_rot"], r["count"], ...).
         Torch device tensors run the device entry point (no allocation beyond `out`, no synchronisation), numpy arrays the host one.
         An int16 capture, shape (n, 2) or (2n,), is read as sc16 (the *_sc16_* entry points): bit-equal to the call on from_sc16(samples)."""
-        sptr, slen, fmt, _keep = _capture(samples, self._dev)
-        L = lib()
+        s, slen, fmt = ops.capture(samples, self._dev)
         if getattr(self, "_estimator", None) is None:
             raise ValueError("set_channel_estimator has not been called on this handle")
         nout_arg = -1 if noutput_size is None else int(noutput_size)
         _, nout, _ = self._layout(True, nout_arg)
-        args = (int(backoff), int(preamble_offset), int(bool(cfo_correction)), nout_arg)
-        if _is_tensor(samples):
-            import torch
-            n = offsets.numel()
-            out = torch.empty(n, nout, dtype=torch.complex64, device=samples.device) if out is None else out
-            rp = None if sc_rot is None else _dev_arg(sc_rot, torch.complex64, n, "sc_rot", self._dev)
-            cp = None if count is None else _dev_arg(count, torch.int64, 1, "count", self._dev)
-            _check(getattr(L, self._bursts_prefix + fmt + "_device")(self._h, self._dp(out, n * nout, "out"), sptr, slen,
-                                                                    _dev_arg(offsets, torch.int64, n, "offsets", self._dev), rp, cp, *args, n,
-                                                                    self._sp(stream)))
-            return out
-        off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
-        n = off.size
-        rot = None if sc_rot is None else _c64(sc_rot).ravel()
-        if rot is not None and rot.size != n:
-            raise RuntimeError("sc_rot has %d elements, expected %d" % (rot.size, n))
-        cnt = None if count is None else np.ascontiguousarray(count, dtype=np.int64).ravel()
-        if cnt is not None and cnt.size != 1:
-            raise RuntimeError("count has %d elements, expected 1" % cnt.size)
-        res = np.empty((n, nout), np.complex64)
-        _check(getattr(L, self._bursts_prefix + fmt + "_host")(self._h, res.ctypes.data, sptr, slen, off.ctypes.data,
-                                                              None if rot is None else rot.ctypes.data, None if cnt is None else cnt.ctypes.data, *args, n))
+        off = ops.vector(offsets, I64, "offsets", self._dev, s, as_what="samples")
+        n = ops.size(off)
+        rot = None if sc_rot is None else ops.vector(sc_rot, C64, "sc_rot", self._dev, s, n, "samples")
+        cnt = ops.count_arg(count, s, self._dev)
+        res = ops.result(s, (n, nout), C64, self._dev, _device_out(out, s))
+        self._run(self._bursts_prefix + fmt, s, (ops.ptr(res), ops.ptr(s), slen, ops.ptr(off), ops.ptr(rot), ops.ptr(cnt), int(backoff),
+                                                       int(preamble_offset), int(bool(cfo_correction)), nout_arg, n), stream)
         return res
 
 
@@ -764,11 +406,7 @@ class Modulator(_Kernel):
 
     def modulate(self, x, out=None, stream=None):
         """numpy in -> numpy out (any whole number of blocks); torch CUDA tensor in -> `out` tensor, async on `stream`."""
-        if _is_tensor(x):
-            import torch
-            out = torch.empty_like(x) if out is None else out
-            return self._device(lib().gfdm_hip_modulator_work_device, out, x, stream=stream)
-        return self._host(lib().gfdm_hip_modulator_work_host, x, out=out)
+        return self._blockwise("gfdm_hip_modulator_work", x, out, stream)
 
 
 class Demodulator(_Receiver):
@@ -810,31 +448,23 @@ class Demodulator(_Receiver):
         _check(lib().gfdm_hip_receiver_ic_filter_taps(self._h, out.ctypes.data))
         return out
 
-    def _call(self, name, x, extra, out, stream, extra_ok_none=False):
-        L = lib()
-        if _is_tensor(x):
-            import torch
-            out = torch.empty_like(x) if out is None else out
-            return self._device(getattr(L, name + "_device"), out, x, extra, stream)
-        return self._host(getattr(L, name + "_host"), x, extra, extra_ok_none, out=out)
-
     def demodulate(self, x, out=None, stream=None):
-        return self._call("gfdm_hip_receiver_demodulate", x, (None,), out, stream, True)
+        return self._blockwise("gfdm_hip_receiver_demodulate", x, out, stream, None, True)
 
     def demodulate_equalize(self, x, f_eq, out=None, stream=None):
-        return self._call("gfdm_hip_receiver_demodulate", x, (f_eq,), out, stream)
+        return self._blockwise("gfdm_hip_receiver_demodulate", x, out, stream, f_eq)
 
     def fft_filter_downsample(self, x, out=None, stream=None):
-        return self._call("gfdm_hip_receiver_fft_filter_downsample", x, (None,), out, stream, True)
+        return self._blockwise("gfdm_hip_receiver_fft_filter_downsample", x, out, stream, None, True)
 
     def fft_equalize_filter_downsample(self, x, f_eq, out=None, stream=None):
-        return self._call("gfdm_hip_receiver_fft_filter_downsample", x, (f_eq,), out, stream)
+        return self._blockwise("gfdm_hip_receiver_fft_filter_downsample", x, out, stream, f_eq)
 
     def transform_subcarriers_to_td(self, x, out=None, stream=None):
-        return self._call("gfdm_hip_receiver_transform_subcarriers_to_td", x, (), out, stream)
+        return self._blockwise("gfdm_hip_receiver_transform_subcarriers_to_td", x, out, stream)
 
     def cancel_sc_interference(self, td, fd, out=None, stream=None):
-        return self._call("gfdm_hip_receiver_cancel_sc_interference", td, (fd,), out, stream)
+        return self._blockwise("gfdm_hip_receiver_cancel_sc_interference", td, out, stream, fd)
 
 
 class AdvancedReceiver(_Receiver):
@@ -885,21 +515,13 @@ class AdvancedReceiver(_Receiver):
     def get_phase_compensation(self):
         return lib().gfdm_hip_advanced_receiver_get_phase_compensation(self._h)
 
-    def _call(self, x, f_eq, out, stream):
-        L = lib()
-        if _is_tensor(x):
-            import torch
-            out = torch.empty_like(x) if out is None else out
-            return self._device(L.gfdm_hip_advanced_receiver_work_device, out, x, (f_eq,), stream)
-        return self._host(L.gfdm_hip_advanced_receiver_work_host, x, (f_eq,), True, out=out)
-
     def demodulate(self, x, out=None, stream=None):
         """generic_work: IC receiver without equaliser."""
-        return self._call(x, None, out, stream)
+        return self._blockwise("gfdm_hip_advanced_receiver_work", x, out, stream, None, True)
 
     def demodulate_equalize(self, x, f_eq, out=None, stream=None):
         """generic_work_equalize: one f_eq vector per block."""
-        return self._call(x, f_eq, out, stream)
+        return self._blockwise("gfdm_hip_advanced_receiver_work", x, out, stream, f_eq, True)
 
 
 class Transmitter(_Kernel):
@@ -945,34 +567,24 @@ class Transmitter(_Kernel):
 
     def _split(self, x, ninput_size):
         n = self.input_vector_size() if ninput_size is None else int(ninput_size)
-        size = x.numel() if _is_tensor(x) else np.asarray(x).size
-        if n <= 0 or size % n:
-            raise RuntimeError("input size(%d) MUST be a multiple of ninput_size(%d)!" % (size, n))
-        return n, size // n
+        return n, ops.batches(x, n, "input size(%d) MUST be a multiple of ninput_size(%d)!")
 
     def transmit(self, symbols, ninput_size=None, n_ports=None, stream=None, outs=None):
         """All ports (or the first n_ports): list of (nblocks, output_vector_size) arrays / tensors, one per cyclic shift.
         `outs` (device path only): one tensor of nblocks * output_vector_size elements per port to write into."""
-        L = lib()
         n, nb = self._split(symbols, ninput_size)
         ports = len(self._shifts) if n_ports is None else n_ports
         F = self.output_vector_size()
-        if _is_tensor(symbols):
-            import torch
-            if outs is None:
-                outs = [torch.empty(nb, F, dtype=torch.complex64, device=symbols.device) for _ in range(ports)]
-            elif len(outs) != ports:
-                raise RuntimeError("outs has %d tensors, expected one per port (%d)" % (len(outs), ports))
-            outs = list(outs)
-            arr = (ctypes.c_void_p * ports)(*[self._dp(o, nb * F, "outs[%d]" % i) for i, o in enumerate(outs)])
-            _check(L.gfdm_hip_transmitter_work_device(self._h, arr, ports, self._dp(symbols, nb * n, "in"), n, nb, self._sp(stream)))
-            return outs
-        if outs is not None:
+        x = ops.operand(symbols, C64, "in", self._dev)
+        if outs is None:
+            outs = [None] * ports
+        elif not ops.on_device(x):
             raise TypeError("outs is for device tensors; the numpy path returns new arrays")
-        x = _c64(symbols)
-        outs = [np.empty((nb, F), np.complex64) for _ in range(ports)]
-        arr = (ctypes.c_void_p * ports)(*[o.ctypes.data for o in outs])
-        _check(L.gfdm_hip_transmitter_work_host(self._h, arr, ports, x.ctypes.data, n, nb))
+        elif len(outs) != ports:
+            raise RuntimeError("outs has %d tensors, expected one per port (%d)" % (len(outs), ports))
+        outs = [ops.result(x, (nb, F), C64, self._dev, o, "outs[%d]" % i) for i, o in enumerate(outs)]
+        arr = (ctypes.c_void_p * ports)(*[ops.ptr(o) for o in outs])
+        self._run("gfdm_hip_transmitter_work", x, (arr, ports, ops.ptr(x), n, nb), stream)
         return outs
 
     def generic_work(self, symbols, ninput_size=None):
@@ -980,36 +592,21 @@ class Transmitter(_Kernel):
         return self.transmit(symbols, ninput_size, 1)[0]
 
     def modulate(self, symbols, ninput_size=None, stream=None, out=None):
-        L = lib()
         n, nb = self._split(symbols, ninput_size)
         N = self.block_size()
-        if _is_tensor(symbols):
-            import torch
-            out = torch.empty(nb, N, dtype=torch.complex64, device=symbols.device) if out is None else out
-            _check(L.gfdm_hip_transmitter_modulate_device(self._h, self._dp(out, nb * N, "out"), self._dp(symbols, nb * n, "in"), n, nb, self._sp(stream)))
-            return out
-        if out is not None:
-            raise TypeError("out is for device tensors; the numpy path returns a new array")
-        x = _c64(symbols)
-        out = np.empty((nb, N), np.complex64)
-        _check(L.gfdm_hip_transmitter_modulate_host(self._h, out.ctypes.data, x.ctypes.data, n, nb))
+        x = ops.operand(symbols, C64, "in", self._dev)
+        out = ops.result(x, (nb, N), C64, self._dev, _device_out(out, x, refuse=True))
+        self._run("gfdm_hip_transmitter_modulate", x, (ops.ptr(out), ops.ptr(x), n, nb), stream)
         return out
 
     def add_frame(self, blocks, cyclic_shift, stream=None, out=None):
-        L = lib()
         N, F = self.block_size(), self.output_vector_size()
-        if _is_tensor(blocks):
-            import torch
-            nb = blocks.numel() // N
-            out = torch.empty(nb, F, dtype=torch.complex64, device=blocks.device) if out is None else out
-            _check(L.gfdm_hip_transmitter_add_frame_device(self._h, self._dp(out, nb * F, "out"), self._dp(blocks, nb * N, "in"), int(cyclic_shift), nb, self._sp(stream)))
-            return out
-        if out is not None:
-            raise TypeError("out is for device tensors; the numpy path returns a new array")
-        x = _c64(blocks)
-        nb = x.size // N
-        out = np.empty((nb, F), np.complex64)
-        _check(L.gfdm_hip_transmitter_add_frame_host(self._h, out.ctypes.data, x.ctypes.data, int(cyclic_shift), nb))
+        x = ops.operand(blocks, C64, "in", self._dev)
+        nb = ops.size(x) // N
+        if ops.on_device(x):                                   # (the host flavour leaves an incomplete last block unread)
+            ops.sized(x, nb * N, "in")
+        out = ops.result(x, (nb, F), C64, self._dev, _device_out(out, x, refuse=True))
+        self._run("gfdm_hip_transmitter_add_frame", x, (ops.ptr(out), ops.ptr(x), int(cyclic_shift), nb), stream)
         return out
 
 
@@ -1033,34 +630,16 @@ class ResourceMapper(_Kernel):
     def frame_size(self):
         return lib().gfdm_hip_resource_mapper_frame_size(self._h)
 
-    def _run(self, host, dev, x, n_in, n_out, size_arg, stream, out=None):
-        size = x.numel() if _is_tensor(x) else np.asarray(x).size
-        if n_in <= 0 or size % n_in:
-            raise RuntimeError("input size(%d) MUST be a multiple of %d!" % (size, n_in))
-        nb = size // n_in
-        if _is_tensor(x):
-            import torch
-            if out is None:
-                out = torch.empty(nb, n_out, dtype=torch.complex64, device=x.device)
-            _check(dev(self._h, self._dp(out, nb * n_out, "out"), self._dp(x, size, "in"), size_arg, nb, self._sp(stream)))
-            return out
-        a = _c64(x)
-        out = np.empty((nb, n_out), np.complex64)
-        _check(host(self._h, out.ctypes.data, a.ctypes.data, size_arg, nb))
-        return out[0] if (np.asarray(x).ndim == 1 and nb == 1) else out
-
     def map_to_resources(self, symbols, ninput_size=None, stream=None, out=None):
         """ninput_size symbols per block (default block_size) -> frame_size grid values per block, unfilled slots zero."""
         n = self.block_size() if ninput_size is None else int(ninput_size)
         if n == 0:
             raise RuntimeError("ninput_size 0: give the number of blocks through a [nblocks][0] input of the C-ABI instead")
-        L = lib()
-        return self._run(L.gfdm_hip_resource_mapper_map_host, L.gfdm_hip_resource_mapper_map_device, symbols, n, self.frame_size(), n, stream, out)
+        return self._batched("gfdm_hip_resource_mapper_map", symbols, n, self.frame_size(), (n,), stream, out)
 
     def demap_from_resources(self, grid, noutput_size=None, stream=None, out=None):
         n = self.block_size() if noutput_size is None else int(noutput_size)
-        L = lib()
-        return self._run(L.gfdm_hip_resource_mapper_demap_host, L.gfdm_hip_resource_mapper_demap_device, grid, self.frame_size(), n, n, stream, out)
+        return self._batched("gfdm_hip_resource_mapper_demap", grid, self.frame_size(), n, (n,), stream, out)
 
 
 class CyclicPrefixer(_Kernel):
@@ -1085,44 +664,14 @@ class CyclicPrefixer(_Kernel):
     def cyclic_shift(self):
         return lib().gfdm_hip_cyclic_prefixer_cyclic_shift(self._h)
 
-    def _batch(self, x, n_in):
-        size = x.numel() if _is_tensor(x) else np.asarray(x).size
-        if size % n_in:
-            raise RuntimeError("input size(%d) MUST be a multiple of %d!" % (size, n_in))
-        return size, size // n_in
-
     def add_cyclic_prefix(self, blocks, cyclic_shift=None, stream=None, out=None):
-        L = lib()
         s = self.cyclic_shift() if cyclic_shift is None else int(cyclic_shift)
-        N, F = self.block_size(), self.frame_size()
-        size, nb = self._batch(blocks, N)
-        if _is_tensor(blocks):
-            import torch
-            if out is None:
-                out = torch.empty(nb, F, dtype=torch.complex64, device=blocks.device)
-            _check(L.gfdm_hip_cyclic_prefixer_add_device(self._h, self._dp(out, nb * F, "out"), self._dp(blocks, size, "in"), s, nb, self._sp(stream)))
-            return out
-        a = _c64(blocks)
-        out = np.empty((nb, F), np.complex64)
-        _check(L.gfdm_hip_cyclic_prefixer_add_host(self._h, out.ctypes.data, a.ctypes.data, s, nb))
-        return out[0] if (np.asarray(blocks).ndim == 1 and nb == 1) else out
+        return self._batched("gfdm_hip_cyclic_prefixer_add", blocks, self.block_size(), self.frame_size(), (s,), stream, out)
 
     generic_work = add_cyclic_prefix
 
     def remove_cyclic_prefix(self, frames, stream=None, out=None):
-        L = lib()
-        N, F = self.block_size(), self.frame_size()
-        size, nb = self._batch(frames, F)
-        if _is_tensor(frames):
-            import torch
-            if out is None:
-                out = torch.empty(nb, N, dtype=torch.complex64, device=frames.device)
-            _check(L.gfdm_hip_cyclic_prefixer_remove_device(self._h, self._dp(out, nb * N, "out"), self._dp(frames, size, "in"), nb, self._sp(stream)))
-            return out
-        a = _c64(frames)
-        out = np.empty((nb, N), np.complex64)
-        _check(L.gfdm_hip_cyclic_prefixer_remove_host(self._h, out.ctypes.data, a.ctypes.data, nb))
-        return out[0] if (np.asarray(frames).ndim == 1 and nb == 1) else out
+        return self._batched("gfdm_hip_cyclic_prefixer_remove", frames, self.frame_size(), self.block_size(), (), stream, out)
 
 
 class ChannelEstimator(_Kernel):
@@ -1172,64 +721,41 @@ class ChannelEstimator(_Kernel):
     def _lens(self):
         return {"rx": 2 * self.fft_len(), "est": self.fft_len(), "filt": self.filtered_len(), "frame": self.frame_len()}
 
-    def _run(self, name, x, n_in, n_out, stream):
-        L = lib()
-        if _is_tensor(x):
-            import torch
-            if x.numel() % n_in:
-                raise RuntimeError("Input size %d is not a multiple of %d" % (x.numel(), n_in))
-            nf = x.numel() // n_in
-            out = torch.empty((nf, n_out) if x.dim() > 1 or nf != 1 else (n_out,), dtype=torch.complex64, device=x.device)
-            _check(getattr(L, name + "_device")(self._h, out.data_ptr(), self._dp(x, nf * n_in, "in"), nf, self._sp(stream)))
-            return out
-        a = _c64(x)
-        if a.size % n_in:
-            raise RuntimeError("Input size %d is not a multiple of %d" % (a.size, n_in))
-        nf = a.size // n_in
-        out = np.empty((nf, n_out) if a.ndim > 1 or nf != 1 else (n_out,), np.complex64)
-        _check(getattr(L, name + "_host")(self._h, out.ctypes.data, a.ctypes.data, nf))
+    def _frames(self, x, n_in):
+        """x checked, and its number of frames of n_in"""
+        x = ops.operand(x, C64, "in", self._dev)
+        return x, ops.batches(x, n_in, "Input size %d is not a multiple of %d")
+
+    def _stage(self, name, x, n_in, n_out, stream):
+        lens = self._lens()
+        x, nf = self._frames(x, lens[n_in])
+        n_out = lens[n_out]
+        out = ops.result(x, (nf, n_out) if x.ndim > 1 or nf != 1 else (n_out,), C64, self._dev)
+        self._run("gfdm_hip_channel_estimator_" + name, x, (ops.ptr(out), ops.ptr(x), nf), stream)
         return out
 
     def estimate_frame(self, rx_preamble, stream=None):
-        n = self._lens()
-        return self._run("gfdm_hip_channel_estimator_estimate_frame", rx_preamble, n["rx"], n["frame"], stream)
+        return self._stage("estimate_frame", rx_preamble, "rx", "frame", stream)
 
     def estimate_preamble_channel(self, rx_preamble, stream=None):
-        n = self._lens()
-        return self._run("gfdm_hip_channel_estimator_estimate_preamble_channel", rx_preamble, n["rx"], n["est"], stream)
+        return self._stage("estimate_preamble_channel", rx_preamble, "rx", "est", stream)
 
     def filter_preamble_estimate(self, estimate, stream=None):
-        n = self._lens()
-        return self._run("gfdm_hip_channel_estimator_filter_preamble_estimate", estimate, n["est"], n["filt"], stream)
+        return self._stage("filter_preamble_estimate", estimate, "est", "filt", stream)
 
     def interpolate_frame(self, filtered, stream=None):
-        n = self._lens()
-        return self._run("gfdm_hip_channel_estimator_interpolate_frame", filtered, n["filt"], n["frame"], stream)
+        return self._stage("interpolate_frame", filtered, "filt", "frame", stream)
 
     def prepare_for_zf(self, frame_estimate, stream=None):
-        n = self._lens()
-        return self._run("gfdm_hip_channel_estimator_prepare_for_zf", frame_estimate, n["frame"], n["frame"], stream)
+        return self._stage("prepare_for_zf", frame_estimate, "frame", "frame", stream)
 
     def estimate_snr(self, rx_preamble, stream=None):
         """(snr_lin, cnrs): scalars / [active] for one preamble, [nframes] / [nframes][active] for a batch."""
-        L = lib()
-        n_in, A = 2 * self.fft_len(), self.active_subcarriers()
-        if _is_tensor(rx_preamble):
-            import torch
-            nf = rx_preamble.numel() // n_in
-            snr = torch.empty(nf, dtype=torch.float32, device=rx_preamble.device)
-            cnrs = torch.empty(nf, A, dtype=torch.float32, device=rx_preamble.device)
-            _check(L.gfdm_hip_channel_estimator_estimate_snr_device(self._h, snr.data_ptr(), cnrs.data_ptr(), self._dp(rx_preamble, nf * n_in, "in"),
-                                                                    nf, self._sp(stream)))
-            return snr, cnrs
-        a = _c64(rx_preamble)
-        if a.size % n_in:
-            raise RuntimeError("Input size %d is not a multiple of %d" % (a.size, n_in))
-        nf = a.size // n_in
-        snr = np.empty(nf, np.float32)
-        cnrs = np.empty((nf, A), np.float32)
-        _check(L.gfdm_hip_channel_estimator_estimate_snr_host(self._h, snr.ctypes.data, cnrs.ctypes.data, a.ctypes.data, nf))
-        if a.ndim <= 1 and nf == 1:
+        x, nf = self._frames(rx_preamble, 2 * self.fft_len())
+        snr = ops.result(x, (nf,), F32, self._dev)
+        cnrs = ops.result(x, (nf, self.active_subcarriers()), F32, self._dev)
+        self._run("gfdm_hip_channel_estimator_estimate_snr", x, (ops.ptr(snr), ops.ptr(cnrs), ops.ptr(x), nf), stream)
+        if not ops.on_device(x) and x.ndim <= 1 and nf == 1:                    # (the device flavour keeps the batch shape)
             return float(snr[0]), cnrs[0]
         return snr, cnrs
 
@@ -1242,17 +768,6 @@ def threshold_factor(false_alarm_prob):
     return float(np.sqrt(-(4 / np.pi) * np.log(false_alarm_prob)))
 
 
-def _dev_arg(t, dtype, n_elems, what, device):
-    """device pointer of a contiguous torch tensor of `dtype` with n_elems elements on `device`"""
-    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        raise TypeError("%s must be a contiguous %s CUDA/HIP tensor" % (what, dtype))
-    if t.device.index != device:
-        raise RuntimeError("%s lives on GPU %d, the handle on GPU %d" % (what, t.device.index, device))
-    if t.numel() != n_elems:
-        raise RuntimeError("%s has %d elements, expected %d" % (what, t.numel(), n_elems))
-    return t.data_ptr()
-
-
 class BurstSync(_Kernel):
     """Preamble timing / CFO synchronisation: pygfdm's find_frame_start (python/pygfdm/synchronization.py:154-263) on every window
     stream[first + b * stride : ... + window_len] of a capture buffer (contract in include/gfdm_hip.h).  numpy samples -> numpy results
@@ -1260,6 +775,7 @@ class BurstSync(_Kernel):
     takes `samples` also takes an sc16 capture -- int16 I/Q of shape (n, 2) or (2n,), numpy or torch -- and reads it as it is (the *_sc16_*
     entry points): bit-equal to the call on from_sc16(samples)."""
     _destroy = "gfdm_hip_burst_sync_destroy"
+    _OUT = (("frame_start", I64), ("coarse", I64), ("cfo", F32), ("metric", F32), ("sc_rot", C64))
 
     def __init__(self, fft_len, cp_len, core_preamble, window_len, device=0):
         p = _c64(core_preamble).ravel()
@@ -1284,51 +800,28 @@ class BurstSync(_Kernel):
     def _grid(self, first, stride, n_windows):
         return int(first), self.window_len() if stride is None else int(stride), int(n_windows)
 
+    def _outputs(self, n, like):
+        """the five per-window result arrays, of `like`'s kind, and their pointers in the C-ABI's order"""
+        r = {key: ops.result(like, (n,), dtype, self._dev) for key, dtype in self._OUT}
+        return r, [ops.ptr(a) for a in r.values()]
+
     def find_frame_start(self, samples, first=0, stride=None, n_windows=1, stream=None):
         """dict of per-window arrays: frame_start, coarse (stream indices, int64), cfo, metric (float32), sc_rot (complex64).
         stride defaults to window_len (windows back to back)."""
-        sptr, n, fmt, _keep = _capture(samples, self._dev)
-        L = lib()
+        s, n, fmt = ops.capture(samples, self._dev)
         first, stride, nw = self._grid(first, stride, n_windows)
-        if _is_tensor(samples):
-            r = self._outputs(nw, samples.device)
-            _check(getattr(L, "gfdm_hip_burst_sync_find_frame_start%s_device" % fmt)(self._h, *[r[k].data_ptr() for k in self._OUT], sptr, n, first, stride, nw,
-                                                                                    self._sp(stream)))
-            return r
-        r = self._outputs(nw)
-        _check(getattr(L, "gfdm_hip_burst_sync_find_frame_start%s_host" % fmt)(self._h, *[r[k].ctypes.data for k in self._OUT], sptr, n, first, stride, nw))
+        r, ptrs = self._outputs(nw, s)
+        self._run("gfdm_hip_burst_sync_find_frame_start" + fmt, s, (*ptrs, ops.ptr(s), n, first, stride, nw), stream)
         return r
-
-    _OUT = ("frame_start", "coarse", "cfo", "metric", "sc_rot")
-
-    @staticmethod
-    def _outputs(n, device=None):
-        """the five per-window result arrays: torch tensors on `device`, numpy arrays without one"""
-        if device is None:
-            return {"frame_start": np.empty(n, np.int64), "coarse": np.empty(n, np.int64), "cfo": np.empty(n, np.float32),
-                    "metric": np.empty(n, np.float32), "sc_rot": np.empty(n, np.complex64)}
-        import torch
-        return {"frame_start": torch.empty(n, dtype=torch.int64, device=device), "coarse": torch.empty(n, dtype=torch.int64, device=device),
-                "cfo": torch.empty(n, dtype=torch.float32, device=device), "metric": torch.empty(n, dtype=torch.float32, device=device),
-                "sc_rot": torch.empty(n, dtype=torch.complex64, device=device)}
 
     def find_frame_start_at(self, samples, starts, stream=None):
         """find_frame_start on the windows samples[st : st + window_len], st = clamp(starts[w], 0, len(samples) - window_len): the same
         dict, bit-equal per window to find_frame_start(first=st).  starts: int64 (a device tensor when samples is one)."""
-        sptr, n, fmt, _keep = _capture(samples, self._dev)
-        L = lib()
-        if _is_tensor(samples):
-            import torch
-            nw = starts.numel()
-            r = self._outputs(nw, samples.device)
-            _check(getattr(L, "gfdm_hip_burst_sync_find_frame_start_at%s_device" % fmt)(self._h, *[r[k].data_ptr() for k in self._OUT], sptr, n,
-                                                                                       _dev_arg(starts, torch.int64, nw, "starts", self._dev), nw,
-                                                                                       self._sp(stream)))
-            return r
-        st = np.ascontiguousarray(starts, dtype=np.int64).ravel()
-        r = self._outputs(st.size)
-        _check(getattr(L, "gfdm_hip_burst_sync_find_frame_start_at%s_host" % fmt)(self._h, *[r[k].ctypes.data for k in self._OUT], sptr, n, st.ctypes.data,
-                                                                                 st.size))
+        s, n, fmt = ops.capture(samples, self._dev)
+        st = ops.vector(starts, I64, "starts", self._dev, s, as_what="samples")
+        nw = ops.size(st)
+        r, ptrs = self._outputs(nw, s)
+        self._run("gfdm_hip_burst_sync_find_frame_start_at" + fmt, s, (*ptrs, ops.ptr(s), n, ops.ptr(st), nw), stream)
         return r
 
     def detect(self, samples, threshold, min_distance, lead=None, max_bursts=None, stream=None):
@@ -1337,7 +830,7 @@ class BurstSync(_Kernel):
         count (total peaks found: int on the host path, a one-element int64 tensor on the device path, which does not synchronise) and
         the five find_frame_start arrays with max_bursts slots, those from min(count, max_bursts) on at frame_start = coarse = -1.
         Defaults: lead = cp_len + fft_len // 2, max_bursts = ceil(P / (min_distance + 1)), the most peaks P positions can hold."""
-        sptr, n, fmt, _keep = _capture(samples, self._dev)
+        s, n, fmt = ops.capture(samples, self._dev)
         L = lib()
         R = int(min_distance)
         lead = self.cp_len() + self.fft_len() // 2 if lead is None else int(lead)
@@ -1345,39 +838,22 @@ class BurstSync(_Kernel):
             max_bursts = max(0, -(-(n - 2 * self.fft_len()) // (max(R, 0) + 1)))
         nb = int(max_bursts)
         _check(L.gfdm_hip_burst_sync_detect_check(self.fft_len(), self.cp_len(), self.window_len(), n, threshold, R, lead, nb))
-        if _is_tensor(samples):
-            import torch
-            d = samples.device
-            r = self._outputs(nb, d)
-            count = torch.empty(1, dtype=torch.int64, device=d)
-            ws = torch.empty(L.gfdm_hip_burst_sync_detect_workspace_bytes(self._h, n), dtype=torch.uint8, device=d)
-            _check(getattr(L, "gfdm_hip_burst_sync_detect%s_device" % fmt)(self._h, count.data_ptr(), *[r[k].data_ptr() for k in self._OUT], sptr, n,
-                                                                          threshold, R, lead, nb, ws.data_ptr(), self._sp(stream)))
-            r["count"] = count
-            return r
-        r = self._outputs(nb)
-        count = np.zeros(1, np.int64)
-        _check(getattr(L, "gfdm_hip_burst_sync_detect%s_host" % fmt)(self._h, count.ctypes.data, *[r[k].ctypes.data for k in self._OUT], sptr, n, threshold, R,
-                                                                    lead, nb))
-        r["count"] = int(count[0])
+        r, ptrs = self._outputs(nb, s)
+        host = not ops.on_device(s)
+        count = np.zeros(1, np.int64) if host else ops.result(s, (1,), I64, self._dev)
+        self._run("gfdm_hip_burst_sync_detect" + fmt, s, (ops.ptr(count), *ptrs, ops.ptr(s), n, threshold, R, lead, nb), stream,
+                  scratch=lambda: ops.workspace(None, s, L.gfdm_hip_burst_sync_detect_workspace_bytes(self._h, n), self._dev))
+        r["count"] = int(count[0]) if host else count
         return r
 
     def auto_correlate(self, samples, first=0, stride=None, n_windows=1, stream=None):
         """(ac, ic): [n_windows][corr_len] complex64 / float32 (pygfdm's auto_correlate_signal and abs_integrate)."""
-        sptr, n, fmt, _keep = _capture(samples, self._dev)
-        L = lib()
+        s, n, fmt = ops.capture(samples, self._dev)
         first, stride, nw = self._grid(first, stride, n_windows)
         P = self.corr_len()
-        if _is_tensor(samples):
-            import torch
-            ac = torch.empty(nw, P, dtype=torch.complex64, device=samples.device)
-            ic = torch.empty(nw, P, dtype=torch.float32, device=samples.device)
-            _check(getattr(L, "gfdm_hip_burst_sync_auto_correlate%s_device" % fmt)(self._h, ac.data_ptr(), ic.data_ptr(), sptr, n, first, stride, nw,
-                                                                                  self._sp(stream)))
-            return ac, ic
-        ac = np.empty((nw, P), np.complex64)
-        ic = np.empty((nw, P), np.float32)
-        _check(getattr(L, "gfdm_hip_burst_sync_auto_correlate%s_host" % fmt)(self._h, ac.ctypes.data, ic.ctypes.data, sptr, n, first, stride, nw))
+        ac = ops.result(s, (nw, P), C64, self._dev)
+        ic = ops.result(s, (nw, P), F32, self._dev)
+        self._run("gfdm_hip_burst_sync_auto_correlate" + fmt, s, (ops.ptr(ac), ops.ptr(ic), ops.ptr(s), n, first, stride, nw), stream)
         return ac, ic
 
 
@@ -1410,29 +886,14 @@ class BurstExtractor(_Kernel):
     def extract(self, samples, offsets, scale=None, sc_rot=None, stream=None):
         """[n][burst_len] bursts; offsets are tag positions in `samples` (the extractor subtracts tag_backoff).  An int16 capture, shape (n, 2)
         or (2n,), is read as sc16, unscaled: scale = 1 / 32768 gives unit full scale."""
-        sptr, slen, fmt, _keep = _capture(samples, self._dev)
-        L = lib()
+        s, slen, fmt = ops.capture(samples, self._dev)
         B = self.burst_len()
-        if _is_tensor(samples):
-            import torch
-            n = offsets.numel()
-            out = torch.empty(n, B, dtype=torch.complex64, device=samples.device)
-            sp = None if scale is None else _dev_arg(scale, torch.float32, n, "scale", self._dev)
-            rp = None if sc_rot is None else _dev_arg(sc_rot, torch.complex64, n, "sc_rot", self._dev)
-            _check(getattr(L, "gfdm_hip_burst_extractor_extract%s_device" % fmt)(self._h, out.data_ptr(), sptr, slen,
-                                                                                _dev_arg(offsets, torch.int64, n, "offsets", self._dev), sp, rp, n,
-                                                                                self._sp(stream)))
-            return out
-        off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
-        n = off.size
-        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32).ravel()
-        rot = None if sc_rot is None else _c64(sc_rot).ravel()
-        for v, what in ((sc, "scale"), (rot, "sc_rot")):
-            if v is not None and v.size != n:
-                raise RuntimeError("%s has %d elements, expected %d" % (what, v.size, n))
-        out = np.empty((n, B), np.complex64)
-        _check(getattr(L, "gfdm_hip_burst_extractor_extract%s_host" % fmt)(self._h, out.ctypes.data, sptr, slen, off.ctypes.data,
-                                                                          None if sc is None else sc.ctypes.data, None if rot is None else rot.ctypes.data, n))
+        off = ops.vector(offsets, I64, "offsets", self._dev, s, as_what="samples")
+        n = ops.size(off)
+        sc = None if scale is None else ops.vector(scale, F32, "scale", self._dev, s, n, "samples")
+        rot = None if sc_rot is None else ops.vector(sc_rot, C64, "sc_rot", self._dev, s, n, "samples")
+        out = ops.result(s, (n, B), C64, self._dev)
+        self._run("gfdm_hip_burst_extractor_extract" + fmt, s, (ops.ptr(out), ops.ptr(s), slen, ops.ptr(off), ops.ptr(sc), ops.ptr(rot), n), stream)
         return out
 
 
@@ -1479,151 +940,97 @@ class BurstShaper(_Kernel):
         return n
 
     @staticmethod
-    def _peak(sc16, peak):
+    def _ports(call, frames, out):
+        """`frames` a list of per-port arrays: call(frames[p], out[p]) for every port, `out` (if given) holding one array per port"""
+        if out is not None and len(out) != len(frames):
+            raise ValueError("out must hold one array per port")
+        return [call(f, None if out is None else out[p]) for p, f in enumerate(frames)]
+
+    def _arguments(self, frames, out, sc16, peak):
+        """(frames, peak) as the C-ABI takes them: what can be said of frames, out and peak without the handle is raised here"""
         if peak is None:
-            return 0.0
-        if not sc16:
+            pk = 0.0
+        elif not sc16:
             raise ValueError("peak normalises sc16 output: pass sc16=True (complex64 output is scaled by `scale` alone)")
-        if not 0 < peak <= 32767:
+        elif not 0 < peak <= 32767:
             raise ValueError("peak must lie in (0, 32767]")
-        return float(peak)
-
-    @staticmethod
-    def _kinds(frames, out, sc16, what="frames"):
-        """what can be said of frames and out without the handle (kind, dtype, layout): raised before the library is asked"""
-        if _is_tensor(frames):
-            import torch
-            if frames.dtype != torch.complex64 or not frames.is_cuda or not frames.is_contiguous():
-                raise TypeError("%s must be a contiguous complex64 CUDA/HIP tensor" % what)
         else:
-            a = np.asarray(frames)
-            if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.complexfloating)):
-                raise TypeError("%s must be complex samples, not %s" % (what, a.dtype))
-            frames = _c64(a).ravel()
-        if out is not None:
-            if _is_tensor(out) != _is_tensor(frames):
-                raise TypeError("out must be a %s, as %s is" % ("CUDA/HIP tensor" if _is_tensor(frames) else "numpy array", what))
-            if not _is_tensor(out) and not isinstance(out, np.ndarray):
-                raise TypeError("out must be a numpy array")
-            have = str(out.dtype).replace("torch.", "")
-            if have != ("int16" if sc16 else "complex64"):
-                raise TypeError("out must be %s, not %s" % ("int16 I/Q (sc16)" if sc16 else "complex64", have))
-            contiguous = out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous
-            if not contiguous:
-                raise TypeError("out must be contiguous")
-            if sc16:
-                _sc16_pairs(out.shape, "out")
-        return frames
+            pk = float(peak)
+        frames = ops.operand(frames, C64, "frames", self._dev, floating=True)
+        ops.check_result(out, frames, I16 if sc16 else C64, self._dev, as_what="frames")
+        return frames, pk
 
-    def _frames(self, frames):
-        """n_bursts of the frames of one port: any shape whose size is a multiple of frame_len"""
-        F = self.frame_len()
-        size = frames.numel() if _is_tensor(frames) else frames.size
-        if size % F:
-            raise RuntimeError("frames size(%d) MUST be a multiple of frame_len(%d)!" % (size, F))
-        return size // F
+    def _geometry(self, pk, n, out_len):
+        """the library's own check of a call's geometry: before anything else is said of starts and count, or allocated"""
+        _check(lib().gfdm_hip_burst_shaper_check(self.frame_len(), self.pre_padding(), self.post_padding(), pk, n, out_len))
 
-    def _out(self, out, n, sc16, like):
-        """the output array of n samples -- `out` (checked by _kinds), or a new one of `like`'s kind -- and its pointer"""
-        if out is None:
-            if _is_tensor(like):
-                import torch
-                out = torch.empty((n, 2) if sc16 else (n,), dtype=torch.int16 if sc16 else torch.complex64, device=like.device)
-            else:
-                out = np.empty((n, 2) if sc16 else (n,), np.int16 if sc16 else np.complex64)
-        have = _sc16_pairs(out.shape, "out") if sc16 else (out.numel() if _is_tensor(out) else out.size)
-        if have != n:
-            raise RuntimeError("out holds %d samples, expected %d" % (have, n))
-        if _is_tensor(out):
-            if out.device.index != self._dev:
-                raise RuntimeError("out lives on GPU %d, the handle on GPU %d" % (out.device.index, self._dev))
-            return out, out.data_ptr()
-        return out, out.ctypes.data
-
-    def _workspace(self, ws, like, n, out_len, pk):
-        """pointer of the device scratch of a normalised call (`ws`: a uint8 device tensor of workspace_bytes(), or None for a new one)"""
-        if not pk:
-            return None, None
-        import torch
-        need = self.workspace_bytes(n, out_len)
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=like.device)
-        elif not _is_tensor(ws) or ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < need or ws.device.index != self._dev:
-            raise TypeError("workspace must be a contiguous uint8 CUDA/HIP tensor of at least %d bytes on GPU %d" % (need, self._dev))
-        return ws, ws.data_ptr()
+    def _call(self, name, frames, n, out_len, sc16, pk, out, stream, workspace, *args):
+        """make the result of out_len samples and run gfdm_hip_burst_shaper_<name>[_sc16](handle, result, *args[, peak])"""
+        res = ops.stream_result(frames, out_len, sc16, self._dev, out, "frames")
+        self._run("gfdm_hip_burst_shaper_" + name + ("_sc16" if sc16 else ""), frames, (ops.ptr(res),) + args + ((pk,) if sc16 else ()), stream,
+                  scratch=lambda: ops.workspace(workspace, frames, self.workspace_bytes(n, out_len), self._dev) if pk else None)
+        return res
 
     def shape(self, frames, sc16=False, peak=None, out=None, stream=None, workspace=None):
         """n_bursts * slot_len() samples: every frame scaled, behind pre_padding and in front of post_padding zeros.  workspace (device path,
         normalised sc16 only): a uint8 tensor of workspace_bytes() to use instead of a new one; afterwards its first two floats are the gain
         and the largest component found."""
         if isinstance(frames, (list, tuple)):
-            if out is not None and len(out) != len(frames):
-                raise ValueError("out must hold one array per port")
-            return [self.shape(f, sc16, peak, None if out is None else out[p], stream, workspace) for p, f in enumerate(frames)]
-        pk = self._peak(sc16, peak)
-        frames = self._kinds(frames, out, sc16)
-        n = self._frames(frames)
-        L = lib()
-        _check(L.gfdm_hip_burst_shaper_check(self.frame_len(), self.pre_padding(), self.post_padding(), pk, n, n * self.slot_len()))
-        res, optr = self._out(out, n * self.slot_len(), sc16, frames)
-        if _is_tensor(frames):
-            fptr = self._dp(frames, frames.numel(), "frames")
-            ws, wptr = self._workspace(workspace, frames, n, n * self.slot_len(), pk)
-            if sc16:
-                _check(L.gfdm_hip_burst_shaper_shape_sc16_device(self._h, optr, fptr, n, pk, wptr, self._sp(stream)))
-            else:
-                _check(L.gfdm_hip_burst_shaper_shape_device(self._h, optr, fptr, n, wptr, self._sp(stream)))
-            return res
-        if sc16:
-            _check(L.gfdm_hip_burst_shaper_shape_sc16_host(self._h, optr, frames.ctypes.data, n, pk))
-        else:
-            _check(L.gfdm_hip_burst_shaper_shape_host(self._h, optr, frames.ctypes.data, n))
-        return res
+            return self._ports(lambda f, out: self.shape(f, sc16, peak, out, stream, workspace), frames, out)
+        frames, pk = self._arguments(frames, out, sc16, peak)
+        n = ops.batches(frames, self.frame_len(), "frames size(%d) MUST be a multiple of frame_len(%d)!")
+        self._geometry(pk, n, n * self.slot_len())
+        return self._call("shape", frames, n, n * self.slot_len(), sc16, pk, out, stream, workspace, ops.ptr(frames), n)
 
     def place(self, frames, starts, out_len, count=None, sc16=False, peak=None, out=None, stream=None, workspace=None):
         """out_len samples: frame b from sample starts[b] on (starts ascending, int64; a device tensor when frames is one), zeros
         elsewhere.  count (an int, or on the device path a one-element int64 tensor such as detect's) limits the call to the first
         count frames; it is clamped to [0, n_bursts].  workspace: as in shape()."""
         if isinstance(frames, (list, tuple)):
-            if out is not None and len(out) != len(frames):
-                raise ValueError("out must hold one array per port")
-            return [self.place(f, starts, out_len, count, sc16, peak, None if out is None else out[p], stream, workspace) for p, f in enumerate(frames)]
-        pk = self._peak(sc16, peak)
-        frames = self._kinds(frames, out, sc16)
-        if _is_tensor(frames) != _is_tensor(starts):
-            raise TypeError("starts must be %s, as frames is" % ("a torch.int64 CUDA/HIP tensor" if _is_tensor(frames) else "an integer array"))
-        n = self._frames(frames)
+            return self._ports(lambda f, out: self.place(f, starts, out_len, count, sc16, peak, out, stream, workspace), frames, out)
+        frames, pk = self._arguments(frames, out, sc16, peak)
+        st = ops.vector(starts, I64, "starts", self._dev, frames, as_what="frames")
+        n = ops.batches(frames, self.frame_len(), "frames size(%d) MUST be a multiple of frame_len(%d)!")
         out_len = int(out_len)
-        L = lib()
-        _check(L.gfdm_hip_burst_shaper_check(self.frame_len(), self.pre_padding(), self.post_padding(), pk, n, out_len))
-        if _is_tensor(frames):
-            import torch
-            sptr = _dev_arg(starts, torch.int64, n, "starts", self._dev)
-            if count is not None and not _is_tensor(count):
-                count = torch.full((1,), int(count), dtype=torch.int64, device=frames.device)
-            cptr = None if count is None else _dev_arg(count, torch.int64, 1, "count", self._dev)
-            res, optr = self._out(out, out_len, sc16, frames)
-            fptr = self._dp(frames, frames.numel(), "frames")
-            ws, wptr = self._workspace(workspace, frames, n, out_len, pk)
-            if sc16:
-                _check(L.gfdm_hip_burst_shaper_place_sc16_device(self._h, optr, out_len, fptr, sptr, cptr, n, pk, wptr, self._sp(stream)))
-            else:
-                _check(L.gfdm_hip_burst_shaper_place_device(self._h, optr, out_len, fptr, sptr, cptr, n, wptr, self._sp(stream)))
-            return res
-        st = np.ascontiguousarray(starts, dtype=np.int64).ravel()
-        if st.size != n:
-            raise RuntimeError("starts has %d elements, expected %d" % (st.size, n))
-        cnt = None if count is None else np.array([int(count)], np.int64)
-        res, optr = self._out(out, out_len, sc16, frames)
-        cptr = None if cnt is None else cnt.ctypes.data
-        if sc16:
-            _check(L.gfdm_hip_burst_shaper_place_sc16_host(self._h, optr, out_len, frames.ctypes.data, st.ctypes.data, cptr, n, pk))
-        else:
-            _check(L.gfdm_hip_burst_shaper_place_host(self._h, optr, out_len, frames.ctypes.data, st.ctypes.data, cptr, n))
-        return res
+        self._geometry(pk, n, out_len)
+        ops.sized(st, n, "starts")
+        cnt = ops.count_arg(count, frames, self._dev)
+        return self._call("place", frames, n, out_len, sc16, pk, out, stream, workspace, out_len, ops.ptr(frames), ops.ptr(st), ops.ptr(cnt), n)
 
 
-class SymbolMapper(_Kernel):
+class _Rows(_Kernel):
+    """What SymbolMapper and LinkMeter share: a constellation handle of the C-ABI kind `_kind`, calls on rows of symbols."""
+    _kind = None                   # "gfdm_hip_symbol_mapper" | "gfdm_hip_link_meter"
+
+    def __init__(self, points, decision=DECIDE_AUTO, device=0):
+        pts = _c64(np.asarray(points).ravel())
+        h = ctypes.c_void_p()
+        _check(getattr(lib(), self._kind + "_create")(ctypes.byref(h), pts.ctypes.data, pts.size, DECIDE.get(decision, decision), device))
+        self._h = h
+        self._dev = int(device)
+        self._k = getattr(lib(), self._kind + "_bits_per_symbol")(h)
+
+    def bits_per_symbol(self):
+        return self._k
+
+    def decision_rule(self):
+        """'nearest' | 'qpsk' | 'bpsk': the rule SymbolMapper.decode and LinkMeter.measure decide by (gfdm_hip_*_decision)"""
+        code = getattr(lib(), self._kind + "_decision")(self._h)
+        return {v: k for k, v in DECIDE.items() if k != "auto"}[code]
+
+    def row_bytes(self, n_sym):
+        """bytes of a packed row of n_sym symbols: ceil(n_sym * k / 8)"""
+        return _bytes(getattr(lib(), self._kind + "_row_bytes")(self._h, int(n_sym)))
+
+
+def _bytes(n):
+    """a byte count of the C-ABI: negative values are its status codes"""
+    if n < 0:
+        _check(n)
+    return n
+
+
+class SymbolMapper(_Rows):
     """Payload bytes <-> constellation symbols, and max-log soft bits (contract in include/gfdm_hip.h, gfdm_hip_symbol_mapper): map() is
     repack_bits_bb(8 -> k, MSB first) + chunks_to_symbols in front of Transmitter.transmit, decode() is constellation_decoder_cb +
     repack_bits_bb(k -> 8) behind demodulate_frames / demodulate_estimated / demodulate_bursts, soft() feeds a decoder instead.  Rows are
@@ -1632,17 +1039,7 @@ class SymbolMapper(_Kernel):
     flavour on the current stream unless given.  count (an int, or on the device path a one-element int64 tensor such as detect's) limits
     the call to the first count rows, the rest is written as zeros; it is clamped to [0, n_rows]."""
     _destroy = "gfdm_hip_symbol_mapper_destroy"
-
-    def __init__(self, points, decision=DECIDE_AUTO, device=0):
-        pts = _c64(np.asarray(points).ravel())
-        h = ctypes.c_void_p()
-        _check(lib().gfdm_hip_symbol_mapper_create(ctypes.byref(h), pts.ctypes.data, pts.size, DECIDE.get(decision, decision), device))
-        self._h = h
-        self._dev = int(device)
-        self._k = lib().gfdm_hip_symbol_mapper_bits_per_symbol(h)
-
-    def bits_per_symbol(self):
-        return self._k
+    _kind = "gfdm_hip_symbol_mapper"
 
     def points(self):
         """the points as given to the constructor (complex64, bit for bit)"""
@@ -1650,131 +1047,42 @@ class SymbolMapper(_Kernel):
         _check(lib().gfdm_hip_symbol_mapper_points(self._h, p.ctypes.data))
         return p
 
-    def decision_rule(self):
-        """'nearest' | 'qpsk' | 'bpsk': the rule decode() runs (gfdm_hip_symbol_mapper_decision)"""
-        code = lib().gfdm_hip_symbol_mapper_decision(self._h)
-        return {v: k for k, v in DECIDE.items() if k != "auto"}[code]
+    def _symbols(self, symbols):
+        symbols, n_rows, n_sym, flat = ops.rows(symbols, C64, "symbols", self._dev)
+        _check(lib().gfdm_hip_symbol_mapper_check(1 << self._k, n_sym, n_rows))
+        return symbols, n_rows, n_sym, flat
 
-    def row_bytes(self, n_sym):
-        """bytes of a packed row of n_sym symbols: ceil(n_sym * k / 8)"""
-        n = lib().gfdm_hip_symbol_mapper_row_bytes(self._h, int(n_sym))
-        if n < 0:
-            _check(n)
-        return n
-
-    def _rows(self, x, dtype, what, width=None):
-        """x as rows of `dtype` -> (x, n_rows, width, was 1-D); nothing touches the device"""
-        name = np.dtype(dtype).name
-        if _is_tensor(x):
-            if str(x.dtype).replace("torch.", "") != name or not x.is_cuda or not x.is_contiguous():
-                raise TypeError("%s must be a contiguous %s CUDA/HIP tensor" % (what, name))
-            if x.device.index != self._dev:
-                raise RuntimeError("%s lives on GPU %d, the handle on GPU %d" % (what, x.device.index, self._dev))
-        else:
-            x = np.asarray(x)
-            if dtype == np.uint8 and x.dtype != np.uint8:
-                raise TypeError("%s must be uint8 (packed bytes), not %s" % (what, x.dtype))
-            if dtype == np.complex64 and not (np.issubdtype(x.dtype, np.floating) or np.issubdtype(x.dtype, np.complexfloating)):
-                raise TypeError("%s must be complex symbols, not %s" % (what, x.dtype))
-            x = np.ascontiguousarray(x, dtype=dtype)
-        if x.ndim not in (1, 2):
-            raise ValueError("%s must be (n_rows, n) or one row (n,), not %s" % (what, tuple(x.shape)))
-        flat = x.ndim == 1
-        n_rows, w = (1, x.shape[0]) if flat else (x.shape[0], x.shape[1])
-        if width is not None and w != width:
-            raise RuntimeError("%s has rows of %d elements, expected %d" % (what, w, width))
-        return x, int(n_rows), int(w), flat
-
-    def _result(self, out, like, shape, dtype, flat):
-        name = np.dtype(dtype).name
-        shape = shape[1:] if flat else shape
-        if out is None:
-            if _is_tensor(like):
-                import torch
-                return torch.empty(shape, dtype=getattr(torch, name), device=like.device)
-            return np.empty(shape, dtype)
-        if _is_tensor(out) != _is_tensor(like) or (not _is_tensor(out) and not isinstance(out, np.ndarray)):
-            raise TypeError("out must be a %s, as the input is" % ("CUDA/HIP tensor" if _is_tensor(like) else "numpy array"))
-        if str(out.dtype).replace("torch.", "") != name or not (out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous):
-            raise TypeError("out must be contiguous %s" % name)
-        if _is_tensor(out) and (not out.is_cuda or out.device.index != self._dev):
-            raise RuntimeError("out must live on GPU %d, as the handle does" % self._dev)
-        if int(np.prod(out.shape)) != int(np.prod(shape)):
-            raise RuntimeError("out holds %d elements, expected %d" % (int(np.prod(out.shape)), int(np.prod(shape))))
-        return out
-
-    def _count(self, count, like, keep):
-        """pointer of the optional count (None: every row)"""
-        if count is None:
-            return None
-        if _is_tensor(like):
-            import torch
-            if not _is_tensor(count):
-                count = torch.full((1,), int(count), dtype=torch.int64, device=like.device)
-            keep.append(count)
-            return _dev_arg(count, torch.int64, 1, "count", self._dev)
-        if _is_tensor(count):
-            raise TypeError("count must be an int on the host path")
-        keep.append(np.array([int(count)], np.int64))
-        return keep[-1].ctypes.data
-
-    @staticmethod
-    def _ptr(a):
-        return a.data_ptr() if _is_tensor(a) else a.ctypes.data
-
-    def _run(self, name, res, x, extra, count, n_sym, n_rows, stream):
-        keep = []
-        cptr = self._count(count, x, keep)
-        L = lib()
-        _check(L.gfdm_hip_symbol_mapper_check(1 << self._k, n_sym, n_rows))
-        if _is_tensor(x):
-            _check(getattr(L, name + "_device")(self._h, self._ptr(res), self._ptr(x), *extra, cptr, n_sym, n_rows, self._sp(stream)))
-        else:
-            _check(getattr(L, name + "_host")(self._h, self._ptr(res), self._ptr(x), *extra, cptr, n_sym, n_rows))
+    def _call(self, name, x, extra, width, dtype, flat, count, out, n_sym, n_rows, stream):
+        res = ops.result(x, (width,) if flat else (n_rows, width), dtype, self._dev, out, off_device=RuntimeError)
+        cnt = ops.count_arg(count, x, self._dev)
+        _check(lib().gfdm_hip_symbol_mapper_check(1 << self._k, n_sym, n_rows))
+        self._run("gfdm_hip_symbol_mapper_" + name, x, (ops.ptr(res), ops.ptr(x), *extra, ops.ptr(cnt), n_sym, n_rows), stream)
         return res
 
     def map(self, data, n_sym, count=None, out=None, stream=None):
         """packed bytes (n_rows, row_bytes(n_sym)) uint8 -> symbols (n_rows, n_sym) complex64: points[index], a bit copy"""
         n_sym = int(n_sym)
-        data, n_rows, _, flat = self._rows(data, np.uint8, "data", self.row_bytes(n_sym))
-        res = self._result(out, data, (n_rows, n_sym), np.complex64, flat)
-        return self._run("gfdm_hip_symbol_mapper_map", res, data, (), count, n_sym, n_rows, stream)
+        data, n_rows, _, flat = ops.rows(data, U8, "data", self._dev, self.row_bytes(n_sym))
+        return self._call("map", data, (), n_sym, C64, flat, count, out, n_sym, n_rows, stream)
 
     def decode(self, symbols, count=None, out=None, stream=None):
         """symbols (n_rows, n_sym) complex64 -> packed bytes (n_rows, row_bytes(n_sym)) uint8, by the rule of decision_rule()"""
-        symbols, n_rows, n_sym, flat = self._rows(symbols, np.complex64, "symbols")
-        _check(lib().gfdm_hip_symbol_mapper_check(1 << self._k, n_sym, n_rows))
-        res = self._result(out, symbols, (n_rows, self.row_bytes(n_sym)), np.uint8, flat)
-        return self._run("gfdm_hip_symbol_mapper_decode", res, symbols, (), count, n_sym, n_rows, stream)
+        symbols, n_rows, n_sym, flat = self._symbols(symbols)
+        return self._call("decode", symbols, (), self.row_bytes(n_sym), U8, flat, count, out, n_sym, n_rows, stream)
 
     def soft(self, symbols, scale=None, count=None, out=None, stream=None):
         """symbols (n_rows, n_sym) complex64 -> max-log LLRs (n_rows, n_sym * k) float32, positive for bit 0; scale: float32 (n_rows,), one
         factor per row (typically 1 / sigma^2), a device tensor when symbols is one"""
-        symbols, n_rows, n_sym, flat = self._rows(symbols, np.complex64, "symbols")
-        _check(lib().gfdm_hip_symbol_mapper_check(1 << self._k, n_sym, n_rows))
-        sptr = None
-        if scale is not None:
-            if _is_tensor(symbols):
-                import torch
-                if not _is_tensor(scale):
-                    raise TypeError("scale must be a float32 CUDA/HIP tensor, as symbols is a tensor")
-                sptr = _dev_arg(scale, torch.float32, n_rows, "scale", self._dev)
-            else:
-                if _is_tensor(scale):
-                    raise TypeError("scale must be a host array, as symbols is one")
-                scale = np.ascontiguousarray(scale, dtype=np.float32).ravel()
-                if scale.size != n_rows:
-                    raise RuntimeError("scale has %d elements, expected %d" % (scale.size, n_rows))
-                sptr = scale.ctypes.data
-        res = self._result(out, symbols, (n_rows, n_sym * self._k), np.float32, flat)
-        return self._run("gfdm_hip_symbol_mapper_soft", res, symbols, (sptr,), count, n_sym, n_rows, stream)
+        symbols, n_rows, n_sym, flat = self._symbols(symbols)
+        sc = None if scale is None else ops.vector(scale, F32, "scale", self._dev, symbols, n_rows, "symbols")
+        return self._call("soft", symbols, (ops.ptr(sc),), n_sym * self._k, F32, flat, count, out, n_sym, n_rows, stream)
 
 
 def awgn_noise_voltage(signal, snr_db, rate=1.0):
     """ChannelModel's noise_voltage for `snr_db` on `signal`: sqrt(2 * v), v pygfdm's calculate_awgn_noise_variance (python/pygfdm/utils.py:
     106-110, the variance PER COMPONENT: average sample energy / (2 * rate * 10^(snr_db / 10))) -- the noise power of the channel model is
     noise_voltage^2 = 2 v.  `signal` is a numpy array or a torch tensor; the energy of a tensor is summed on its device."""
-    if _is_tensor(signal):
+    if ops.is_tensor(signal):
         flat = signal.reshape(-1)
         energy, n = float((flat.real.double() ** 2 + flat.imag.double() ** 2).sum().item()) if flat.is_complex() else float((flat.double() ** 2).sum().item()), flat.numel()
     else:
@@ -1840,9 +1148,6 @@ class ChannelModel(_Kernel):
     def set_seed(self, noise_seed):
         _check(lib().gfdm_hip_channel_model_set_seed(self._h, int(noise_seed) & 0xFFFFFFFFFFFFFFFF))
 
-    _kinds = staticmethod(BurstShaper._kinds)
-    _out = BurstShaper._out
-
     def apply(self, x, history=0, offset=0, sc16=False, gain=1.0, out=None, stream=None):
         """x holds history + n samples, the result has n: sample i of the result is the channel's output for x[history + i], whose absolute
         index is offset + i; the first `history` samples are the FIR's past (GNU Radio's history; what lies before them is zeros).  A stream
@@ -1851,30 +1156,20 @@ class ChannelModel(_Kernel):
         given).  sc16=True writes int16 I/Q of shape (n, 2), truncated and saturated, of y * gain."""
         if not sc16 and float(gain) != 1.0:
             raise ValueError("gain scales sc16 output: pass sc16=True (complex64 output is not scaled)")
-        x = self._kinds(x, out, sc16, "x")
+        x = ops.operand(x, C64, "x", self._dev, floating=True)
+        ops.check_result(out, x, I16 if sc16 else C64, self._dev, as_what="x")
         history, offset = int(history), int(offset)
-        size = x.numel() if _is_tensor(x) else x.size
+        size = ops.size(x)
         if history < 0 or history > size:
             raise ValueError("history(%d) must lie in 0 .. the size of x(%d)" % (history, size))
         n = size - history
-        res, optr = self._out(out, n, sc16, x)
-        L = lib()
-        if _is_tensor(x):
-            xptr = self._dp(x, size, "x") + 8 * history
-            if sc16:
-                _check(L.gfdm_hip_channel_model_apply_sc16_device(self._h, optr, xptr, n, history, offset, float(gain), self._sp(stream)))
-            else:
-                _check(L.gfdm_hip_channel_model_apply_device(self._h, optr, xptr, n, history, offset, self._sp(stream)))
-            return res
-        xptr = x.ctypes.data + 8 * history
-        if sc16:
-            _check(L.gfdm_hip_channel_model_apply_sc16_host(self._h, optr, xptr, n, history, offset, float(gain)))
-        else:
-            _check(L.gfdm_hip_channel_model_apply_host(self._h, optr, xptr, n, history, offset))
+        res = ops.stream_result(x, n, sc16, self._dev, out, "x")
+        self._run("gfdm_hip_channel_model_apply" + ("_sc16" if sc16 else ""), x,
+                  (ops.ptr(res), ops.ptr(x) + 8 * history, n, history, offset) + ((float(gain),) if sc16 else ()), stream)
         return res
 
 
-class LinkMeter(_Kernel):
+class LinkMeter(_Rows):
     """Closing the loop on the device (contract in include/gfdm_hip.h, gfdm_hip_link_meter): match() pairs BurstSync.detect's detections
     with the bursts that were sent, measure() counts bit / symbol / row errors of demodulated rows against the sent payload with the
     decisions SymbolMapper.decode makes and gives every row's error-vector power (data-aided: the EVM; without a payload: the
@@ -1884,93 +1179,25 @@ class LinkMeter(_Kernel):
     one-element int64 tensor.  out: a dict with any of the result's keys, to write into existing arrays; workspace: a uint8 device
     tensor of match_workspace_bytes() / measure_workspace_bytes() to use instead of a new one."""
     _destroy = "gfdm_hip_link_meter_destroy"
+    _kind = "gfdm_hip_link_meter"
     FIELDS = ("rows", "symbols", "bits", "bit_errors", "symbol_errors", "row_errors", "detections", "matched", "missed", "false_alarms")
-
-    def __init__(self, points, decision=DECIDE_AUTO, device=0):
-        pts = _c64(np.asarray(points).ravel())
-        h = ctypes.c_void_p()
-        _check(lib().gfdm_hip_link_meter_create(ctypes.byref(h), pts.ctypes.data, pts.size, DECIDE.get(decision, decision), device))
-        self._h = h
-        self._dev = int(device)
-        self._k = lib().gfdm_hip_link_meter_bits_per_symbol(h)
-
-    def bits_per_symbol(self):
-        return self._k
-
-    def decision_rule(self):
-        """'nearest' | 'qpsk' | 'bpsk': the rule measure() decides by (SymbolMapper.decode's for the same points)"""
-        code = lib().gfdm_hip_link_meter_decision(self._h)
-        return {v: k for k, v in DECIDE.items() if k != "auto"}[code]
-
-    def row_bytes(self, n_sym):
-        n = lib().gfdm_hip_link_meter_row_bytes(self._h, int(n_sym))
-        if n < 0:
-            _check(n)
-        return n
 
     @staticmethod
     def match_workspace_bytes(n_sent):
-        n = lib().gfdm_hip_link_meter_match_workspace_bytes(int(n_sent))
-        if n < 0:
-            _check(n)
-        return n
+        return _bytes(lib().gfdm_hip_link_meter_match_workspace_bytes(int(n_sent)))
 
     @staticmethod
     def measure_workspace_bytes(n_sym, n_rows):
-        n = lib().gfdm_hip_link_meter_measure_workspace_bytes(int(n_sym), int(n_rows))
-        if n < 0:
-            _check(n)
-        return n
-
-    _rows = SymbolMapper._rows
-    _count = SymbolMapper._count
-    _ptr = staticmethod(SymbolMapper._ptr)
-
-    def _vector(self, x, dtype, n, what, like):
-        """an input of n elements of `dtype`, of `like`'s kind (device tensor or host array)"""
-        name = np.dtype(dtype).name
-        if _is_tensor(like):
-            import torch
-            if not _is_tensor(x):
-                raise TypeError("%s must be a torch.%s CUDA/HIP tensor, as the other arrays are" % (what, name))
-            _dev_arg(x, getattr(torch, name), n, what, self._dev)
-            return x
-        if _is_tensor(x):
-            raise TypeError("%s must be a host array, as the other arrays are" % what)
-        x = np.ascontiguousarray(x, dtype=dtype).ravel()
-        if x.size != n:
-            raise RuntimeError("%s has %d elements, expected %d" % (what, x.size, n))
-        return x
+        return _bytes(lib().gfdm_hip_link_meter_measure_workspace_bytes(int(n_sym), int(n_rows)))
 
     def _result(self, out, key, like, n, dtype):
         """the output `key` of n elements: out[key] where given, else a new array of `like`'s kind"""
-        name = np.dtype(dtype).name
-        res = None if out is None else out.get(key)
-        if res is None:
-            if _is_tensor(like):
-                import torch
-                return torch.empty((n,), dtype=getattr(torch, name), device=like.device)
-            return np.empty((n,), dtype)
-        if _is_tensor(res) != _is_tensor(like) or (not _is_tensor(res) and not isinstance(res, np.ndarray)):
-            raise TypeError("out[%r] must be a %s, as the input is" % (key, "CUDA/HIP tensor" if _is_tensor(like) else "numpy array"))
-        if str(res.dtype).replace("torch.", "") != name or not (res.is_contiguous() if _is_tensor(res) else res.flags.c_contiguous):
-            raise TypeError("out[%r] must be contiguous %s" % (key, name))
-        if _is_tensor(res) and (not res.is_cuda or res.device.index != self._dev):
-            raise RuntimeError("out[%r] must live on GPU %d, as the handle does" % (key, self._dev))
-        if int(np.prod(res.shape)) != n:
-            raise RuntimeError("out[%r] holds %d elements, expected %d" % (key, int(np.prod(res.shape)), n))
-        return res
+        return ops.result(like, (n,), dtype, self._dev, None if out is None else out.get(key), "out[%r]" % key, off_device=RuntimeError)
 
-    def _workspace(self, ws, like, need):
-        import torch
-        if ws is None:
-            return torch.empty(need, dtype=torch.uint8, device=like.device)
-        if not _is_tensor(ws) or ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < need or ws.device.index != self._dev:
-            raise TypeError("workspace must be a contiguous uint8 CUDA/HIP tensor of at least %d bytes on GPU %d" % (need, self._dev))
-        return ws
-
-    def _settle(self):
+    def _settle(self, lead):
         """the host flavours run on the handle's own stream: what torch's current stream still holds for this handle (a reset) goes first"""
+        if ops.on_device(lead):
+            return
         try:
             import torch
         except ImportError:
@@ -2005,25 +1232,16 @@ class LinkMeter(_Kernel):
     def match(self, frame_start, sent_pos, tol, offset=0, count=None, out=None, stream=None, workspace=None):
         """{"ref_row": int64 (n_rows,), "sent_row": int64 (n_sent,)}: ref_row[d] is the sent burst detection d is (or -1), sent_row[j] the
         detection that is sent burst j (or -1); sent_pos ascending, a detection matches within |frame_start - (sent_pos + offset)| <= tol"""
-        if not _is_tensor(frame_start):
-            frame_start = np.ascontiguousarray(frame_start, dtype=np.int64).ravel()
-        n_rows = int(frame_start.numel() if _is_tensor(frame_start) else frame_start.size)
-        frame_start = self._vector(frame_start, np.int64, n_rows, "frame_start", frame_start)
-        n_sent = int(sent_pos.numel() if _is_tensor(sent_pos) else np.asarray(sent_pos).size)
-        sent_pos = self._vector(sent_pos, np.int64, n_sent, "sent_pos", frame_start)
+        fs = ops.vector(frame_start, I64, "frame_start", self._dev, None)
+        sent = ops.vector(sent_pos, I64, "sent_pos", self._dev, fs, as_what="frame_start")
+        n_rows, n_sent = ops.size(fs), ops.size(sent)
         tol, offset = int(tol), int(offset)
-        res = {"ref_row": self._result(out, "ref_row", frame_start, n_rows, np.int64), "sent_row": self._result(out, "sent_row", frame_start, n_sent, np.int64)}
-        keep = []
-        cptr = self._count(count, frame_start, keep)
-        L = lib()
-        if _is_tensor(frame_start):
-            ws = self._workspace(workspace, frame_start, self.match_workspace_bytes(n_sent))
-            _check(L.gfdm_hip_link_meter_match_device(self._h, self._ptr(res["ref_row"]), self._ptr(res["sent_row"]), self._ptr(frame_start), cptr, n_rows,
-                                                      self._ptr(sent_pos), n_sent, offset, tol, ws.data_ptr(), self._sp(stream)))
-        else:
-            self._settle()
-            _check(L.gfdm_hip_link_meter_match_host(self._h, self._ptr(res["ref_row"]), self._ptr(res["sent_row"]), self._ptr(frame_start), cptr, n_rows,
-                                                    self._ptr(sent_pos), n_sent, offset, tol))
+        res = {"ref_row": self._result(out, "ref_row", fs, n_rows, I64), "sent_row": self._result(out, "sent_row", fs, n_sent, I64)}
+        cnt = ops.count_arg(count, fs, self._dev)
+        self._settle(fs)
+        self._run("gfdm_hip_link_meter_match", fs, (ops.ptr(res["ref_row"]), ops.ptr(res["sent_row"]), ops.ptr(fs), ops.ptr(cnt), n_rows, ops.ptr(sent),
+                                                    n_sent, offset, tol), stream,
+                  scratch=lambda: ops.workspace(workspace, fs, self.match_workspace_bytes(n_sent), self._dev))
         return res
 
     def measure(self, symbols, payload=None, ref_row=None, count=None, out=None, stream=None, workspace=None):
@@ -2031,34 +1249,25 @@ class LinkMeter(_Kernel):
         "ref_power": float32}, each (n_rows,); row r is compared with payload row ref_row[r] (None: r), a row whose ref_row is negative or
         beyond the payload gives -1 / 0 / 0 and is not read.  payload None: decision-directed, err_power against the decided points, no
         bit_errors."""
-        symbols, n_rows, n_sym, _ = self._rows(symbols, np.complex64, "symbols")
+        symbols, n_rows, n_sym, _ = ops.rows(symbols, C64, "symbols", self._dev)
         n_ref = 0
         if payload is not None:
-            if _is_tensor(payload) != _is_tensor(symbols):
-                raise TypeError("payload must be a %s, as symbols is" % ("CUDA/HIP tensor" if _is_tensor(symbols) else "numpy array"))
-            payload, n_ref, _, _ = self._rows(payload, np.uint8, "payload", self.row_bytes(n_sym))
+            payload, n_ref, _, _ = ops.rows(payload, U8, "payload", self._dev, self.row_bytes(n_sym), symbols, "symbols")
         if ref_row is not None:
-            ref_row = self._vector(ref_row, np.int64, n_rows, "ref_row", symbols)
+            ref_row = ops.vector(ref_row, I64, "ref_row", self._dev, symbols, n_rows, "symbols")
         res = {}
         if payload is not None:
-            res["bit_errors"] = self._result(out, "bit_errors", symbols, n_rows, np.int32)
+            res["bit_errors"] = self._result(out, "bit_errors", symbols, n_rows, I32)
         elif out is not None and out.get("bit_errors") is not None:
             raise ValueError("bit_errors needs a payload: a decision-directed call counts no errors")
-        res["err_power"] = self._result(out, "err_power", symbols, n_rows, np.float32)
-        res["ref_power"] = self._result(out, "ref_power", symbols, n_rows, np.float32)
-        keep = []
-        cptr = self._count(count, symbols, keep)
-        ptr = lambda a: None if a is None else self._ptr(a)
-        L = lib()
-        if _is_tensor(symbols):
-            if payload is not None and n_ref == 0:                           # an empty tensor has no pointer, and NULL would mean decision-directed
-                import torch
-                payload = torch.empty(16, dtype=torch.uint8, device=symbols.device)
-            ws = self._workspace(workspace, symbols, self.measure_workspace_bytes(n_sym, n_rows))
-            _check(L.gfdm_hip_link_meter_measure_device(self._h, ptr(res.get("bit_errors")), ptr(res["err_power"]), ptr(res["ref_power"]), self._ptr(symbols),
-                                                        ptr(payload), n_ref, ptr(ref_row), cptr, n_sym, n_rows, ws.data_ptr(), self._sp(stream)))
-        else:
-            self._settle()
-            _check(L.gfdm_hip_link_meter_measure_host(self._h, ptr(res.get("bit_errors")), ptr(res["err_power"]), ptr(res["ref_power"]), self._ptr(symbols),
-                                                      ptr(payload), n_ref, ptr(ref_row), cptr, n_sym, n_rows))
+        res["err_power"] = self._result(out, "err_power", symbols, n_rows, F32)
+        res["ref_power"] = self._result(out, "ref_power", symbols, n_rows, F32)
+        cnt = ops.count_arg(count, symbols, self._dev)
+        if ops.on_device(symbols) and payload is not None and n_ref == 0:          # an empty tensor has no pointer, and NULL would mean decision-directed
+            import torch
+            payload = torch.empty(16, dtype=torch.uint8, device=symbols.device)
+        self._settle(symbols)
+        self._run("gfdm_hip_link_meter_measure", symbols, (ops.ptr(res.get("bit_errors")), ops.ptr(res["err_power"]), ops.ptr(res["ref_power"]),
+                                                           ops.ptr(symbols), ops.ptr(payload), n_ref, ops.ptr(ref_row), ops.ptr(cnt), n_sym, n_rows), stream,
+                  scratch=lambda: ops.workspace(workspace, symbols, self.measure_workspace_bytes(n_sym, n_rows), self._dev))
         return res

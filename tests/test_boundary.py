@@ -19,6 +19,62 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(gfdm_hip_[a-z_0-9]+)\s*\(", text)))
 
 
+C_CLASS = {"int": "i32", "unsigned": "i32", "int64_t": "i64", "uint64_t": "i64", "size_t": "i64", "float": "f32", "double": "f64", "void": "void"}
+CTYPES_CLASS = {None: "void", ctypes.c_void_p: "ptr", ctypes.c_char_p: "ptr", ctypes.c_int: "i32", ctypes.c_uint: "i32", ctypes.c_int64: "i64",
+                ctypes.c_uint64: "i64", ctypes.c_size_t: "i64", ctypes.c_float: "f32", ctypes.c_double: "f64"}
+
+
+def c_class(decl, named):
+    """class of a C parameter or return type: 'ptr' for any pointer, else by its base type (qualifiers and, with `named`, the parameter's name dropped)"""
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w not in ("const", "signed")]
+    if named and len(words) > 1:
+        words = words[:-1]
+    assert len(words) == 1 or words == ["unsigned", "int"], decl
+    return C_CLASS[words[0]]
+
+
+def ctypes_class(t):
+    if t in CTYPES_CLASS:
+        return CTYPES_CLASS[t]
+    assert issubclass(t, ctypes._Pointer), t
+    return "ptr"
+
+
+def declared_prototypes():
+    """{name: (class of the return type, [class of every parameter])} of include/gfdm_hip.h"""
+    text = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M).replace('extern "C"', " ")
+    protos = {}
+    for stmt in re.split(r"[;{}]", text):
+        m = re.fullmatch(r"\s*([\w\s\*]+?)\b(gfdm_hip_\w+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        if not m:
+            continue
+        ret, name, params = m.groups()
+        params = [] if params.strip() == "void" else [c_class(p, True) for p in params.split(",")]
+        assert name not in protos, name
+        protos[name] = (c_class(ret, False), params)
+    return protos
+
+
+def test_ctypes_signatures_match_the_header():
+    """every binding takes the header's number of parameters, each of the header's class (pointer, 32-bit integer, 64-bit integer, float,
+    double), and returns the header's class: ctypes converts silently, so a wrong width or arity would show only as a wrong result"""
+    import gfdm_amd
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_functions()
+    L = gfdm_amd.lib()
+    bad = []
+    for name, (ret, params) in sorted(protos.items()):
+        fn = getattr(L, name)
+        have = (ctypes_class(fn.restype), [ctypes_class(a) for a in fn.argtypes])
+        if have != (ret, params):
+            bad.append("%s: header %s%s, binding %s%s" % (name, ret, params, have[0], have[1]))
+    assert not bad, "\n".join(bad)
+
+
 def test_library_exports_every_declared_symbol():
     import gfdm_amd
     lib = ctypes.CDLL(gfdm_amd.capi.LIB_PATH)

@@ -79,6 +79,26 @@ def test_estimator_stages_against_oracle(M, K, A, dc_free):
         assert rel_err(fused[:, written], ref_i[:, written]) < TOL
 
 
+def test_stage_calls_host_flavour_equals_device_flavour():
+    """every stand-alone stage on device tensors gives the host flavour's result bit for bit (the same kernel on either path), in the
+    host flavour's shape: two preambles of the file's smallest shape"""
+    import torch
+    import gfdm_amd
+    M, K, A, dc_free = 7, 12, 8, True
+    rng = np.random.default_rng(3)
+    pre = (rng.standard_normal(2 * K) + 1j * rng.standard_normal(2 * K)) / np.sqrt(2)
+    rx = (rng.standard_normal((2, 2 * K)) + 1j * rng.standard_normal((2, 2 * K))).astype(np.complex64)
+    est = gfdm_amd.ChannelEstimator(M, K, A, dc_free, 0, pre)
+    x = rx
+    for stage in (est.estimate_preamble_channel, est.filter_preamble_estimate, est.interpolate_frame, est.prepare_for_zf):
+        host = stage(x)
+        dev = stage(torch.tensor(x, device="cuda:0"))
+        torch.cuda.synchronize()
+        assert host.dtype == np.complex64 and host.shape == tuple(dev.shape) and host.shape[0] == 2
+        assert np.array_equal(host.view(np.uint8), dev.cpu().numpy().view(np.uint8)), stage.__name__
+        x = host
+
+
 def test_estimate_frame_families_agree():
     """row-lane estimate_frame == generic estimate_frame (same device functions, different FFT) on a big ragged batch."""
     import gfdm_amd

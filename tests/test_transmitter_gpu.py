@@ -29,6 +29,20 @@ def _tx_from_golden(g, cls):
                g["shifts"], list(g["preambles"]))
 
 
+def test_generic_work_host_flavour_equals_device_flavour():
+    """generic_work (the frame of the first cyclic shift) on a device tensor: the host flavour's frames bit for bit, two blocks"""
+    import torch
+    import gfdm_amd
+    g = load_tx_golden("tx_k32_m5_short")
+    tx = _tx_from_golden(g, gfdm_amd.Transmitter)
+    sym = g["symbols"][:2].astype(np.complex64)
+    host = tx.generic_work(sym, sym.shape[1])
+    dev = tx.generic_work(torch.tensor(sym, device="cuda:0"), sym.shape[1])
+    torch.cuda.synchronize()
+    assert host.shape == tuple(dev.shape) == (2, tx.output_vector_size())
+    assert np.array_equal(host.view(np.uint8), dev.cpu().numpy().view(np.uint8))
+
+
 @pytest.mark.parametrize("name", tx_golden_names())
 def test_transmitter_matches_pygfdm_frames(name):
     """python/qa_transmitter_cc.py:80-183 (single port and cyclic-delay diversity, 5 places) on the fused kernel."""
