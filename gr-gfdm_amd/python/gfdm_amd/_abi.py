@@ -166,6 +166,18 @@ def _signatures():
     fn("link_meter_measure_workspace_bytes", i64, i64, i64)
     call("link_meter_match", vp, vp, vp, vp, i64, vp, i64, i64, i64, device=ws_stream)
     call("link_meter_measure", vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, device=ws_stream)
+
+    # ---- convolutional code ----
+    fn("conv_code_create", i32, out(vp), i32, i32, i32, i32)
+    getters("conv_code", "destroy mode")
+    fn("conv_code_poly", i32, vp, i32)
+    for name in ("steps", "coded_bits", "coded_bytes", "info_bytes"):
+        fn("conv_code_" + name, i64, vp, i64)
+    fn("conv_code_decode_workspace_bytes", i64, vp, i64, i64)
+    fn("conv_code_check", i32, i32, i32, i32, i64, i64)
+    call("conv_code_encode", vp, vp, vp, i64, i64, i64)
+    call("conv_code_decode", vp, vp, vp, vp, i64, i64, f32, i64, device=ws_stream)
+    call("conv_code_decode_hard", vp, vp, vp, vp, i64, i64, i64, device=ws_stream)
     return sig
 
 

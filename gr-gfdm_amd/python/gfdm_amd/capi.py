@@ -1271,3 +1271,91 @@ class LinkMeter(_Rows):
                                                            ops.ptr(symbols), ops.ptr(payload), n_ref, ops.ptr(ref_row), ops.ptr(cnt), n_sym, n_rows), stream,
                   scratch=lambda: ops.workspace(workspace, symbols, self.measure_workspace_bytes(n_sym, n_rows), self._dev))
         return res
+
+
+CC_MODES = {"terminated": 0, "truncated": 1}
+CC_TERMINATED, CC_TRUNCATED = "terminated", "truncated"                   # the keys of CC_MODES, as mode() reports them
+
+
+class ConvolutionalCode(_Kernel):
+    """The constraint-length-7, rate-1/2 convolutional code (contract in include/gfdm_hip.h, gfdm_hip_conv_code): encode() in front of
+    SymbolMapper.map, decode() -- a soft-input Viterbi decoder -- behind SymbolMapper.soft, decode_hard() behind SymbolMapper.decode.
+    polys: the two generators, 1 <= |g| <= 127, a negative one complements its output; the default is 171 / 133 octal, GNU Radio's
+    [109, 79] (the code is defined by the header's formulas; parity with GNU Radio's blocks is unpinned).  mode: "terminated" (six zero
+    tail bits, steps = n_info + 6) or "truncated".  Rows are frames or bursts: information bytes (n_rows, info_bytes(n_info)), coded bytes
+    (n_rows, >= coded_bytes(n_info)), LLRs (n_rows, >= coded_bits(n_info)) float32, positive for bit 0; a 1-D input is one row and gives a
+    1-D result.  numpy arrays run the host flavour; torch device tensors the device flavour on the current stream unless given.  count (an
+    int, or on the device path a one-element int64 tensor such as detect's) limits the call to the first count rows, the rest is written
+    as zeros; it is clamped to [0, n_rows].  path_metric: an int32 array / tensor (n_rows,) that receives every row's final metric.
+    workspace: a uint8 device tensor of workspace_bytes() to use instead of a new one (long rows only)."""
+    _destroy = "gfdm_hip_conv_code_destroy"
+
+    def __init__(self, polys=(109, 79), mode=CC_TERMINATED, device=0):
+        g0, g1 = (int(g) for g in polys)
+        h = ctypes.c_void_p()
+        _check(lib().gfdm_hip_conv_code_create(ctypes.byref(h), g0, g1, CC_MODES.get(mode, mode), device))
+        self._h = h
+        self._dev = int(device)
+
+    def polys(self):
+        return tuple(lib().gfdm_hip_conv_code_poly(self._h, i) for i in (0, 1))
+
+    def mode(self):
+        """'terminated' | 'truncated'"""
+        return {v: k for k, v in CC_MODES.items()}[lib().gfdm_hip_conv_code_mode(self._h)]
+
+    def steps(self, n_info):
+        """trellis steps of a row: n_info + 6 (terminated) or n_info"""
+        return _bytes(lib().gfdm_hip_conv_code_steps(self._h, int(n_info)))
+
+    def coded_bits(self, n_info):
+        return _bytes(lib().gfdm_hip_conv_code_coded_bits(self._h, int(n_info)))
+
+    def coded_bytes(self, n_info):
+        return _bytes(lib().gfdm_hip_conv_code_coded_bytes(self._h, int(n_info)))
+
+    def info_bytes(self, n_info):
+        return _bytes(lib().gfdm_hip_conv_code_info_bytes(self._h, int(n_info)))
+
+    def workspace_bytes(self, n_info, n_rows):
+        """bytes of device scratch a device decode of n_rows rows needs: 0 while a row's survivor decisions fit in LDS"""
+        return _bytes(lib().gfdm_hip_conv_code_decode_workspace_bytes(self._h, int(n_info), int(n_rows)))
+
+    def _table(self, n_info, n_rows):
+        g0, g1 = self.polys()
+        _check(lib().gfdm_hip_conv_code_check(g0, g1, lib().gfdm_hip_conv_code_mode(self._h), n_info, n_rows))
+
+    def encode(self, data, n_info, out_row_bytes=None, count=None, out=None, stream=None):
+        """information bytes (n_rows, info_bytes(n_info)) uint8 -> coded bytes (n_rows, out_row_bytes) uint8; out_row_bytes (default
+        coded_bytes(n_info)) may be wider, e.g. SymbolMapper.row_bytes(n_sym): what lies behind the coded bits is written as 0"""
+        n_info = int(n_info)
+        data, n_rows, _, flat = ops.rows(data, U8, "data", self._dev, self.info_bytes(n_info))
+        self._table(n_info, n_rows)
+        width = self.coded_bytes(n_info) if out_row_bytes is None else int(out_row_bytes)
+        res = ops.result(data, (width,) if flat else (n_rows, width), U8, self._dev, out, off_device=RuntimeError)
+        cnt = ops.count_arg(count, data, self._dev)
+        self._run("gfdm_hip_conv_code_encode", data, (ops.ptr(res), ops.ptr(data), ops.ptr(cnt), n_info, width, n_rows), stream)
+        return res
+
+    def _decode(self, stem, x, dtype, what, n_info, extra, count, out, path_metric, workspace, stream):
+        n_info = int(n_info)
+        x, n_rows, width, flat = ops.rows(x, dtype, what, self._dev)
+        self._table(n_info, n_rows)
+        nb = self.info_bytes(n_info)
+        res = ops.result(x, (nb,) if flat else (n_rows, nb), U8, self._dev, out, as_what=what, off_device=RuntimeError)
+        ops.check_result(path_metric, x, I32, self._dev, "path_metric", what, n_rows, off_device=RuntimeError)
+        cnt = ops.count_arg(count, x, self._dev)
+        need = self.workspace_bytes(n_info, n_rows)
+        self._run(stem, x, (ops.ptr(res), ops.ptr(path_metric), ops.ptr(x), ops.ptr(cnt), n_info, width, *extra, n_rows), stream,
+                  scratch=lambda: ops.workspace(workspace, x, need, self._dev) if need else None)
+        return res
+
+    def decode(self, llr, n_info, gain, count=None, out=None, path_metric=None, workspace=None, stream=None):
+        """LLRs (n_rows, llr_stride >= coded_bits(n_info)) float32 -- SymbolMapper.soft's output as it is -> information bytes
+        (n_rows, info_bytes(n_info)) uint8.  A value enters the trellis as clamp(rint(llr * gain), -127, 127); gain is finite and > 0."""
+        return self._decode("gfdm_hip_conv_code_decode", llr, F32, "llr", n_info, (float(gain),), count, out, path_metric, workspace, stream)
+
+    def decode_hard(self, coded, n_info, count=None, out=None, path_metric=None, workspace=None, stream=None):
+        """coded bytes (n_rows, in_row_bytes >= coded_bytes(n_info)) uint8 -- encode's output, SymbolMapper.decode's bytes -> information
+        bytes (n_rows, info_bytes(n_info)) uint8: the same decoder on +1 / -1"""
+        return self._decode("gfdm_hip_conv_code_decode_hard", coded, U8, "coded", n_info, (), count, out, path_metric, workspace, stream)

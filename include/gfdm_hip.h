@@ -908,6 +908,86 @@ int gfdm_hip_link_meter_measure_device(gfdm_hip_link_meter* m, void* bit_errors,
                                        const void* payload, int64_t n_ref, const void* ref_row, const void* count, int64_t n_sym, int64_t n_rows,
                                        void* workspace, void* stream);
 
+/* ---- gfdm_hip_conv_code: convolutional code, encode and soft- / hard-input Viterbi decode ------------------------------------------
+ * The forward error correction pair of the chain: encode in front of gfdm_hip_symbol_mapper_map, decode behind ..._soft (decode_hard
+ * behind ..._decode).  Constraint length 7, rate 1/2 and nothing else; the default generators are 171 / 133 octal, GNU Radio's
+ * fec.cc_encoder / cc_decoder default polys = [109, 79].  GNU Radio is not part of this project's test bed: the code is DEFINED by the
+ * formulas below, and bit-compatibility with GNU Radio's blocks is unpinned.  All arithmetic is integer, so every result is exact.
+ * Encoder: g0, g1 are the generators, 1 <= |g_i| <= 127; a negative g_i complements that output (Karn's convention).  With u_t the
+ *   input bits, t = 0 .. T-1, u_t = 0 for t < 0 and for the tail:
+ *     R_t = sum_{d=0..6} u_{t-d} << d                    (the newest bit is bit 0)
+ *     c_{t,i} = parity(R_t & |g_i|) XOR (g_i < 0)
+ *   and the coded row is c_{0,0} c_{0,1} c_{1,0} c_{1,1} ...: coded_bits = 2 T.
+ * Modes: GFDM_HIP_CC_TERMINATED: six zero bits follow the n_info information bits, T = steps = n_info + 6, the trellis ends in state 0.
+ *   GFDM_HIP_CC_TRUNCATED: T = n_info, the final state is free.  T <= 2^20.
+ * Packing is the symbol mapper's: MSB first, every row starts on a byte.  An information row is info_bytes = ceil(n_info / 8) bytes; the
+ *   spare low bits of its last byte are ignored by encode and written as 0 by decode.  A coded row is coded_bytes = ceil(2 T / 8) bytes.
+ * encode: bytes [n_rows][info_bytes] -> bytes [n_rows][out_row_bytes], out_row_bytes >= coded_bytes; everything behind the 2 T coded bits
+ *   of a row is written as 0, so a row may have the width gfdm_hip_symbol_mapper_row_bytes(n_sym) and go straight into map.
+ * decode: float32 LLRs [n_rows][llr_stride], llr_stride >= coded_bits (the floats behind the coded bits are never read: soft's
+ *   [n_rows][n_sym k] goes in as it is) -> bytes [n_rows][info_bytes] and, where path_metric is not NULL, int32 [n_rows].
+ *   Soft value of a coded bit: q = clamp(rintf(llr * gain), -127, 127) -- one fp32 product, rintf rounds half to even, NaN gives 0, +-inf
+ *   gives +-127; positive means bit 0 (soft's sign); gain is a finite float > 0.  decode_hard reads a packed coded row
+ *   [n_rows][in_row_bytes], in_row_bytes >= coded_bytes (encode's output, gfdm_hip_symbol_mapper_decode's bytes): q = +1 for a 0 bit, -1
+ *   for a 1 bit.
+ *   Path metrics are int32: PM_{-1}[0] = 0, PM_{-1}[s] = -(1 << 30) for s != 0.  At step t state s has the predecessors
+ *   p_b = (s >> 1) + 32 b, b in {0, 1}, over the register value R = s | (b << 6):
+ *     m_b = PM_{t-1}[p_b] + sum_i (1 - 2 c_i(R)) q_{t,i},     d_t[s] = (m_1 > m_0)  (strict: a tie keeps b = 0),     PM_t[s] = max(m_0, m_1).
+ *   No normalisation: 2^20 * 254 < 2^30 - 2^28 keeps every metric inside int32.
+ *   Traceback: start state s = 0 (terminated) or the first state of maximal PM_{T-1} (truncated); for t = T-1 .. 0: u_t = s & 1, then
+ *   s = (s >> 1) | (d_t[s] << 5).  The output is u_0 .. u_{n_info-1}; path_metric is PM_{T-1} at the start state.  An all-zero row of
+ *   LLRs (erasures) therefore decodes to zero bits with metric 0.
+ * Workspace: the survivor decisions of a row are 8 T bytes.  Rows of at most GFDM_HIP_CC_LDS_STEPS steps keep them in LDS and
+ *   decode_workspace_bytes is 0 (workspace may be NULL); longer rows need decode_workspace_bytes(c, n_info, n_rows) bytes of device
+ *   memory, 16-byte aligned, whose content is not preserved between calls.  It grows with n_rows only up to the 2048 rows a launch
+ *   keeps in flight.
+ * count, *_device, *_host: as for gfdm_hip_symbol_mapper.  Rows from n_live = clamp(*count, 0, n_rows) on are written as zeros
+ *   (path_metric 0) and their input is never read; every output element is written exactly once by the one kernel of the call, with
+ *   no memset in front, so a graph replay with a changed count is correct.  The device flavours neither allocate nor synchronise and
+ *   are hipGraph-capturable.  Buffers need the alignment of one element and no more: 1 byte for bytes, 4 bytes for LLRs and
+ *   path_metric (8 for count); byte offsets are 64-bit.  The host flavours upload, run the device call with a workspace of their own,
+ *   and download: a convenience, not a pipeline.
+ * GFDM_HIP_EINVAL from check (the argument table alone, without a handle or a device) and from every call: a generator of 0 or with
+ *   |g| > 127; an unknown mode; n_info < 1; T > 2^20; n_rows < 0; byte sizes that overflow int64.  From the calls also: a stride or row
+ *   width below the minimum; gain non-finite or <= 0; a NULL buffer the call would touch (the workspace where one is needed).
+ *   n_rows == 0 returns GFDM_HIP_OK without a launch.  The size getters return int64, negative values are status codes; poly returns
+ *   0 for a bad handle or index.
+ * Not here: puncturing (a caller depunctures by writing LLR 0), interleaving, tail-biting and streaming modes, other constraint
+ *   lengths or rates, int8 LLR input.
+ * Tested range (bit for bit, path_metric included, against the numpy restatement of the above in tests/conv_code_ref.py): both modes;
+ *   n_info 1, 2, 5, 6, 7, 8, 57, 58, 59, 122, 456, the last three that keep T <= GFDM_HIP_CC_LDS_STEPS and the two after, one row of
+ *   2^16 + 3; 1, 3, 4, 5, 7, 5000 (n_info 3) and 32768 + 7 (n_info 2) rows per call; polys (109, 79), (109, -79), (91, 121), (55, 79);
+ *   saturating, half-way, NaN, infinite and all-zero LLRs; llr_stride coded_bits + 0, 1, 12; buffers at every alignment of one
+ *   element; count below, at and beyond n_rows. */
+typedef enum gfdm_hip_cc_mode {
+    GFDM_HIP_CC_TERMINATED = 0,
+    GFDM_HIP_CC_TRUNCATED = 1
+} gfdm_hip_cc_mode;
+#define GFDM_HIP_CC_LDS_STEPS 2048 /* rows of up to this many trellis steps keep their decisions in LDS (16 KiB per row) */
+typedef struct gfdm_hip_conv_code gfdm_hip_conv_code;
+int gfdm_hip_conv_code_create(gfdm_hip_conv_code** out, int poly0, int poly1, int mode, int device);
+int gfdm_hip_conv_code_destroy(gfdm_hip_conv_code* c);
+int gfdm_hip_conv_code_poly(const gfdm_hip_conv_code* c, int i);
+int gfdm_hip_conv_code_mode(const gfdm_hip_conv_code* c);
+int64_t gfdm_hip_conv_code_steps(const gfdm_hip_conv_code* c, int64_t n_info);
+int64_t gfdm_hip_conv_code_coded_bits(const gfdm_hip_conv_code* c, int64_t n_info);
+int64_t gfdm_hip_conv_code_coded_bytes(const gfdm_hip_conv_code* c, int64_t n_info);
+int64_t gfdm_hip_conv_code_info_bytes(const gfdm_hip_conv_code* c, int64_t n_info);
+int64_t gfdm_hip_conv_code_decode_workspace_bytes(const gfdm_hip_conv_code* c, int64_t n_info, int64_t n_rows);
+int gfdm_hip_conv_code_check(int poly0, int poly1, int mode, int64_t n_info, int64_t n_rows);
+int gfdm_hip_conv_code_encode_host(gfdm_hip_conv_code* c, uint8_t* out, const uint8_t* data, const int64_t* count, int64_t n_info,
+                                   int64_t out_row_bytes, int64_t n_rows);
+int gfdm_hip_conv_code_encode_device(gfdm_hip_conv_code* c, void* out, const void* data, const void* count, int64_t n_info, int64_t out_row_bytes,
+                                     int64_t n_rows, void* stream);
+int gfdm_hip_conv_code_decode_host(gfdm_hip_conv_code* c, uint8_t* out, int32_t* path_metric, const float* llr, const int64_t* count, int64_t n_info,
+                                   int64_t llr_stride, float gain, int64_t n_rows);
+int gfdm_hip_conv_code_decode_device(gfdm_hip_conv_code* c, void* out, void* path_metric, const void* llr, const void* count, int64_t n_info,
+                                     int64_t llr_stride, float gain, int64_t n_rows, void* workspace, void* stream);
+int gfdm_hip_conv_code_decode_hard_host(gfdm_hip_conv_code* c, uint8_t* out, int32_t* path_metric, const uint8_t* coded, const int64_t* count,
+                                        int64_t n_info, int64_t in_row_bytes, int64_t n_rows);
+int gfdm_hip_conv_code_decode_hard_device(gfdm_hip_conv_code* c, void* out, void* path_metric, const void* coded, const void* count, int64_t n_info,
+                                          int64_t in_row_bytes, int64_t n_rows, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
