@@ -23,7 +23,8 @@
 // phase of sample n is reduced in fp64 (n angle(r) mod 2 pi) and only then rounded to fp32 for sincos, so the rotation error does
 // not grow with n (an fp32 recurrence as in volk's rotator drifts by ~n ulp).
 //
-// The *_host flavours are the device entry points between an upload and a download on the handle's own stream (gfdm_hostcall.h).
+// The *_host flavours are the enqueues of the device entry points inside a staged call (gfdm::HostCall, gfdm_hostcall.h): one allocation,
+// uploads, the enqueue, downloads and one synchronise on the handle's own stream.
 #include "../../include/gfdm_hip.h"
 #include "gfdm_hostcall.h"
 #include "gfdm_dft.h"
@@ -39,7 +40,6 @@
 using gfdm::cf;
 using gfdm::api_fail;
 using gfdm::DeviceGuard;
-using gfdm::DevBuf;
 using gfdm::sample_bytes;
 
 namespace {
@@ -477,8 +477,9 @@ struct gfdm_hip_burst_sync {
     cf* d_preamble = nullptr;          // [2K], normalised to unit average energy
     ~gfdm_hip_burst_sync()
     {
+        if (!d_preamble) return;
         DeviceGuard guard(ctx.device);
-        if (d_preamble) (void)hipFree(d_preamble);
+        (void)hipFree(d_preamble);
     }
 };
 
@@ -557,27 +558,17 @@ int sync_enqueue(gfdm_hip_burst_sync* h, const SyncArgs& a, const SyncOut& o, hi
     return GFDM_HIP_OK;
 }
 
-// ---- host paths: the five outputs of n windows in one device buffer (int64 first: alignment), and back into the caller's arrays ----
-size_t out_bytes(int64_t n) { return (size_t)n * (2 * sizeof(int64_t) + 2 * sizeof(float) + sizeof(cf)); }
-SyncOut carve_out(DevBuf& b, int64_t n)
+// host paths: the five outputs of n windows as pieces of the staged call, in the caller's arrays afterwards
+struct SyncPieces {
+    gfdm::HostCall::Piece<int64_t> frame_start, coarse;
+    gfdm::HostCall::Piece<float> cfo, metric;
+    gfdm::HostCall::Piece<cf> sc_rot;
+    SyncOut dev() const { return SyncOut{ frame_start.dev(), coarse.dev(), cfo.dev(), metric.dev(), sc_rot.dev() }; }
+};
+SyncPieces sync_pieces(gfdm::HostCall& hc, const SyncOut& host, int64_t n)
 {
-    SyncOut o;
-    o.frame_start = b.take<int64_t>(n);
-    o.coarse = b.take<int64_t>(n);
-    o.sc_rot = b.take<cf>(n);
-    o.cfo = b.take<float>(n);
-    o.metric = b.take<float>(n);
-    return o;
-}
-
-int fetch_out(const SyncOut& host, const SyncOut& d, int64_t n, hipStream_t s)
-{
-    GFDM_TRY(gfdm::download(host.frame_start, d.frame_start, (size_t)n * sizeof(int64_t), s));
-    GFDM_TRY(gfdm::download(host.coarse, d.coarse, (size_t)n * sizeof(int64_t), s));
-    GFDM_TRY(gfdm::download(host.sc_rot, d.sc_rot, (size_t)n * sizeof(cf), s));
-    GFDM_TRY(gfdm::download(host.cfo, d.cfo, (size_t)n * sizeof(float), s));
-    GFDM_TRY(gfdm::download(host.metric, d.metric, (size_t)n * sizeof(float), s));
-    return GFDM_HIP_OK;
+    return SyncPieces{ hc.out(host.frame_start, (size_t)n), hc.out(host.coarse, (size_t)n), hc.out(host.cfo, (size_t)n), hc.out(host.metric, (size_t)n),
+                       hc.out(host.sc_rot, (size_t)n) };
 }
 
 int check_at(const gfdm_hip_burst_sync* h, const void* samples, int64_t stream_len, const void* starts, int64_t n)
@@ -692,9 +683,7 @@ int sync_find_frame_start_device(int fmt, gfdm_hip_burst_sync* h, void* frame_st
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     const SyncOut o = sync_out(frame_start, coarse, cfo, metric, sc_rot);
     if (!o.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), o, (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) { return sync_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), o, s); });
 }
 
 // host paths over a window grid: the span the windows cover goes up (the grid starts at its sample 0, origin = first), the results come back
@@ -705,21 +694,12 @@ int sync_find_frame_start_host(int fmt, gfdm_hip_burst_sync* h, int64_t* frame_s
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     const SyncOut host = sync_out(frame_start, coarse, cfo, metric, sc_rot);
     if (!host.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const int64_t n = n_windows;
-    const size_t sb = sample_bytes(fmt), span = (size_t)((n - 1) * stride + h->W) * sb;
-    DevBuf d_in, d_out;
-    GFDM_TRY(d_in.alloc(span));
-    GFDM_TRY(d_out.alloc(out_bytes(n)));
-    GFDM_TRY(gfdm::upload(d_in.p, static_cast<const unsigned char*>(samples) + (size_t)first * sb, span, h->ctx.stream));
-    const SyncOut o = carve_out(d_out, n);
-    rc = sync_enqueue(h, grid_args(h, d_in.p, fmt, 0, stride, n, first), o, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    rc = fetch_out(host, o, n, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    const size_t sb = sample_bytes(fmt);
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(static_cast<const unsigned char*>(samples) + (size_t)first * sb, (size_t)((n - 1) * stride + h->W) * sb);
+    const SyncPieces o = sync_pieces(hc, host, n);
+    return hc.run([&](hipStream_t s) { return sync_enqueue(h, grid_args(h, x.dev(), fmt, 0, stride, n, first), o.dev(), s); });
 }
 
 int sync_auto_correlate_device(int fmt, gfdm_hip_burst_sync* h, void* ac, void* ic, const void* samples, int64_t stream_len, int64_t first,
@@ -728,9 +708,9 @@ int sync_auto_correlate_device(int fmt, gfdm_hip_burst_sync* h, void* ac, void* 
     int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return ac_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), static_cast<cf*>(ac), static_cast<float*>(ic), (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
+        return ac_enqueue(h, grid_args(h, samples, fmt, first, stride, n_windows, 0), static_cast<cf*>(ac), static_cast<float*>(ic), s);
+    });
 }
 
 int sync_auto_correlate_host(int fmt, gfdm_hip_burst_sync* h, float* ac, float* ic, const void* samples, int64_t stream_len, int64_t first,
@@ -739,22 +719,13 @@ int sync_auto_correlate_host(int fmt, gfdm_hip_burst_sync* h, float* ac, float* 
     int rc = check_windows(h, samples, stream_len, first, stride, n_windows);
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     if (!ac && !ic) return api_fail(GFDM_HIP_EINVAL, "NULL output buffers");
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const int64_t n = n_windows;
-    const size_t sb = sample_bytes(fmt), span = (size_t)((n - 1) * stride + h->W) * sb, np = (size_t)n * (h->W - 2 * h->K);
-    DevBuf d_in, d_out;
-    GFDM_TRY(d_in.alloc(span));
-    GFDM_TRY(d_out.alloc(np * (sizeof(cf) + sizeof(float))));
-    GFDM_TRY(gfdm::upload(d_in.p, static_cast<const unsigned char*>(samples) + (size_t)first * sb, span, h->ctx.stream));
-    cf* d_ac = d_out.take<cf>(np);
-    float* d_ic = d_out.take<float>(np);
-    rc = ac_enqueue(h, grid_args(h, d_in.p, fmt, 0, stride, n, first), d_ac, d_ic, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(ac, d_ac, np * sizeof(cf), h->ctx.stream));          // (an output the caller left out is skipped)
-    GFDM_TRY(gfdm::download(ic, d_ic, np * sizeof(float), h->ctx.stream));
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    const size_t sb = sample_bytes(fmt), np = (size_t)n * (h->W - 2 * h->K);
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(static_cast<const unsigned char*>(samples) + (size_t)first * sb, (size_t)((n - 1) * stride + h->W) * sb);
+    const auto d_ac = hc.out(reinterpret_cast<cf*>(ac), np);          // (an output the caller left out is NULL to the kernel, which then skips it)
+    const auto d_ic = hc.out(ic, np);
+    return hc.run([&](hipStream_t s) { return ac_enqueue(h, grid_args(h, x.dev(), fmt, 0, stride, n, first), d_ac.dev(), d_ic.dev(), s); });
 }
 
 /* windows at arbitrary starts: the regular-grid kernels with a start array (bit-equal results per window) */
@@ -765,9 +736,9 @@ int sync_find_frame_start_at_device(int fmt, gfdm_hip_burst_sync* h, void* frame
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     const SyncOut o = sync_out(frame_start, coarse, cfo, metric, sc_rot);
     if (!o.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return sync_enqueue(h, list_args(h, samples, fmt, stream_len, static_cast<const int64_t*>(starts), n_windows, n_windows, 0), o, (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
+        return sync_enqueue(h, list_args(h, samples, fmt, stream_len, static_cast<const int64_t*>(starts), n_windows, n_windows, 0), o, s);
+    });
 }
 
 int sync_find_frame_start_at_host(int fmt, gfdm_hip_burst_sync* h, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
@@ -777,22 +748,12 @@ int sync_find_frame_start_at_host(int fmt, gfdm_hip_burst_sync* h, int64_t* fram
     if (rc != GFDM_HIP_OK || n_windows == 0) return rc;
     const SyncOut host = sync_out(frame_start, coarse, cfo, metric, sc_rot);
     if (!host.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const int64_t n = n_windows;
-    DevBuf d_in, d_st, d_out;
-    GFDM_TRY(d_in.alloc((size_t)stream_len * sample_bytes(fmt)));
-    GFDM_TRY(d_st.alloc((size_t)n * sizeof(int64_t)));
-    GFDM_TRY(d_out.alloc(out_bytes(n)));
-    GFDM_TRY(gfdm::upload(d_in.p, samples, (size_t)stream_len * sample_bytes(fmt), h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_st.p, starts, (size_t)n * sizeof(int64_t), h->ctx.stream));
-    const SyncOut o = carve_out(d_out, n);
-    rc = sync_enqueue(h, list_args(h, d_in.p, fmt, stream_len, d_st.as<const int64_t>(), n, n, 0), o, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    rc = fetch_out(host, o, n, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(static_cast<const unsigned char*>(samples), (size_t)stream_len * sample_bytes(fmt));
+    const auto st = hc.in(starts, (size_t)n);
+    const SyncPieces o = sync_pieces(hc, host, n);
+    return hc.run([&](hipStream_t s) { return sync_enqueue(h, list_args(h, x.dev(), fmt, stream_len, st.dev(), n, n, 0), o.dev(), s); });
 }
 
 int sync_detect_device(int fmt, gfdm_hip_burst_sync* h, void* count, void* frame_start, void* coarse, void* cfo, void* metric, void* sc_rot,
@@ -806,10 +767,9 @@ int sync_detect_device(int fmt, gfdm_hip_burst_sync* h, void* count, void* frame
     const SyncOut o = sync_out(frame_start, coarse, cfo, metric, sc_rot);
     if (max_bursts > 0 && !o.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
     if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return detect_enqueue(h, static_cast<int64_t*>(count), o, samples, fmt, stream_len, threshold, min_distance, lead, max_bursts, workspace,
-                          (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
+        return detect_enqueue(h, static_cast<int64_t*>(count), o, samples, fmt, stream_len, threshold, min_distance, lead, max_bursts, workspace, s);
+    });
 }
 
 int sync_detect_host(int fmt, gfdm_hip_burst_sync* h, int64_t* count, int64_t* frame_start, int64_t* coarse, float* cfo, float* metric, float* sc_rot,
@@ -822,25 +782,15 @@ int sync_detect_host(int fmt, gfdm_hip_burst_sync* h, int64_t* count, int64_t* f
     const SyncOut host = sync_out(frame_start, coarse, cfo, metric, sc_rot);
     if (max_bursts > 0 && !host.complete()) return api_fail(GFDM_HIP_EINVAL, "NULL output buffer");
     if (max_bursts > (int64_t)1 << 31) return api_fail(GFDM_HIP_EINVAL, "max_bursts above 2^31");
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const int64_t n = max_bursts;
-    DevBuf d_in, d_ws, d_out, d_count;
-    GFDM_TRY(d_in.alloc((size_t)stream_len * sample_bytes(fmt)));
-    GFDM_TRY(d_ws.alloc(detect_geom(h, stream_len).bytes));
-    GFDM_TRY(d_out.alloc(out_bytes(n)));
-    GFDM_TRY(d_count.alloc(sizeof(int64_t)));
-    GFDM_TRY(gfdm::upload(d_in.p, samples, (size_t)stream_len * sample_bytes(fmt), h->ctx.stream));
-    const SyncOut o = carve_out(d_out, n);
-    rc = detect_enqueue(h, d_count.as<int64_t>(), o, d_in.p, fmt, stream_len, threshold, min_distance, lead, n, d_ws.p, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(count, d_count.p, sizeof(int64_t), h->ctx.stream));
-    if (n > 0) {
-        rc = fetch_out(host, o, n, h->ctx.stream);
-        if (rc != GFDM_HIP_OK) return rc;
-    }
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(static_cast<const unsigned char*>(samples), (size_t)stream_len * sample_bytes(fmt));
+    const auto ws = hc.scratch<unsigned char>(detect_geom(h, stream_len).bytes);
+    const auto cnt = hc.out(count, 1);
+    const SyncPieces o = sync_pieces(hc, host, n);
+    return hc.run([&](hipStream_t s) {
+        return detect_enqueue(h, cnt.dev(), o.dev(), x.dev(), fmt, stream_len, threshold, min_distance, lead, n, ws.dev(), s);
+    });
 }
 
 int extractor_extract_device(int fmt, gfdm_hip_burst_extractor* h, void* out, const void* samples, int64_t stream_len, const void* offsets,
@@ -848,10 +798,10 @@ int extractor_extract_device(int fmt, gfdm_hip_burst_extractor* h, void* out, co
 {
     int rc = extract_check(h, out, samples, stream_len, offsets, n_bursts);
     if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return extract_enqueue(h, static_cast<cf*>(out), samples, fmt, stream_len, static_cast<const int64_t*>(offsets),
-                           static_cast<const float*>(scale), static_cast<const cf*>(sc_rot), n_bursts, (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
+        return extract_enqueue(h, static_cast<cf*>(out), samples, fmt, stream_len, static_cast<const int64_t*>(offsets), static_cast<const float*>(scale),
+                               static_cast<const cf*>(sc_rot), n_bursts, s);
+    });
 }
 
 int extractor_extract_host(int fmt, gfdm_hip_burst_extractor* h, float* out, const void* samples, int64_t stream_len, const int64_t* offsets,
@@ -859,25 +809,14 @@ int extractor_extract_host(int fmt, gfdm_hip_burst_extractor* h, float* out, con
 {
     int rc = extract_check(h, out, samples, stream_len, offsets, n_bursts);
     if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t n = (size_t)n_bursts, L = (size_t)h->burst_len;
-    DevBuf d_s, d_args, d_out;
-    GFDM_TRY(d_s.alloc((size_t)stream_len * sample_bytes(fmt)));
-    GFDM_TRY(d_args.alloc(n * (sizeof(int64_t) + sizeof(float) + sizeof(cf))));
-    GFDM_TRY(d_out.alloc(n * L * sizeof(cf)));
-    int64_t* d_off = d_args.take<int64_t>(n);
-    cf* d_rot = d_args.take<cf>(n);
-    float* d_scale = d_args.take<float>(n);
-    GFDM_TRY(gfdm::upload(d_s.p, samples, (size_t)stream_len * sample_bytes(fmt), h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_off, offsets, n * sizeof(int64_t), h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_rot, sc_rot, n * sizeof(cf), h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_scale, scale, n * sizeof(float), h->ctx.stream));
-    rc = extract_enqueue(h, d_out.as<cf>(), d_s.p, fmt, stream_len, d_off, scale ? d_scale : nullptr, sc_rot ? d_rot : nullptr, n_bursts, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(out, d_out.p, n * L * sizeof(cf), h->ctx.stream));
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    const size_t n = (size_t)n_bursts;
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(static_cast<const unsigned char*>(samples), (size_t)stream_len * sample_bytes(fmt));
+    const auto off = hc.in(offsets, n);
+    const auto rot = hc.in(reinterpret_cast<const cf*>(sc_rot), n);
+    const auto sc = hc.in(scale, n);
+    const auto y = hc.out(reinterpret_cast<cf*>(out), n * (size_t)h->burst_len);
+    return hc.run([&](hipStream_t s) { return extract_enqueue(h, y.dev(), x.dev(), fmt, stream_len, off.dev(), sc.dev(), rot.dev(), n_bursts, s); });
 }
 
 }  // namespace
@@ -886,46 +825,37 @@ extern "C" {
 
 int gfdm_hip_burst_sync_create(gfdm_hip_burst_sync** out, int fft_len, int cp_len, const float* core_preamble, int n_preamble, int64_t window_len, int device)
 {
-    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
-    *out = nullptr;
     const int K = fft_len;
-    char buf[200];
-    if (K < 2 || K > kMaxK) return api_fail(GFDM_HIP_EINVAL, "fft_len must lie in [2, 1024]");
-    if (!core_preamble || n_preamble != 2 * K) {                                                    // synchronization.py:228-229
-        snprintf(buf, sizeof(buf), "Preamble length(%d) must be equal to 2K(%d)!", n_preamble, 2 * K);
-        return api_fail(GFDM_HIP_EINVAL, buf);
-    }
-    if (cp_len < 0) return api_fail(GFDM_HIP_EINVAL, "cp_len must be >= 0");
-    if (window_len < (int64_t)2 * K + cp_len + 1) {
-        snprintf(buf, sizeof(buf), "window_len(%lld) must be at least 2 fft_len + cp_len + 1 (%d)", (long long)window_len, 2 * K + cp_len + 1);
-        return api_fail(GFDM_HIP_EINVAL, buf);
-    }
-    if (window_len > (int64_t)1 << 30) return api_fail(GFDM_HIP_EINVAL, "window_len above 2^30");
-    // initialize_sync_algorithm (synchronization.py:225-236): unit average energy
-    double e = 0.0;
-    for (int i = 0; i < 4 * K; ++i) e += (double)core_preamble[i] * core_preamble[i];
-    if (!(e > 0.0) || !std::isfinite(e)) return api_fail(GFDM_HIP_EINVAL, "preamble has no energy");
-    const double g = 1.0 / std::sqrt(e / (2 * K));
-    std::vector<float> pre(4 * K);
-    for (int i = 0; i < 4 * K; ++i) pre[i] = (float)(core_preamble[i] * g);
-    gfdm_hip_burst_sync* h = new (std::nothrow) gfdm_hip_burst_sync();
-    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->K = K;
-    h->cp = cp_len;
-    h->W = (int)window_len;
-    int rc = h->ctx.open(device);
-    if (rc == GFDM_HIP_OK) {
-        DeviceGuard guard(device);
-        hipError_t err = hipMalloc(&h->d_preamble, pre.size() * sizeof(float));
-        if (err == hipSuccess) err = hipMemcpy(h->d_preamble, pre.data(), pre.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (err != hipSuccess) rc = gfdm::api_fail_hip(err, "burst_sync_create");
-    }
-    if (rc != GFDM_HIP_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return GFDM_HIP_OK;
+    std::vector<float> pre;
+    return gfdm::create_handle(out, device, [&](gfdm_hip_burst_sync& h) -> int {
+        char buf[200];
+        if (K < 2 || K > kMaxK) return api_fail(GFDM_HIP_EINVAL, "fft_len must lie in [2, 1024]");
+        if (!core_preamble || n_preamble != 2 * K) {                                                    // synchronization.py:228-229
+            snprintf(buf, sizeof(buf), "Preamble length(%d) must be equal to 2K(%d)!", n_preamble, 2 * K);
+            return api_fail(GFDM_HIP_EINVAL, buf);
+        }
+        if (cp_len < 0) return api_fail(GFDM_HIP_EINVAL, "cp_len must be >= 0");
+        if (window_len < (int64_t)2 * K + cp_len + 1) {
+            snprintf(buf, sizeof(buf), "window_len(%lld) must be at least 2 fft_len + cp_len + 1 (%d)", (long long)window_len, 2 * K + cp_len + 1);
+            return api_fail(GFDM_HIP_EINVAL, buf);
+        }
+        if (window_len > (int64_t)1 << 30) return api_fail(GFDM_HIP_EINVAL, "window_len above 2^30");
+        // initialize_sync_algorithm (synchronization.py:225-236): unit average energy
+        double e = 0.0;
+        for (int i = 0; i < 4 * K; ++i) e += (double)core_preamble[i] * core_preamble[i];
+        if (!(e > 0.0) || !std::isfinite(e)) return api_fail(GFDM_HIP_EINVAL, "preamble has no energy");
+        const double g = 1.0 / std::sqrt(e / (2 * K));
+        pre.resize(4 * K);
+        for (int i = 0; i < 4 * K; ++i) pre[i] = (float)(core_preamble[i] * g);
+        h.K = K;
+        h.cp = cp_len;
+        h.W = (int)window_len;
+        return GFDM_HIP_OK;
+    }, [&](gfdm_hip_burst_sync& h) {
+        hipError_t err = hipMalloc(&h.d_preamble, pre.size() * sizeof(float));
+        if (err == hipSuccess) err = hipMemcpy(h.d_preamble, pre.data(), pre.size() * sizeof(float), hipMemcpyHostToDevice);
+        return err == hipSuccess ? GFDM_HIP_OK : gfdm::api_fail_hip(err, "burst_sync_create");
+    });
 }
 
 int gfdm_hip_burst_sync_destroy(gfdm_hip_burst_sync* h) { delete h; return GFDM_HIP_OK; }
@@ -950,21 +880,13 @@ int64_t gfdm_hip_burst_sync_detect_workspace_bytes(const gfdm_hip_burst_sync* h,
 
 int gfdm_hip_burst_extractor_create(gfdm_hip_burst_extractor** out, int burst_len, int tag_backoff, int activate_cfo_correction, int device)
 {
-    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
-    *out = nullptr;
-    if (burst_len < 1) return api_fail(GFDM_HIP_EINVAL, "burst_len must be >= 1");
-    gfdm_hip_burst_extractor* h = new (std::nothrow) gfdm_hip_burst_extractor();
-    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->burst_len = burst_len;
-    h->backoff = tag_backoff;
-    h->correct = activate_cfo_correction ? 1 : 0;
-    const int rc = h->ctx.open(device);
-    if (rc != GFDM_HIP_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return GFDM_HIP_OK;
+    return gfdm::create_handle(out, device, [&](gfdm_hip_burst_extractor& h) -> int {
+        if (burst_len < 1) return api_fail(GFDM_HIP_EINVAL, "burst_len must be >= 1");
+        h.burst_len = burst_len;
+        h.backoff = tag_backoff;
+        h.correct = activate_cfo_correction ? 1 : 0;
+        return GFDM_HIP_OK;
+    });
 }
 
 int gfdm_hip_burst_extractor_destroy(gfdm_hip_burst_extractor* h) { delete h; return GFDM_HIP_OK; }

@@ -19,12 +19,10 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <new>
 
 using gfdm::cf;
 using gfdm::api_fail;
-using gfdm::DeviceGuard;
-using gfdm::DevBuf;
+using gfdm::misaligned;
 
 namespace {
 
@@ -250,7 +248,7 @@ int check_call(const gfdm_hip_channel_model* h, const void* out, const void* in,
 int channel_enqueue(const gfdm_hip_channel_model* h, int sc16, void* out, const cf* in, int64_t n, int64_t history, int64_t offset, double gain, hipStream_t s)
 {
     if (n == 0) return GFDM_HIP_OK;
-    if (((uintptr_t)out % (sc16 ? 4 : 8)) || ((uintptr_t)in % 8)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
+    if (misaligned(out, sc16 ? 4 : 8) || misaligned(in, 8)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
     ChannelArgs a;
     a.in = in;
     a.n = n;
@@ -279,9 +277,9 @@ int channel_device(gfdm_hip_channel_model* h, int sc16, void* out, const void* i
 {
     const int rc = check_call(h, out, in, sc16, n, history, offset, gain);
     if (rc != GFDM_HIP_OK || n == 0) return rc;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return channel_enqueue(h, sc16, out, static_cast<const cf*>(in), n, history, offset, gain, (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
+        return channel_enqueue(h, sc16, out, static_cast<const cf*>(in), n, history, offset, gain, s);
+    });
 }
 
 // upload history + n samples, one enqueue on the handle's stream, download n
@@ -289,18 +287,10 @@ int channel_host(gfdm_hip_channel_model* h, int sc16, void* out, const float* in
 {
     const int rc = check_call(h, out, in, sc16, n, history, offset, gain);
     if (rc != GFDM_HIP_OK || n == 0) return rc;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t ibytes = (size_t)(history + n) * sizeof(cf), obytes = (size_t)n * (sc16 ? 2 * sizeof(int16_t) : sizeof(cf));
-    DevBuf d_in, d_out;
-    GFDM_TRY(d_in.alloc(ibytes));
-    GFDM_TRY(d_out.alloc(obytes));
-    GFDM_TRY(gfdm::upload(d_in.p, reinterpret_cast<const cf*>(in) - history, ibytes, h->ctx.stream));
-    const int rc2 = channel_enqueue(h, sc16, d_out.p, d_in.as<const cf>() + history, n, history, offset, gain, h->ctx.stream);
-    if (rc2 != GFDM_HIP_OK) return rc2;
-    GFDM_TRY(gfdm::download(out, d_out.p, obytes, h->ctx.stream));
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(reinterpret_cast<const cf*>(in) - history, (size_t)(history + n));
+    const auto y = hc.out(static_cast<unsigned char*>(out), (size_t)n * (sc16 ? 2 * sizeof(int16_t) : sizeof(cf)));
+    return hc.run([&](hipStream_t s) { return channel_enqueue(h, sc16, y.dev(), x.dev() + history, n, history, offset, gain, s); });
 }
 
 }  // namespace
@@ -310,28 +300,20 @@ extern "C" {
 int gfdm_hip_channel_model_create(gfdm_hip_channel_model** out, const float* taps, int n_taps, double frequency_offset, double noise_voltage, uint64_t seed,
                                   int device)
 {
-    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
-    *out = nullptr;
-    int rc = taps_check(taps, n_taps);
-    if (rc == GFDM_HIP_OK) rc = channel_check(n_taps, frequency_offset, noise_voltage, 0, 0, 0, 1.0);
-    if (rc != GFDM_HIP_OK) return rc;
-    gfdm_hip_channel_model* h = new (std::nothrow) gfdm_hip_channel_model();
-    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->T = n_taps;
-    for (int t = 0; t < n_taps; ++t) {
-        h->taps[t] = make_float2(taps[2 * t], taps[2 * t + 1]);
-        if (taps[2 * t + 1] != 0.f) h->real_taps = 0;
-    }
-    h->f = frequency_offset;
-    h->s = noise_voltage;
-    h->seed = seed;
-    rc = h->ctx.open(device);
-    if (rc != GFDM_HIP_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return GFDM_HIP_OK;
+    return gfdm::create_handle(out, device, [&](gfdm_hip_channel_model& h) -> int {
+        int rc = taps_check(taps, n_taps);
+        if (rc == GFDM_HIP_OK) rc = channel_check(n_taps, frequency_offset, noise_voltage, 0, 0, 0, 1.0);
+        if (rc != GFDM_HIP_OK) return rc;
+        h.T = n_taps;
+        for (int t = 0; t < n_taps; ++t) {
+            h.taps[t] = make_float2(taps[2 * t], taps[2 * t + 1]);
+            if (taps[2 * t + 1] != 0.f) h.real_taps = 0;
+        }
+        h.f = frequency_offset;
+        h.s = noise_voltage;
+        h.seed = seed;
+        return GFDM_HIP_OK;
+    });
 }
 
 int gfdm_hip_channel_model_destroy(gfdm_hip_channel_model* h) { delete h; return GFDM_HIP_OK; }

@@ -1,11 +1,21 @@
 // Internal, device side: the hard decision of one symbol pair and what goes with it, shared by the symbol mapper (gfdm_symbols.hip:
 // decode) and the link meter (gfdm_linkmeter.hip: measure) -- one device function, so that an error counted by the meter is an error in
-// the bytes decode writes, to the bit.  The contract is written out in include/gfdm_hip.h (gfdm_hip_symbol_mapper, decode).
+// the bytes decode writes, to the bit.  The contract is written out in include/gfdm_hip.h (gfdm_hip_symbol_mapper, decode).  live_rows is
+// the clamp of the optional `count` operand, for those two, the convolutional code and the burst shaper.
 #pragma once
 #include "../../include/gfdm_hip.h"
 #include "gfdm_plan.h"
 
+#include <algorithm>
+
 namespace gfdm {
+
+// the rows (bursts) of a call that are live: all of them, or the optional device-side count clamped to [0, n_rows]
+__host__ __device__ __forceinline__ int64_t live_rows(const int64_t* count, int64_t n_rows)
+{
+    if (!count) return n_rows;
+    return std::min(std::max(*count, (int64_t)0), n_rows);
+}
 
 // (row, index in the row) of the flat element d behind the one at (r0, i0); rows of n elements, i0 < n.  No 64-bit division: past the
 // first row what is left of d is below 2^32, and so is n where a quotient is needed at all.

@@ -30,13 +30,12 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <new>
 
 using gfdm::RowPos;
 using gfdm::advance;
 using gfdm::api_fail;
-using gfdm::DeviceGuard;
-using gfdm::DevBuf;
+using gfdm::live_rows;
+using gfdm::misaligned;
 
 namespace {
 
@@ -69,12 +68,6 @@ struct EncodeArgs {
     int n_info, steps;
     int g0, g1;
 };
-
-__device__ __forceinline__ int64_t live_rows(const int64_t* count, int64_t n_rows)
-{
-    if (!count) return n_rows;
-    return std::min(std::max(*count, (int64_t)0), n_rows);
-}
 
 // c_i(R) = parity(R & |g|) ^ (g < 0)
 __device__ __forceinline__ int coded_bit(int R, int g)
@@ -348,7 +341,7 @@ int encode_enqueue(const gfdm_hip_conv_code* h, void* out, const void* data, con
                    hipStream_t s)
 {
     if (n_rows == 0) return GFDM_HIP_OK;
-    if ((uintptr_t)count % sizeof(int64_t)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one element");
+    if (misaligned(count, sizeof(int64_t))) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one element");
     const Geometry geo = geometry_of(h, n_info);
     const EncodeArgs a = { static_cast<const unsigned char*>(data), static_cast<unsigned char*>(out), static_cast<const int64_t*>(count), n_rows,
                            geo.info_bytes, out_row_bytes, (int)n_info, (int)geo.steps, h->g[0], h->g[1] };
@@ -364,12 +357,12 @@ int decode_enqueue(const gfdm_hip_conv_code* h, Op op, void* out, void* path_met
                    float gain, int64_t n_rows, void* workspace, hipStream_t s)
 {
     if (n_rows == 0) return GFDM_HIP_OK;
-    if (((uintptr_t)count % sizeof(int64_t)) || ((uintptr_t)path_metric % sizeof(int32_t)) || (op == OP_SOFT && ((uintptr_t)in % sizeof(float))))
+    if (misaligned(count, sizeof(int64_t)) || misaligned(path_metric, sizeof(int32_t)) || (op == OP_SOFT && misaligned(in, sizeof(float))))
         return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one element");
     const Geometry geo = geometry_of(h, n_info);
     const bool ws = geo.steps > GFDM_HIP_CC_LDS_STEPS;
     if (ws && !workspace) return api_fail(GFDM_HIP_EINVAL, "rows of this length need a workspace (gfdm_hip_conv_code_decode_workspace_bytes)");
-    if (ws && ((uintptr_t)workspace % 16)) return api_fail(GFDM_HIP_EINVAL, "the workspace must be 16-byte aligned");
+    if (ws && misaligned(workspace, 16)) return api_fail(GFDM_HIP_EINVAL, "the workspace must be 16-byte aligned");
     const int tpad = (int)tpad_of(geo.steps);
     const DecodeArgs a = { in, static_cast<unsigned char*>(out), static_cast<int32_t*>(path_metric), static_cast<const int64_t*>(count),
                            ws ? static_cast<unsigned long long*>(workspace) : nullptr, n_rows, stride, geo.info_bytes, (int)n_info, (int)geo.steps, tpad,
@@ -393,20 +386,11 @@ int encode_host(gfdm_hip_conv_code* h, uint8_t* out, const uint8_t* data, const 
     const int rc0 = check_encode(h, out, data, n_info, out_row_bytes, n_rows);
     if (rc0 != GFDM_HIP_OK) return rc0;
     if (n_rows == 0) return GFDM_HIP_OK;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t ibytes = (size_t)n_rows * (size_t)geometry_of(h, n_info).info_bytes, obytes = (size_t)n_rows * (size_t)out_row_bytes;
-    DevBuf d_in, d_count, d_out;
-    GFDM_TRY(d_in.alloc(ibytes));
-    GFDM_TRY(d_count.alloc(sizeof(int64_t)));
-    GFDM_TRY(d_out.alloc(obytes));
-    GFDM_TRY(gfdm::upload(d_in.p, data, ibytes, h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_count.p, count, sizeof(int64_t), h->ctx.stream));
-    const int rc = encode_enqueue(h, d_out.p, d_in.p, count ? d_count.p : nullptr, n_info, out_row_bytes, n_rows, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(out, d_out.p, obytes, h->ctx.stream));
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(data, (size_t)n_rows * (size_t)geometry_of(h, n_info).info_bytes);
+    const auto cnt = hc.in(count, 1);
+    const auto y = hc.out(out, (size_t)n_rows * (size_t)out_row_bytes);
+    return hc.run([&](hipStream_t s) { return encode_enqueue(h, y.dev(), x.dev(), cnt.dev(), n_info, out_row_bytes, n_rows, s); });
 }
 
 // upload the rows (and the count), one enqueue on the handle's stream with a workspace of the call's own, download the result
@@ -416,25 +400,16 @@ int decode_host(gfdm_hip_conv_code* h, Op op, uint8_t* out, int32_t* path_metric
     const int rc0 = check_decode(h, op, out, in, n_info, stride, gain, n_rows);
     if (rc0 != GFDM_HIP_OK) return rc0;
     if (n_rows == 0) return GFDM_HIP_OK;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t n = (size_t)n_rows, ibytes = n * (size_t)stride * (op == OP_SOFT ? sizeof(float) : 1), obytes = n * (size_t)geometry_of(h, n_info).info_bytes;
-    DevBuf d_in, d_args, d_out, d_ws;
-    GFDM_TRY(d_in.alloc(ibytes));
-    GFDM_TRY(d_args.alloc(sizeof(int64_t) + n * sizeof(int32_t)));
-    GFDM_TRY(d_out.alloc(obytes));
-    GFDM_TRY(d_ws.alloc((size_t)workspace_bytes_of(h, n_info, n_rows)));
-    int64_t* d_count = d_args.take<int64_t>(1);
-    int32_t* d_metric = d_args.take<int32_t>(n);
-    GFDM_TRY(gfdm::upload(d_in.p, in, ibytes, h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_count, count, sizeof(int64_t), h->ctx.stream));
-    const int rc = decode_enqueue(h, op, d_out.p, path_metric ? d_metric : nullptr, d_in.p, count ? d_count : nullptr, n_info, stride, gain, n_rows, d_ws.p,
-                                  h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(out, d_out.p, obytes, h->ctx.stream));
-    GFDM_TRY(gfdm::download(path_metric, d_metric, n * sizeof(int32_t), h->ctx.stream));
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    const size_t n = (size_t)n_rows;
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(static_cast<const unsigned char*>(in), n * (size_t)stride * (op == OP_SOFT ? sizeof(float) : 1));
+    const auto cnt = hc.in(count, 1);
+    const auto y = hc.out(out, n * (size_t)geometry_of(h, n_info).info_bytes);
+    const auto pm = hc.out(path_metric, n);
+    const auto ws = hc.scratch<unsigned char>((size_t)workspace_bytes_of(h, n_info, n_rows));
+    return hc.run([&](hipStream_t s) {
+        return decode_enqueue(h, op, y.dev(), pm.dev(), x.dev(), cnt.dev(), n_info, stride, gain, n_rows, ws.dev(), s);
+    });
 }
 
 int decode_device(gfdm_hip_conv_code* h, Op op, void* out, void* path_metric, const void* in, const void* count, int64_t n_info, int64_t stride, float gain,
@@ -442,9 +417,9 @@ int decode_device(gfdm_hip_conv_code* h, Op op, void* out, void* path_metric, co
 {
     const int rc = check_decode(h, op, out, in, n_info, stride, gain, n_rows);
     if (rc != GFDM_HIP_OK) return rc;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return decode_enqueue(h, op, out, path_metric, in, count, n_info, stride, gain, n_rows, workspace, (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
+        return decode_enqueue(h, op, out, path_metric, in, count, n_info, stride, gain, n_rows, workspace, s);
+    });
 }
 
 // a size getter: the status code where the arguments are bad
@@ -461,22 +436,12 @@ extern "C" {
 
 int gfdm_hip_conv_code_create(gfdm_hip_conv_code** out, int poly0, int poly1, int mode, int device)
 {
-    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
-    *out = nullptr;
-    const int rc0 = code_check(poly0, poly1, mode, 1, 0);
-    if (rc0 != GFDM_HIP_OK) return rc0;
-    gfdm_hip_conv_code* h = new (std::nothrow) gfdm_hip_conv_code();
-    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->g[0] = poly0;
-    h->g[1] = poly1;
-    h->mode = mode;
-    const int rc = h->ctx.open(device);
-    if (rc != GFDM_HIP_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return GFDM_HIP_OK;
+    return gfdm::create_handle(out, device, [&](gfdm_hip_conv_code& h) {
+        h.g[0] = poly0;
+        h.g[1] = poly1;
+        h.mode = mode;
+        return code_check(poly0, poly1, mode, 1, 0);
+    });
 }
 
 int gfdm_hip_conv_code_destroy(gfdm_hip_conv_code* c) { delete c; return GFDM_HIP_OK; }
@@ -514,9 +479,7 @@ int gfdm_hip_conv_code_encode_device(gfdm_hip_conv_code* c, void* out, const voi
 {
     const int rc = check_encode(c, out, data, n_info, out_row_bytes, n_rows);
     if (rc != GFDM_HIP_OK) return rc;
-    DeviceGuard guard(c->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return encode_enqueue(c, out, data, count, n_info, out_row_bytes, n_rows, (hipStream_t)stream);
+    return gfdm::on_device(c->ctx.device, stream, [&](hipStream_t s) { return encode_enqueue(c, out, data, count, n_info, out_row_bytes, n_rows, s); });
 }
 int gfdm_hip_conv_code_decode_host(gfdm_hip_conv_code* c, uint8_t* out, int32_t* path_metric, const float* llr, const int64_t* count, int64_t n_info,
                                    int64_t llr_stride, float gain, int64_t n_rows)

@@ -1776,9 +1776,9 @@ int bursts_device(RxCore& rx, void* out, const void* samples, int fmt, int64_t s
     ep.io.off = static_cast<const int64_t*>(offsets);
     ep.io.rot = cfo_correction ? static_cast<const cf*>(sc_rot) : nullptr;
     ep.io.count = static_cast<const int64_t*>(count);
-    DeviceGuard guard(rx.plan.device);
-    if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return status_of(rx_launch(rx.plan, ic, rx.mode, static_cast<cf*>(out), nullptr, nullptr, n_bursts, static_cast<hipStream_t>(stream), &ep.est));
+    return gfdm::on_device(rx.plan.device, stream, [&](hipStream_t s) {
+        return status_of(rx_launch(rx.plan, ic, rx.mode, static_cast<cf*>(out), nullptr, nullptr, n_bursts, s, &ep.est));
+    });
 }
 
 // convenience, not a pipeline: capture (in the caller's format: an sc16 capture goes up as int16) and arrays to the device, ONE launch,
@@ -1792,26 +1792,16 @@ int bursts_host(RxCore& rx, float* out, const void* samples, int fmt, int64_t st
     int rc = bursts_call_io(rx, stream_len, backoff, preamble_offset, noutput_size, n_bursts, io, ep);
     if (rc != GFDM_HIP_OK || n_bursts == 0) return rc;
     if (!out || !offsets || (!samples && stream_len > 0)) return fail(GFDM_HIP_EINVAL, "NULL buffer");
-    DeviceGuard guard(pl.device);
-    if (!guard.ok) return fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t n = (size_t)n_bursts, out_bytes = n * (size_t)io.nout * sizeof(cf), cap_bytes = (size_t)stream_len * gfdm::sample_bytes(fmt);
-    gfdm::DevBuf d_s, d_args, d_out;
-    GFDM_TRY(d_s.alloc(cap_bytes));
-    GFDM_TRY(d_args.alloc((n + 1) * sizeof(int64_t) + n * sizeof(cf)));
-    GFDM_TRY(d_out.alloc(out_bytes));
-    int64_t* d_off = d_args.take<int64_t>(n);
-    int64_t* d_cnt = d_args.take<int64_t>(1);
-    cf* d_rot = d_args.take<cf>(n);
-    GFDM_TRY(gfdm::upload(d_s.p, samples, cap_bytes, pl.stream));
-    GFDM_TRY(gfdm::upload(d_off, offsets, n * sizeof(int64_t), pl.stream));
-    GFDM_TRY(gfdm::upload(d_cnt, count, sizeof(int64_t), pl.stream));
-    GFDM_TRY(gfdm::upload(d_rot, sc_rot, n * sizeof(cf), pl.stream));
-    rc = bursts_device(rx, d_out.p, d_s.p, fmt, stream_len, d_off, sc_rot ? d_rot : nullptr, count ? d_cnt : nullptr, backoff, preamble_offset,
-                       cfo_correction, noutput_size, n_bursts, pl.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(out, d_out.p, out_bytes, pl.stream));
-    GFDM_TRY(hipStreamSynchronize(pl.stream));
-    return GFDM_HIP_OK;
+    const size_t n = (size_t)n_bursts;
+    gfdm::HostCall hc(pl.device, pl.stream);
+    const auto x = hc.in(static_cast<const unsigned char*>(samples), (size_t)stream_len * gfdm::sample_bytes(fmt));
+    const auto off = hc.in(offsets, n);
+    const auto cnt = hc.in(count, 1);
+    const auto rot = hc.in(sc_rot, 2 * n);
+    const auto y = hc.out(out, n * (size_t)io.nout * 2);
+    return hc.run([&](hipStream_t s) {
+        return bursts_device(rx, y.dev(), x.dev(), fmt, stream_len, off.dev(), rot.dev(), cnt.dev(), backoff, preamble_offset, cfo_correction, noutput_size, n_bursts, s);
+    });
 }
 
 }  // namespace

@@ -1,12 +1,18 @@
 // Internal, host only: what every translation unit of the C-ABI needs around a runtime call -- error reporting, the device guard, the device
-// check, a handle's device + private stream, and the device memory of one convenience host call.  Never seen by hiprtc (not in JIT_HDRS).
+// check, a handle's device + private stream, the skeletons of a constructor (create_handle) and of a *_device call (on_device), the staged
+// *_host call (HostCall: one allocation, uploads, the enqueue, downloads, one synchronise) and the constellation the symbol mapper and the
+// link meter share.  Compiled as plain C++ by tests/sanitize (hostcall_check.cc).  Never seen by hiprtc (not in JIT_HDRS).
 #pragma once
 #include "../../include/gfdm_hip.h"
 #include "gfdm_plan.h"
 
 #include <cfloat>
+#include <algorithm>
 #include <cmath>
+#include <new>
 #include <string>
+#include <type_traits>
+#include <vector>
 
 namespace gfdm {
 
@@ -90,42 +96,196 @@ struct DeviceCtx {
     }
     ~DeviceCtx()
     {
+        if (!stream) return;         // never opened (a constructor that refused its arguments): no runtime call
         DeviceGuard guard(device);
-        if (stream) (void)hipStreamDestroy(stream);
+        (void)hipStreamDestroy(stream);
     }
 };
 
 // bytes of one sample of a capture (SampleFormat): the host flavours upload it in the caller's format
 inline size_t sample_bytes(int fmt) { return fmt == SAMPLES_SC16 ? 2 * sizeof(int16_t) : sizeof(cf); }
 
-// Device memory that lives for one host call (upload, ONE enqueue, download, synchronise: a convenience, not a pipeline).  A buffer is
-// handed out whole (as) or piece by piece (take; pieces in descending order of alignment, the caller sizes the buffer for their sum).
-struct DevBuf {
-    void* p = nullptr;
-    size_t taken = 0;
+inline bool misaligned(const void* p, size_t to) { return ((uintptr_t)p % to) != 0; }
 
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }          // a zero-length request still yields a pointer
-    template <class T> T* as() const { return static_cast<T*>(p); }
-    template <class T> T* take(size_t count)
+// The *_device flavour of an entry point, after its checks: make the handle's device current, refuse if that failed, enqueue on the caller's stream.
+template <class F>
+int on_device(int device, void* stream, F enqueue)
+{
+    DeviceGuard guard(device);
+    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+    return enqueue((hipStream_t)stream);
+}
+
+// The skeleton of a constructor.  `init` checks the arguments and fills the handle's host fields; `on_dev` runs with the device current and
+// the context open, for what the handle keeps on the device.  Any failure deletes the handle.  A call that `init` refuses makes no runtime
+// call at all, as when the checks ran before the handle existed: the destructor of a handle (and of its DeviceCtx) builds its DeviceGuard
+// only when there is a stream or device memory to release (tests/sanitize/hostcall_check.cc counts the calls).
+template <class H, class Init, class OnDev>
+int create_handle(H** out, int device, Init init, OnDev on_dev)
+{
+    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
+    *out = nullptr;
+    H* h = new (std::nothrow) H();
+    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
+    int rc = init(*h);
+    if (rc == GFDM_HIP_OK) rc = h->ctx.open(device);
+    if (rc == GFDM_HIP_OK) {
+        DeviceGuard guard(device);
+        rc = on_dev(*h);
+    }
+    if (rc != GFDM_HIP_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return GFDM_HIP_OK;
+}
+template <class H, class Init>
+int create_handle(H** out, int device, Init init)
+{
+    return create_handle(out, device, init, [](H&) { return GFDM_HIP_OK; });
+}
+
+// One convenience *_host call (a convenience, not a pipeline): everything around the enqueue of the *_device flavour.  The caller declares
+// its operands -- in: a host array that goes up, out: one that comes back, scratch: device only -- and run() does the rest on the handle's
+// private stream: ONE device allocation for all pieces, the uploads, the callable, the downloads, ONE synchronise; the allocation is freed
+// with the object.  The pieces lie in the order of declaration, each at least 16 bytes long and on a 256-byte boundary, and the allocation
+// ends with the last piece.  256 is what hipMalloc guarantees, so every piece keeps the alignment it had as an allocation of its own: the
+// kernels take the same aligned / unaligned (`mis`) paths, and memsets and copies see the same addresses modulo 256, as before.  An operand whose
+// host pointer is NULL takes no room, is not copied and is NULL to the enqueue; an empty one with a host pointer has a valid device address.
+// A failing runtime call or a non-OK status of the callable ends the call with that status (no synchronise after a failed enqueue).
+class HostCall {
+public:
+    template <class T>
+    class Piece {
+    public:
+        T* dev() const { return present_ ? reinterpret_cast<T*>(hc_->base_ + off_) : nullptr; }      // valid inside run()'s callable
+
+    private:
+        friend class HostCall;
+        const HostCall* hc_;
+        size_t off_;
+        bool present_;
+    };
+
+    HostCall(int device, hipStream_t stream) : guard_(device), stream_(stream) {}
+    explicit HostCall(const DeviceCtx& ctx) : HostCall(ctx.device, ctx.stream) {}
+    HostCall(const HostCall&) = delete;
+    HostCall& operator=(const HostCall&) = delete;
+    ~HostCall() { if (base_) (void)hipFree(base_); }
+
+    template <class T> Piece<const T> in(const T* host, size_t count)
     {
-        T* piece = reinterpret_cast<T*>(static_cast<unsigned char*>(p) + taken);
-        taken += count * sizeof(T);
-        return piece;
+        const Piece<const T> p = place<const T>(host != nullptr, count * sizeof(T));
+        if (host && count) up_.push_back(Copy{ p.off_, const_cast<T*>(host), count * sizeof(T) });
+        return p;
+    }
+    template <class T> Piece<T> out(T* host, size_t count)
+    {
+        const Piece<T> p = place<T>(host != nullptr, count * sizeof(T));
+        if (host && count) down_.push_back(Copy{ p.off_, host, count * sizeof(T) });
+        return p;
+    }
+    template <class T> Piece<T> scratch(size_t count) { return place<T>(true, count * sizeof(T)); }
+
+    template <class F>
+    int run(F enqueue)
+    {
+        if (!guard_.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
+        if (size_) GFDM_TRY(hipMalloc(&base_, size_));
+        for (const Copy& c : up_) GFDM_TRY(hipMemcpyAsync(base_ + c.off, c.host, c.bytes, hipMemcpyHostToDevice, stream_));
+        const int rc = enqueue(stream_);
+        if (rc != GFDM_HIP_OK) return rc;
+        for (const Copy& c : down_) GFDM_TRY(hipMemcpyAsync(c.host, base_ + c.off, c.bytes, hipMemcpyDeviceToHost, stream_));
+        GFDM_TRY(hipStreamSynchronize(stream_));
+        return GFDM_HIP_OK;
+    }
+
+private:
+    struct Copy { size_t off; void* host; size_t bytes; };
+    static constexpr size_t kAlign = 256;      // hipMalloc's own guarantee: a piece is aligned as it was when it had an allocation to itself
+
+    template <class T> Piece<T> place(bool present, size_t bytes)
+    {
+        Piece<T> p;
+        p.hc_ = this;
+        p.off_ = (size_ + kAlign - 1) / kAlign * kAlign;
+        p.present_ = present;
+        if (present) size_ = p.off_ + (bytes > 16 ? bytes : 16);
+        return p;
+    }
+
+    DeviceGuard guard_;              // first: the device stays current until the allocation is freed
+    hipStream_t stream_;
+    unsigned char* base_ = nullptr;
+    size_t size_ = 0;
+    std::vector<Copy> up_, down_;
+};
+
+// ---- the constellation of a handle: the symbol mapper and the link meter decide with the same points and the same rule ----
+inline int bits_of(int n_points)
+{
+    for (int k = 1; k <= 8; ++k)
+        if (n_points == (1 << k)) return k;
+    return 0;
+}
+
+inline int64_t row_bytes_of(int k, int64_t n_sym) { return (n_sym * k + 7) / 8; }
+
+struct Constellation {
+    int k = 0, rule = GFDM_HIP_DECIDE_NEAREST;
+    cf points[256];
+    cf* d_points = nullptr;          // freed by the owning handle's destructor, under the guard it builds for its own device memory
+
+    Constellation() = default;
+    Constellation(const Constellation&) = delete;
+    Constellation& operator=(const Constellation&) = delete;
+    // the argument checks and the host copy: no device yet
+    int set(const float* pts, int n_points, int decision)
+    {
+        const int rc = gfdm_hip_symbol_mapper_check(n_points, 1, 0);
+        if (rc != GFDM_HIP_OK) return rc;
+        if (!pts) return api_fail(GFDM_HIP_EINVAL, "NULL constellation points");
+        if (decision < GFDM_HIP_DECIDE_AUTO || decision > GFDM_HIP_DECIDE_BPSK) return api_fail(GFDM_HIP_EINVAL, "bad decision rule");
+        rule = resolve_decision(reinterpret_cast<const cf*>(pts), n_points, decision);
+        if (rule < 0) return api_fail(GFDM_HIP_EINVAL, "decision rule does not match the number of constellation points");
+        k = bits_of(n_points);
+        std::copy(reinterpret_cast<const cf*>(pts), reinterpret_cast<const cf*>(pts) + n_points, points);
+        return GFDM_HIP_OK;
+    }
+    // the points on the handle's device (which is current)
+    int upload()
+    {
+        const size_t bytes = ((size_t)1 << k) * sizeof(cf);
+        hipError_t e = hipMalloc(&d_points, bytes);
+        if (e == hipSuccess) e = hipMemcpy(d_points, points, bytes, hipMemcpyHostToDevice);
+        return e == hipSuccess ? GFDM_HIP_OK : api_fail_hip(e, "constellation upload");
     }
 };
 
-// host array -> device piece / device piece -> host array on the call's stream; an absent (NULL) host array or an empty one is skipped
-inline hipError_t upload(void* dev, const void* host, size_t bytes, hipStream_t s)
+// f(std::integral_constant<int, K>) for the run-time k = 1 .. 8
+template <class F>
+void dispatch_bits(int k, F f)
 {
-    return (host && bytes) ? hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    switch (k) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 5: f(std::integral_constant<int, 5>()); break;
+    case 6: f(std::integral_constant<int, 6>()); break;
+    case 7: f(std::integral_constant<int, 7>()); break;
+    default: f(std::integral_constant<int, 8>()); break;
+    }
 }
-inline hipError_t download(void* host, const void* dev, size_t bytes, hipStream_t s)
+
+// f(K, RULE) as integral constants for the rule a handle runs: the sign tests exist for the unit QPSK and BPSK points alone
+template <int K, class F>
+void with_rule(int rule, F f)
 {
-    return (host && bytes) ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    if (K == 2 && rule == GFDM_HIP_DECIDE_QPSK) f(std::integral_constant<int, 2>(), std::integral_constant<int, GFDM_HIP_DECIDE_QPSK>());
+    else if (K == 1 && rule == GFDM_HIP_DECIDE_BPSK) f(std::integral_constant<int, 1>(), std::integral_constant<int, GFDM_HIP_DECIDE_BPSK>());
+    else f(std::integral_constant<int, K>(), std::integral_constant<int, GFDM_HIP_DECIDE_NEAREST>());
 }
 
 }  // namespace gfdm

@@ -20,12 +20,13 @@
 
 #include <algorithm>
 #include <climits>
-#include <new>
 
 using gfdm::cf;
 using gfdm::api_fail;
 using gfdm::DeviceGuard;
-using gfdm::DevBuf;
+using gfdm::row_bytes_of;
+using gfdm::live_rows;
+using gfdm::misaligned;
 using gfdm::RowPos;
 using gfdm::advance;
 using gfdm::dist2;
@@ -61,12 +62,6 @@ struct MeasureArgs {
     Partial* part;                   // [ntiles][2]: [0] the row that began before the tile, [1] the row that began in it and ends behind it
     u64* totals;
 };
-
-__device__ __forceinline__ int64_t live_rows(const int64_t* count, int64_t n_rows)
-{
-    if (!count) return n_rows;
-    return std::min(std::max(*count, (int64_t)0), n_rows);
-}
 
 // the payload row of row r, or -1 where r is not measured
 __device__ __forceinline__ int64_t ref_of(const MeasureArgs& a, int64_t r, int64_t n_live)
@@ -471,53 +466,33 @@ __global__ __launch_bounds__(kLanes) void k_meter_match_resolve(MatchArgs a)
     }
 }
 
-int bits_of(int n_points)
-{
-    for (int k = 1; k <= 8; ++k)
-        if (n_points == (1 << k)) return k;
-    return 0;
-}
-
-int64_t row_bytes_of(int k, int64_t n_sym) { return (n_sym * k + 7) / 8; }
-
 int64_t tiles_of(int64_t n_sym, int64_t n_rows) { return (n_sym * n_rows + kTileSyms - 1) / kTileSyms; }
 
 }  // namespace
 
 struct gfdm_hip_link_meter {
     gfdm::DeviceCtx ctx;
-    int k = 0, rule = GFDM_HIP_DECIDE_NEAREST;
-    cf* d_points = nullptr;
+    gfdm::Constellation c;
     u64* d_totals = nullptr;
     ~gfdm_hip_link_meter()
     {
+        if (!c.d_points && !d_totals) return;
         DeviceGuard guard(ctx.device);
-        if (d_points) (void)hipFree(d_points);
-        if (d_totals) (void)hipFree(d_totals);
+        (void)hipFree(c.d_points);
+        (void)hipFree(d_totals);
     }
 };
 
 namespace {
-
-template <int K>
-void launch_measure(const gfdm_hip_link_meter* h, const MeasureArgs& a, unsigned grid, hipStream_t s)
-{
-    const dim3 block(kLanes);
-    if (K == 2 && h->rule == GFDM_HIP_DECIDE_QPSK) hipLaunchKernelGGL((k_meter_measure<2, GFDM_HIP_DECIDE_QPSK>), dim3(grid), block, 0, s, a);
-    else if (K == 1 && h->rule == GFDM_HIP_DECIDE_BPSK) hipLaunchKernelGGL((k_meter_measure<1, GFDM_HIP_DECIDE_BPSK>), dim3(grid), block, 0, s, a);
-    else hipLaunchKernelGGL((k_meter_measure<K, GFDM_HIP_DECIDE_NEAREST>), dim3(grid), block, 0, s, a);
-}
-
-bool misaligned(const void* p, size_t to) { return ((uintptr_t)p % to) != 0; }
 
 // the argument table of measure (include/gfdm_hip.h); needs no device
 int measure_check(const gfdm_hip_link_meter* h, const void* bit_errors, const void* symbols, const void* payload, int64_t n_ref, int64_t n_sym, int64_t n_rows,
                   const void* workspace, bool device)
 {
     if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
-    const int rc = gfdm_hip_symbol_mapper_check(1 << h->k, n_sym, n_rows);
+    const int rc = gfdm_hip_symbol_mapper_check(1 << h->c.k, n_sym, n_rows);
     if (rc != GFDM_HIP_OK) return rc;
-    if (n_sym > (int64_t)INT32_MAX / h->k) return api_fail(GFDM_HIP_EINVAL, "n_sym * k must be <= 2^31 - 1: the bit errors of a row are an int32");
+    if (n_sym > (int64_t)INT32_MAX / h->c.k) return api_fail(GFDM_HIP_EINVAL, "n_sym * k must be <= 2^31 - 1: the bit errors of a row are an int32");
     if (n_ref < 0) return api_fail(GFDM_HIP_EINVAL, "n_ref must be >= 0");
     if (!payload && bit_errors) return api_fail(GFDM_HIP_EINVAL, "bit_errors needs a payload: a decision-directed call counts no errors");
     if (n_rows > 0 && !symbols) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
@@ -534,21 +509,16 @@ int measure_enqueue(const gfdm_hip_link_meter* h, void* bit_errors, void* err_po
         misaligned(ref_row, sizeof(int64_t)) || misaligned(count, sizeof(int64_t)))
         return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one element");
     if (misaligned(workspace, 16)) return api_fail(GFDM_HIP_EINVAL, "the workspace must be 16-byte aligned");
-    const MeasureArgs a = { h->d_points, static_cast<const cf*>(symbols), static_cast<const unsigned char*>(payload), static_cast<const int64_t*>(ref_row),
-                            static_cast<const int64_t*>(count), n_sym, n_rows, n_ref, row_bytes_of(h->k, n_sym), static_cast<int32_t*>(bit_errors),
+    const MeasureArgs a = { h->c.d_points, static_cast<const cf*>(symbols), static_cast<const unsigned char*>(payload), static_cast<const int64_t*>(ref_row),
+                            static_cast<const int64_t*>(count), n_sym, n_rows, n_ref, row_bytes_of(h->c.k, n_sym), static_cast<int32_t*>(bit_errors),
                             static_cast<float*>(err_power), static_cast<float*>(ref_power), static_cast<Partial*>(workspace), h->d_totals };
     const int64_t ntiles = tiles_of(n_sym, n_rows);
     const unsigned grid = (unsigned)std::min<int64_t>(ntiles, kMaxTiles);
-    switch (h->k) {
-    case 1: launch_measure<1>(h, a, grid, s); break;
-    case 2: launch_measure<2>(h, a, grid, s); break;
-    case 3: launch_measure<3>(h, a, grid, s); break;
-    case 4: launch_measure<4>(h, a, grid, s); break;
-    case 5: launch_measure<5>(h, a, grid, s); break;
-    case 6: launch_measure<6>(h, a, grid, s); break;
-    case 7: launch_measure<7>(h, a, grid, s); break;
-    default: launch_measure<8>(h, a, grid, s); break;
-    }
+    gfdm::dispatch_bits(h->c.k, [&](auto bits) {
+        gfdm::with_rule<decltype(bits)::value>(h->c.rule, [&](auto k, auto rule) {
+            hipLaunchKernelGGL((k_meter_measure<decltype(k)::value, decltype(rule)::value>), dim3(grid), dim3(kLanes), 0, s, a);
+        });
+    });
     GFDM_TRY(hipGetLastError());
     if (ntiles > 1) {
         hipLaunchKernelGGL(k_meter_crossing_rows, dim3((unsigned)((ntiles - 1 + kLanes - 1) / kLanes)), dim3(kLanes), 0, s, a, ntiles);
@@ -598,45 +568,27 @@ extern "C" {
 
 int gfdm_hip_link_meter_create(gfdm_hip_link_meter** out, const float* points, int n_points, int decision, int device)
 {
-    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
-    *out = nullptr;
-    const int rc0 = gfdm_hip_symbol_mapper_check(n_points, 1, 0);
-    if (rc0 != GFDM_HIP_OK) return rc0;
-    if (!points) return api_fail(GFDM_HIP_EINVAL, "NULL constellation points");
-    if (decision < GFDM_HIP_DECIDE_AUTO || decision > GFDM_HIP_DECIDE_BPSK) return api_fail(GFDM_HIP_EINVAL, "bad decision rule");
-    const int rule = gfdm::resolve_decision(reinterpret_cast<const cf*>(points), n_points, decision);
-    if (rule < 0) return api_fail(GFDM_HIP_EINVAL, "decision rule does not match the number of constellation points");
-    gfdm_hip_link_meter* h = new (std::nothrow) gfdm_hip_link_meter();
-    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->k = bits_of(n_points);
-    h->rule = rule;
-    int rc = h->ctx.open(device);
-    if (rc == GFDM_HIP_OK) {
-        DeviceGuard guard(device);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_points), (size_t)n_points * sizeof(cf));
-        if (e == hipSuccess) e = hipMemcpy(h->d_points, points, (size_t)n_points * sizeof(cf), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_totals), T_FIELDS * sizeof(u64));
-        if (e == hipSuccess) e = hipMemset(h->d_totals, 0, T_FIELDS * sizeof(u64));
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) rc = gfdm::api_fail_hip(e, "constellation upload");
-    }
-    if (rc != GFDM_HIP_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return GFDM_HIP_OK;
+    return gfdm::create_handle(
+        out, device, [&](gfdm_hip_link_meter& h) { return h.c.set(points, n_points, decision); },
+        [](gfdm_hip_link_meter& h) -> int {
+            const int rc = h.c.upload();
+            if (rc != GFDM_HIP_OK) return rc;
+            hipError_t e = hipMalloc(&h.d_totals, T_FIELDS * sizeof(u64));
+            if (e == hipSuccess) e = hipMemset(h.d_totals, 0, T_FIELDS * sizeof(u64));
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            return e == hipSuccess ? GFDM_HIP_OK : gfdm::api_fail_hip(e, "constellation upload");
+        });
 }
 
 int gfdm_hip_link_meter_destroy(gfdm_hip_link_meter* m) { delete m; return GFDM_HIP_OK; }
-int gfdm_hip_link_meter_bits_per_symbol(const gfdm_hip_link_meter* m) { return m ? m->k : GFDM_HIP_EINVAL; }
-int gfdm_hip_link_meter_n_points(const gfdm_hip_link_meter* m) { return m ? 1 << m->k : GFDM_HIP_EINVAL; }
-int gfdm_hip_link_meter_decision(const gfdm_hip_link_meter* m) { return m ? m->rule : GFDM_HIP_EINVAL; }
+int gfdm_hip_link_meter_bits_per_symbol(const gfdm_hip_link_meter* m) { return m ? m->c.k : GFDM_HIP_EINVAL; }
+int gfdm_hip_link_meter_n_points(const gfdm_hip_link_meter* m) { return m ? 1 << m->c.k : GFDM_HIP_EINVAL; }
+int gfdm_hip_link_meter_decision(const gfdm_hip_link_meter* m) { return m ? m->c.rule : GFDM_HIP_EINVAL; }
 int64_t gfdm_hip_link_meter_row_bytes(const gfdm_hip_link_meter* m, int64_t n_sym)
 {
     if (!m) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
-    const int rc = gfdm_hip_symbol_mapper_check(1 << m->k, n_sym, 0);
-    return rc != GFDM_HIP_OK ? rc : row_bytes_of(m->k, n_sym);
+    const int rc = gfdm_hip_symbol_mapper_check(1 << m->c.k, n_sym, 0);
+    return rc != GFDM_HIP_OK ? rc : row_bytes_of(m->c.k, n_sym);
 }
 
 void* gfdm_hip_link_meter_totals_device(gfdm_hip_link_meter* m) { return m ? m->d_totals : nullptr; }
@@ -644,21 +596,21 @@ void* gfdm_hip_link_meter_totals_device(gfdm_hip_link_meter* m) { return m ? m->
 int gfdm_hip_link_meter_reset(gfdm_hip_link_meter* m, void* stream)
 {
     if (!m) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
-    DeviceGuard guard(m->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    hipLaunchKernelGGL(k_meter_reset, dim3(1), dim3(64), 0, (hipStream_t)stream, m->d_totals);
-    GFDM_TRY(hipGetLastError());
-    return GFDM_HIP_OK;
+    return gfdm::on_device(m->ctx.device, stream, [&](hipStream_t s) -> int {
+        hipLaunchKernelGGL(k_meter_reset, dim3(1), dim3(64), 0, s, m->d_totals);
+        GFDM_TRY(hipGetLastError());
+        return GFDM_HIP_OK;
+    });
 }
 
 int gfdm_hip_link_meter_totals(gfdm_hip_link_meter* m, int64_t* out, void* stream)
 {
     if (!m || !out) return api_fail(GFDM_HIP_EINVAL, "NULL handle or output");
-    DeviceGuard guard(m->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    GFDM_TRY(hipStreamSynchronize((hipStream_t)stream));
-    GFDM_TRY(hipMemcpy(out, m->d_totals, T_FIELDS * sizeof(u64), hipMemcpyDeviceToHost));
-    return GFDM_HIP_OK;
+    return gfdm::on_device(m->ctx.device, stream, [&](hipStream_t s) -> int {
+        GFDM_TRY(hipStreamSynchronize(s));
+        GFDM_TRY(hipMemcpy(out, m->d_totals, T_FIELDS * sizeof(u64), hipMemcpyDeviceToHost));
+        return GFDM_HIP_OK;
+    });
 }
 
 int64_t gfdm_hip_link_meter_match_workspace_bytes(int64_t n_sent)
@@ -679,9 +631,9 @@ int gfdm_hip_link_meter_match_device(gfdm_hip_link_meter* m, void* ref_row, void
 {
     const int rc = match_check(m, frame_start, n_rows, sent_pos, n_sent, tol, workspace, true);
     if (rc != GFDM_HIP_OK) return rc;
-    DeviceGuard guard(m->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return match_enqueue(m, ref_row, sent_row, frame_start, count, n_rows, sent_pos, n_sent, offset, tol, workspace, (hipStream_t)stream);
+    return gfdm::on_device(m->ctx.device, stream, [&](hipStream_t s) {
+        return match_enqueue(m, ref_row, sent_row, frame_start, count, n_rows, sent_pos, n_sent, offset, tol, workspace, s);
+    });
 }
 
 int gfdm_hip_link_meter_match_host(gfdm_hip_link_meter* m, int64_t* ref_row, int64_t* sent_row, const int64_t* frame_start, const int64_t* count, int64_t n_rows,
@@ -690,27 +642,17 @@ int gfdm_hip_link_meter_match_host(gfdm_hip_link_meter* m, int64_t* ref_row, int
     const int rc0 = match_check(m, frame_start, n_rows, sent_pos, n_sent, tol, nullptr, false);
     if (rc0 != GFDM_HIP_OK) return rc0;
     if (n_rows == 0 && n_sent == 0) return GFDM_HIP_OK;
-    DeviceGuard guard(m->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
     const size_t nr = (size_t)n_rows, ns = (size_t)n_sent;
-    DevBuf d;
-    GFDM_TRY(d.alloc((2 * nr + 3 * ns + 1) * sizeof(int64_t)));
-    int64_t* d_fs = d.take<int64_t>(nr);
-    int64_t* d_ref = d.take<int64_t>(nr);
-    int64_t* d_pos = d.take<int64_t>(ns);
-    int64_t* d_sent = d.take<int64_t>(ns);
-    u64* d_key = d.take<u64>(ns);
-    int64_t* d_count = d.take<int64_t>(1);
-    hipStream_t s = m->ctx.stream;
-    GFDM_TRY(gfdm::upload(d_fs, frame_start, nr * sizeof(int64_t), s));
-    GFDM_TRY(gfdm::upload(d_pos, sent_pos, ns * sizeof(int64_t), s));
-    GFDM_TRY(gfdm::upload(d_count, count, sizeof(int64_t), s));
-    const int rc = match_enqueue(m, ref_row ? d_ref : nullptr, sent_row ? d_sent : nullptr, d_fs, count ? d_count : nullptr, n_rows, d_pos, n_sent, offset, tol, d_key, s);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(ref_row, d_ref, nr * sizeof(int64_t), s));
-    GFDM_TRY(gfdm::download(sent_row, d_sent, ns * sizeof(int64_t), s));
-    GFDM_TRY(hipStreamSynchronize(s));
-    return GFDM_HIP_OK;
+    gfdm::HostCall hc(m->ctx);
+    const auto fs = hc.in(frame_start, nr);
+    const auto pos = hc.in(sent_pos, ns);
+    const auto cnt = hc.in(count, 1);
+    const auto ref = hc.out(ref_row, nr);
+    const auto sent = hc.out(sent_row, ns);
+    const auto key = hc.scratch<u64>(ns);
+    return hc.run([&](hipStream_t s) {
+        return match_enqueue(m, ref.dev(), sent.dev(), fs.dev(), cnt.dev(), n_rows, pos.dev(), n_sent, offset, tol, key.dev(), s);
+    });
 }
 
 int gfdm_hip_link_meter_measure_device(gfdm_hip_link_meter* m, void* bit_errors, void* err_power, void* ref_power, const void* symbols, const void* payload,
@@ -718,9 +660,9 @@ int gfdm_hip_link_meter_measure_device(gfdm_hip_link_meter* m, void* bit_errors,
 {
     const int rc = measure_check(m, bit_errors, symbols, payload, n_ref, n_sym, n_rows, workspace, true);
     if (rc != GFDM_HIP_OK) return rc;
-    DeviceGuard guard(m->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return measure_enqueue(m, bit_errors, err_power, ref_power, symbols, payload, n_ref, ref_row, count, n_sym, n_rows, workspace, (hipStream_t)stream);
+    return gfdm::on_device(m->ctx.device, stream, [&](hipStream_t s) {
+        return measure_enqueue(m, bit_errors, err_power, ref_power, symbols, payload, n_ref, ref_row, count, n_sym, n_rows, workspace, s);
+    });
 }
 
 int gfdm_hip_link_meter_measure_host(gfdm_hip_link_meter* m, int32_t* bit_errors, float* err_power, float* ref_power, const float* symbols, const uint8_t* payload,
@@ -729,33 +671,19 @@ int gfdm_hip_link_meter_measure_host(gfdm_hip_link_meter* m, int32_t* bit_errors
     const int rc0 = measure_check(m, bit_errors, symbols, payload, n_ref, n_sym, n_rows, nullptr, false);
     if (rc0 != GFDM_HIP_OK) return rc0;
     if (n_rows == 0) return GFDM_HIP_OK;
-    DeviceGuard guard(m->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t nr = (size_t)n_rows, sym_bytes = nr * (size_t)n_sym * sizeof(cf), packed = payload ? (size_t)n_ref * (size_t)row_bytes_of(m->k, n_sym) : 0;
-    const size_t ws_bytes = (size_t)gfdm_hip_link_meter_measure_workspace_bytes(n_sym, n_rows);
-    DevBuf d_sym, d_ws, d_args, d_pay;
-    GFDM_TRY(d_sym.alloc(sym_bytes));
-    GFDM_TRY(d_ws.alloc(ws_bytes));
-    GFDM_TRY(d_pay.alloc(packed));
-    GFDM_TRY(d_args.alloc((nr + 1) * sizeof(int64_t) + 3 * nr * sizeof(float)));
-    int64_t* d_ref = d_args.take<int64_t>(nr);
-    int64_t* d_count = d_args.take<int64_t>(1);
-    int32_t* d_be = d_args.take<int32_t>(nr);
-    float* d_ep = d_args.take<float>(nr);
-    float* d_rp = d_args.take<float>(nr);
-    hipStream_t s = m->ctx.stream;
-    GFDM_TRY(gfdm::upload(d_sym.p, symbols, sym_bytes, s));
-    GFDM_TRY(gfdm::upload(d_pay.p, payload, packed, s));
-    GFDM_TRY(gfdm::upload(d_ref, ref_row, nr * sizeof(int64_t), s));
-    GFDM_TRY(gfdm::upload(d_count, count, sizeof(int64_t), s));
-    const int rc = measure_enqueue(m, bit_errors ? d_be : nullptr, err_power ? d_ep : nullptr, ref_power ? d_rp : nullptr, d_sym.p, payload ? d_pay.p : nullptr, n_ref,
-                                   ref_row ? d_ref : nullptr, count ? d_count : nullptr, n_sym, n_rows, d_ws.p, s);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(bit_errors, d_be, nr * sizeof(int32_t), s));
-    GFDM_TRY(gfdm::download(err_power, d_ep, nr * sizeof(float), s));
-    GFDM_TRY(gfdm::download(ref_power, d_rp, nr * sizeof(float), s));
-    GFDM_TRY(hipStreamSynchronize(s));
-    return GFDM_HIP_OK;
+    const size_t nr = (size_t)n_rows;
+    gfdm::HostCall hc(m->ctx);
+    const auto sym = hc.in(symbols, nr * (size_t)n_sym * 2);
+    const auto pay = hc.in(payload, (size_t)n_ref * (size_t)row_bytes_of(m->c.k, n_sym));
+    const auto ref = hc.in(ref_row, nr);
+    const auto cnt = hc.in(count, 1);
+    const auto be = hc.out(bit_errors, nr);
+    const auto ep = hc.out(err_power, nr);
+    const auto rp = hc.out(ref_power, nr);
+    const auto ws = hc.scratch<unsigned char>((size_t)gfdm_hip_link_meter_measure_workspace_bytes(n_sym, n_rows));
+    return hc.run([&](hipStream_t s) {
+        return measure_enqueue(m, be.dev(), ep.dev(), rp.dev(), sym.dev(), pay.dev(), n_ref, ref.dev(), cnt.dev(), n_sym, n_rows, ws.dev(), s);
+    });
 }
 
 }  // extern "C"

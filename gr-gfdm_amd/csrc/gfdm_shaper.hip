@@ -18,6 +18,7 @@
 // (plain stores: nothing to zero between calls or graph replays), k_shaper_gain folds them into the gain.  A maximum is exact and
 // independent of order.
 #include "../../include/gfdm_hip.h"
+#include "gfdm_decide.h"
 #include "gfdm_hostcall.h"
 #include "gfdm_sc16out.h"
 
@@ -25,13 +26,12 @@
 #include <climits>
 #include <cmath>
 #include <cstdio>
-#include <new>
 #include <vector>
 
 using gfdm::cf;
 using gfdm::api_fail;
-using gfdm::DeviceGuard;
-using gfdm::DevBuf;
+using gfdm::live_rows;
+using gfdm::misaligned;
 using gfdm::pack_sc16;          // the sc16 output rule: gfdm_sc16out.h
 
 namespace {
@@ -55,12 +55,6 @@ struct ShapeArgs {
     float sr, si;            // scale
     const float* gain;       // sc16, normalised: the gain k_shaper_gain left (device); NULL = 1
 };
-
-__device__ __forceinline__ int64_t live_bursts(const ShapeArgs& a)
-{
-    if (!a.count) return a.n_bursts;
-    return std::min(std::max(*a.count, (int64_t)0), a.n_bursts);
-}
 
 __device__ __forceinline__ int64_t start_of(const ShapeArgs& a, int64_t b) { return a.starts ? a.starts[b] : a.first + b * a.stride; }
 
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(kLanes) void k_shaper_place(ShapeArgs a, void* __re
     constexpr int VPS = SC16 ? 4 : 2;            // samples per 16-byte vector
     constexpr int SB = 16 / VPS;                 // bytes per sample
     __shared__ int64_t win[kLanes];
-    const int64_t n_live = live_bursts(a);
+    const int64_t n_live = live_rows(a.count, a.n_bursts);
     const float g = a.gain ? *a.gain : 1.f;
     const int mis = (int)(((uintptr_t)out / SB) % VPS);        // samples between the 16-byte boundary in front of `out` and `out`
     const int64_t nvec = (a.out_len + mis + VPS - 1) / VPS;
@@ -209,7 +203,7 @@ __global__ __launch_bounds__(kLanes) void k_shaper_place(ShapeArgs a, void* __re
 __global__ __launch_bounds__(kLanes) void k_shaper_peak(ShapeArgs a, float* __restrict__ part)
 {
     __shared__ float wmax[kLanes / 32];
-    const int64_t total = live_bursts(a) * a.F;
+    const int64_t total = live_rows(a.count, a.n_bursts) * a.F;
     float m = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x; i < total; i += (int64_t)gridDim.x * kLanes) {
         const cf y = scaled(a, a.frames[i]);
@@ -297,10 +291,10 @@ int shaper_enqueue(gfdm_hip_burst_shaper* h, int sc16, void* out, const cf* fram
                    hipStream_t s)
 {
     if (l.out_len == 0) return GFDM_HIP_OK;
-    if (((uintptr_t)out % (sc16 ? 4 : 8)) || ((uintptr_t)frames % 8)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
+    if (misaligned(out, sc16 ? 4 : 8) || misaligned(frames, 8)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
     ShapeArgs a = { frames, h->F, n_bursts, l.count, l.starts, l.first, l.stride, l.out_len, h->sr, h->si, nullptr };
     if (sc16 && peak > 0.0) {
-        if (!workspace || ((uintptr_t)workspace % 16)) return api_fail(GFDM_HIP_EINVAL, "normalised sc16 output needs a 16-byte aligned workspace");
+        if (!workspace || misaligned(workspace, 16)) return api_fail(GFDM_HIP_EINVAL, "normalised sc16 output needs a 16-byte aligned workspace");
         float* res = static_cast<float*>(workspace);
         float* part = res + 4;
         const int64_t per = (int64_t)kLanes * kPeakPer;
@@ -325,9 +319,9 @@ int shaper_device(gfdm_hip_burst_shaper* h, int sc16, void* out, const void* fra
 {
     const int rc = check_call(h, out, frames, l, placed, peak, n_bursts);
     if (rc != GFDM_HIP_OK) return rc;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return shaper_enqueue(h, sc16, out, static_cast<const cf*>(frames), l, n_bursts, peak, workspace, (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
+        return shaper_enqueue(h, sc16, out, static_cast<const cf*>(frames), l, n_bursts, peak, workspace, s);
+    });
 }
 
 // what the host flavour of place can see of the live starts (include/gfdm_hip.h)
@@ -355,31 +349,22 @@ int shaper_host(gfdm_hip_burst_shaper* h, int sc16, void* out, const float* fram
     int rc = check_call(h, out, frames, l, placed, peak, n_bursts);
     if (rc != GFDM_HIP_OK) return rc;
     if (placed) {
-        const int64_t n_live = l.count ? std::min(std::max(*l.count, (int64_t)0), n_bursts) : n_bursts;
-        rc = check_starts(h, l.starts, n_live, l.out_len);
+        rc = check_starts(h, l.starts, live_rows(l.count, n_bursts), l.out_len);
         if (rc != GFDM_HIP_OK) return rc;
     }
     if (l.out_len == 0) return GFDM_HIP_OK;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t n = (size_t)n_bursts, fbytes = n * h->F * sizeof(cf), obytes = (size_t)l.out_len * (sc16 ? 2 * sizeof(int16_t) : sizeof(cf));
-    DevBuf d_frames, d_args, d_ws, d_out;
-    GFDM_TRY(d_frames.alloc(fbytes));
-    GFDM_TRY(d_args.alloc((n + 1) * sizeof(int64_t)));
-    GFDM_TRY(d_ws.alloc(kWorkspaceBytes));
-    GFDM_TRY(d_out.alloc(obytes));
-    int64_t* d_count = d_args.take<int64_t>(1);
-    int64_t* d_starts = d_args.take<int64_t>(n);
-    GFDM_TRY(gfdm::upload(d_frames.p, frames, fbytes, h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_count, l.count, sizeof(int64_t), h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_starts, l.starts, n * sizeof(int64_t), h->ctx.stream));
-    if (l.count) l.count = d_count;
-    if (l.starts) l.starts = d_starts;
-    rc = shaper_enqueue(h, sc16, d_out.p, d_frames.as<const cf>(), l, n_bursts, peak, d_ws.p, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(out, d_out.p, obytes, h->ctx.stream));
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    const size_t n = (size_t)n_bursts;
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(reinterpret_cast<const cf*>(frames), n * h->F);
+    const auto cnt = hc.in(l.count, 1);
+    const auto st = hc.in(l.starts, n);
+    const auto ws = hc.scratch<unsigned char>(kWorkspaceBytes);
+    const auto y = hc.out(static_cast<unsigned char*>(out), (size_t)l.out_len * (sc16 ? 2 * sizeof(int16_t) : sizeof(cf)));
+    return hc.run([&](hipStream_t s) {
+        l.count = cnt.dev();
+        l.starts = st.dev();
+        return shaper_enqueue(h, sc16, y.dev(), x.dev(), l, n_bursts, peak, ws.dev(), s);
+    });
 }
 
 }  // namespace
@@ -388,24 +373,14 @@ extern "C" {
 
 int gfdm_hip_burst_shaper_create(gfdm_hip_burst_shaper** out, int frame_len, int pre_padding, int post_padding, float scale_re, float scale_im, int device)
 {
-    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
-    *out = nullptr;
-    const int rc0 = shaper_check(frame_len, pre_padding, post_padding, 0.0, 0, 0);
-    if (rc0 != GFDM_HIP_OK) return rc0;
-    gfdm_hip_burst_shaper* h = new (std::nothrow) gfdm_hip_burst_shaper();
-    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->F = frame_len;
-    h->pre = pre_padding;
-    h->post = post_padding;
-    h->sr = scale_re;
-    h->si = scale_im;
-    const int rc = h->ctx.open(device);
-    if (rc != GFDM_HIP_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return GFDM_HIP_OK;
+    return gfdm::create_handle(out, device, [&](gfdm_hip_burst_shaper& h) {
+        h.F = frame_len;
+        h.pre = pre_padding;
+        h.post = post_padding;
+        h.sr = scale_re;
+        h.si = scale_im;
+        return shaper_check(frame_len, pre_padding, post_padding, 0.0, 0, 0);
+    });
 }
 
 int gfdm_hip_burst_shaper_destroy(gfdm_hip_burst_shaper* h) { delete h; return GFDM_HIP_OK; }

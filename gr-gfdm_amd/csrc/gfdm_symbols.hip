@@ -21,7 +21,6 @@
 
 #include <algorithm>
 #include <climits>
-#include <new>
 
 using gfdm::cf;
 using gfdm::RowPos;
@@ -29,8 +28,10 @@ using gfdm::advance;
 using gfdm::dist2;
 using gfdm::decide2;                 // gfdm_decide.h: shared with the link meter
 using gfdm::api_fail;
-using gfdm::DeviceGuard;
-using gfdm::DevBuf;
+using gfdm::bits_of;
+using gfdm::row_bytes_of;
+using gfdm::live_rows;
+using gfdm::misaligned;
 
 namespace {
 
@@ -48,12 +49,6 @@ struct MapperArgs {
     const int64_t* count;    // optional (device): live rows = clamp(*count, 0, n_rows)
     const float* scale;      // soft, optional (device): [n_rows]
 };
-
-__device__ __forceinline__ int64_t live_rows(const MapperArgs& a)
-{
-    if (!a.count) return a.n_rows;
-    return std::min(std::max(*a.count, (int64_t)0), a.n_rows);
-}
 
 // the 16-byte vector v of the symbol array (symbols 2 v - mis, 2 v - mis + 1 of the flat input; those outside [0, s_end) read as 0)
 __device__ __forceinline__ void load_pair(const cf* __restrict__ in, int64_t s, int64_t s_end, cf& x0, cf& x1)
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(kLanes) void k_symbols_decode(MapperArgs a, const c
     __shared__ cf pts[TABLE ? (1 << K) : 1];
     __shared__ unsigned char idx[kDecodeSlots];
     if constexpr (TABLE) load_points<K>(pts, a);
-    const int64_t n_live = live_rows(a), rb = a.row_bytes;
+    const int64_t n_live = live_rows(a.count, a.n_rows), rb = a.row_bytes;
     const int64_t total = a.n_rows * rb, live_bytes = n_live * rb, s_live = n_live * a.n_sym;
     const int mis = (int)(((uintptr_t)in / sizeof(cf)) & 1);                 // symbols between the 16-byte boundary in front of `in` and `in`
     const int64_t ntiles = (total + kTileBytes - 1) / kTileBytes;
@@ -175,7 +170,7 @@ __global__ __launch_bounds__(kLanes) void k_symbols_soft(MapperArgs a, const cf*
     __shared__ cf pts[1 << K];
     __shared__ float llr[kSoftSlots];
     load_points<K>(pts, a);
-    const int64_t n_live = live_rows(a);
+    const int64_t n_live = live_rows(a.count, a.n_rows);
     const int64_t total = a.n_rows * a.n_sym * K, s_live = n_live * a.n_sym, live_f = s_live * K;
     const int mis = (int)(((uintptr_t)in / sizeof(cf)) & 1);
     const int omis = (int)(((uintptr_t)out / sizeof(float)) & 3);            // floats between the 16-byte boundary in front of `out` and `out`
@@ -237,7 +232,7 @@ __global__ __launch_bounds__(kLanes) void k_symbols_map(MapperArgs a, const unsi
     __shared__ uint2 pts[1 << K];                    // moved as bits: a point goes out as it came in
     for (int i = threadIdx.x; i < (1 << K); i += kLanes) pts[i] = reinterpret_cast<const uint2*>(a.points)[i];
     __syncthreads();
-    const int64_t n_live = live_rows(a);
+    const int64_t n_live = live_rows(a.count, a.n_rows);
     const int64_t total = a.n_rows * a.n_sym, s_live = n_live * a.n_sym;
     const int mis = (int)(((uintptr_t)out / sizeof(cf)) & 1);
     const int64_t nvec = (total + mis + 1) / 2;
@@ -278,13 +273,6 @@ __global__ __launch_bounds__(kLanes) void k_symbols_map(MapperArgs a, const unsi
     }
 }
 
-int bits_of(int n_points)
-{
-    for (int k = 1; k <= 8; ++k)
-        if (n_points == (1 << k)) return k;
-    return 0;
-}
-
 // the argument table (include/gfdm_hip.h); needs no handle, so it is checked before any device is touched
 int mapper_check(int n_points, int64_t n_sym, int64_t n_rows)
 {
@@ -302,21 +290,18 @@ int mapper_check(int n_points, int64_t n_sym, int64_t n_rows)
 
 struct gfdm_hip_symbol_mapper {
     gfdm::DeviceCtx ctx;
-    int k = 0, rule = GFDM_HIP_DECIDE_NEAREST;
-    cf points[256];
-    cf* d_points = nullptr;
+    gfdm::Constellation c;
     ~gfdm_hip_symbol_mapper()
     {
-        DeviceGuard guard(ctx.device);
-        if (d_points) (void)hipFree(d_points);
+        if (!c.d_points) return;
+        gfdm::DeviceGuard guard(ctx.device);
+        (void)hipFree(c.d_points);
     }
 };
 
 namespace {
 
 enum Op { OP_MAP, OP_DECODE, OP_SOFT };
-
-int64_t row_bytes_of(int k, int64_t n_sym) { return (n_sym * k + 7) / 8; }
 
 unsigned grid_for(int64_t ntiles) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, kMaxTiles)); }
 
@@ -334,9 +319,9 @@ void launch_k(const gfdm_hip_symbol_mapper* h, Op op, const MapperArgs& a, void*
         const dim3 grid(grid_for((a.n_rows * a.row_bytes + kLanes * K - 1) / (kLanes * K)));
         const cf* x = static_cast<const cf*>(in);
         unsigned char* y = static_cast<unsigned char*>(out);
-        if (K == 2 && h->rule == GFDM_HIP_DECIDE_QPSK) hipLaunchKernelGGL((k_symbols_decode<2, GFDM_HIP_DECIDE_QPSK>), grid, block, 0, s, a, x, y);
-        else if (K == 1 && h->rule == GFDM_HIP_DECIDE_BPSK) hipLaunchKernelGGL((k_symbols_decode<1, GFDM_HIP_DECIDE_BPSK>), grid, block, 0, s, a, x, y);
-        else hipLaunchKernelGGL((k_symbols_decode<K, GFDM_HIP_DECIDE_NEAREST>), grid, block, 0, s, a, x, y);
+        gfdm::with_rule<K>(h->c.rule, [&](auto k, auto rule) {
+            hipLaunchKernelGGL((k_symbols_decode<decltype(k)::value, decltype(rule)::value>), grid, block, 0, s, a, x, y);
+        });
     }
 }
 
@@ -346,20 +331,10 @@ int mapper_enqueue(const gfdm_hip_symbol_mapper* h, Op op, void* out, const void
 {
     if (n_rows == 0) return GFDM_HIP_OK;
     const void* syms = op == OP_MAP ? out : in;
-    if (((uintptr_t)syms % sizeof(cf)) || (op == OP_SOFT && (((uintptr_t)out % sizeof(float)) || ((uintptr_t)scale % sizeof(float)))) ||
-        ((uintptr_t)count % sizeof(int64_t)))
+    if (misaligned(syms, sizeof(cf)) || (op == OP_SOFT && (misaligned(out, sizeof(float)) || misaligned(scale, sizeof(float)))) || misaligned(count, sizeof(int64_t)))
         return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one element");
-    const MapperArgs a = { h->d_points, n_sym, n_rows, row_bytes_of(h->k, n_sym), static_cast<const int64_t*>(count), static_cast<const float*>(scale) };
-    switch (h->k) {
-    case 1: launch_k<1>(h, op, a, out, in, s); break;
-    case 2: launch_k<2>(h, op, a, out, in, s); break;
-    case 3: launch_k<3>(h, op, a, out, in, s); break;
-    case 4: launch_k<4>(h, op, a, out, in, s); break;
-    case 5: launch_k<5>(h, op, a, out, in, s); break;
-    case 6: launch_k<6>(h, op, a, out, in, s); break;
-    case 7: launch_k<7>(h, op, a, out, in, s); break;
-    default: launch_k<8>(h, op, a, out, in, s); break;
-    }
+    const MapperArgs a = { h->c.d_points, n_sym, n_rows, row_bytes_of(h->c.k, n_sym), static_cast<const int64_t*>(count), static_cast<const float*>(scale) };
+    gfdm::dispatch_bits(h->c.k, [&](auto k) { launch_k<decltype(k)::value>(h, op, a, out, in, s); });
     GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
@@ -367,7 +342,7 @@ int mapper_enqueue(const gfdm_hip_symbol_mapper* h, Op op, void* out, const void
 int check_call(const gfdm_hip_symbol_mapper* h, const void* out, const void* in, int64_t n_sym, int64_t n_rows)
 {
     if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
-    const int rc = mapper_check(1 << h->k, n_sym, n_rows);
+    const int rc = mapper_check(1 << h->c.k, n_sym, n_rows);
     if (rc != GFDM_HIP_OK) return rc;
     if (n_rows > 0 && (!out || !in)) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
     return GFDM_HIP_OK;
@@ -377,9 +352,7 @@ int mapper_device(gfdm_hip_symbol_mapper* h, Op op, void* out, const void* in, c
 {
     const int rc = check_call(h, out, in, n_sym, n_rows);
     if (rc != GFDM_HIP_OK) return rc;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    return mapper_enqueue(h, op, out, in, scale, count, n_sym, n_rows, (hipStream_t)stream);
+    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) { return mapper_enqueue(h, op, out, in, scale, count, n_sym, n_rows, s); });
 }
 
 // upload the rows (and the scale and the count), one enqueue on the handle's stream, download the result
@@ -388,25 +361,14 @@ int mapper_host(gfdm_hip_symbol_mapper* h, Op op, void* out, const void* in, con
     const int rc0 = check_call(h, out, in, n_sym, n_rows);
     if (rc0 != GFDM_HIP_OK) return rc0;
     if (n_rows == 0) return GFDM_HIP_OK;
-    DeviceGuard guard(h->ctx.device);
-    if (!guard.ok) return api_fail(GFDM_HIP_ENODEV, "hipSetDevice failed");
-    const size_t n = (size_t)n_rows, sym_bytes = n * (size_t)n_sym * sizeof(cf), packed = n * (size_t)row_bytes_of(h->k, n_sym),
-                 llr_bytes = n * (size_t)n_sym * h->k * sizeof(float);
-    const size_t ibytes = op == OP_MAP ? packed : sym_bytes, obytes = op == OP_MAP ? sym_bytes : op == OP_DECODE ? packed : llr_bytes;
-    DevBuf d_in, d_args, d_out;
-    GFDM_TRY(d_in.alloc(ibytes));
-    GFDM_TRY(d_args.alloc(sizeof(int64_t) + n * sizeof(float)));
-    GFDM_TRY(d_out.alloc(obytes));
-    int64_t* d_count = d_args.take<int64_t>(1);
-    float* d_scale = d_args.take<float>(n);
-    GFDM_TRY(gfdm::upload(d_in.p, in, ibytes, h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_count, count, sizeof(int64_t), h->ctx.stream));
-    GFDM_TRY(gfdm::upload(d_scale, scale, n * sizeof(float), h->ctx.stream));
-    const int rc = mapper_enqueue(h, op, d_out.p, d_in.p, scale ? d_scale : nullptr, count ? d_count : nullptr, n_sym, n_rows, h->ctx.stream);
-    if (rc != GFDM_HIP_OK) return rc;
-    GFDM_TRY(gfdm::download(out, d_out.p, obytes, h->ctx.stream));
-    GFDM_TRY(hipStreamSynchronize(h->ctx.stream));
-    return GFDM_HIP_OK;
+    const size_t n = (size_t)n_rows, sym_bytes = n * (size_t)n_sym * sizeof(cf), packed = n * (size_t)row_bytes_of(h->c.k, n_sym),
+                 llr_bytes = n * (size_t)n_sym * h->c.k * sizeof(float);
+    gfdm::HostCall hc(h->ctx);
+    const auto x = hc.in(static_cast<const unsigned char*>(in), op == OP_MAP ? packed : sym_bytes);
+    const auto cnt = hc.in(count, 1);
+    const auto sc = hc.in(scale, n);
+    const auto y = hc.out(static_cast<unsigned char*>(out), op == OP_MAP ? sym_bytes : op == OP_DECODE ? packed : llr_bytes);
+    return hc.run([&](hipStream_t s) { return mapper_enqueue(h, op, y.dev(), x.dev(), sc.dev(), cnt.dev(), n_sym, n_rows, s); });
 }
 
 }  // namespace
@@ -415,49 +377,26 @@ extern "C" {
 
 int gfdm_hip_symbol_mapper_create(gfdm_hip_symbol_mapper** out, const float* points, int n_points, int decision, int device)
 {
-    if (!out) return api_fail(GFDM_HIP_EINVAL, "NULL handle pointer");
-    *out = nullptr;
-    const int rc0 = mapper_check(n_points, 1, 0);
-    if (rc0 != GFDM_HIP_OK) return rc0;
-    if (!points) return api_fail(GFDM_HIP_EINVAL, "NULL constellation points");
-    if (decision < GFDM_HIP_DECIDE_AUTO || decision > GFDM_HIP_DECIDE_BPSK) return api_fail(GFDM_HIP_EINVAL, "bad decision rule");
-    const int rule = gfdm::resolve_decision(reinterpret_cast<const cf*>(points), n_points, decision);
-    if (rule < 0) return api_fail(GFDM_HIP_EINVAL, "decision rule does not match the number of constellation points");
-    gfdm_hip_symbol_mapper* h = new (std::nothrow) gfdm_hip_symbol_mapper();
-    if (!h) return api_fail(GFDM_HIP_ENOMEM, "out of host memory");
-    h->k = bits_of(n_points);
-    h->rule = rule;
-    std::copy(reinterpret_cast<const cf*>(points), reinterpret_cast<const cf*>(points) + n_points, h->points);
-    int rc = h->ctx.open(device);
-    if (rc == GFDM_HIP_OK) {
-        DeviceGuard guard(device);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_points), (size_t)n_points * sizeof(cf));
-        if (e == hipSuccess) e = hipMemcpy(h->d_points, h->points, (size_t)n_points * sizeof(cf), hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = gfdm::api_fail_hip(e, "constellation upload");
-    }
-    if (rc != GFDM_HIP_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return GFDM_HIP_OK;
+    return gfdm::create_handle(
+        out, device, [&](gfdm_hip_symbol_mapper& h) { return h.c.set(points, n_points, decision); },
+        [](gfdm_hip_symbol_mapper& h) { return h.c.upload(); });
 }
 
 int gfdm_hip_symbol_mapper_destroy(gfdm_hip_symbol_mapper* m) { delete m; return GFDM_HIP_OK; }
-int gfdm_hip_symbol_mapper_bits_per_symbol(const gfdm_hip_symbol_mapper* m) { return m ? m->k : GFDM_HIP_EINVAL; }
-int gfdm_hip_symbol_mapper_n_points(const gfdm_hip_symbol_mapper* m) { return m ? 1 << m->k : GFDM_HIP_EINVAL; }
-int gfdm_hip_symbol_mapper_decision(const gfdm_hip_symbol_mapper* m) { return m ? m->rule : GFDM_HIP_EINVAL; }
+int gfdm_hip_symbol_mapper_bits_per_symbol(const gfdm_hip_symbol_mapper* m) { return m ? m->c.k : GFDM_HIP_EINVAL; }
+int gfdm_hip_symbol_mapper_n_points(const gfdm_hip_symbol_mapper* m) { return m ? 1 << m->c.k : GFDM_HIP_EINVAL; }
+int gfdm_hip_symbol_mapper_decision(const gfdm_hip_symbol_mapper* m) { return m ? m->c.rule : GFDM_HIP_EINVAL; }
 int gfdm_hip_symbol_mapper_points(const gfdm_hip_symbol_mapper* m, float* points)
 {
     if (!m || !points) return api_fail(GFDM_HIP_EINVAL, "NULL handle or output");
-    std::copy(m->points, m->points + (1 << m->k), reinterpret_cast<cf*>(points));
+    std::copy(m->c.points, m->c.points + (1 << m->c.k), reinterpret_cast<cf*>(points));
     return GFDM_HIP_OK;
 }
 int64_t gfdm_hip_symbol_mapper_row_bytes(const gfdm_hip_symbol_mapper* m, int64_t n_sym)
 {
     if (!m) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
-    const int rc = mapper_check(1 << m->k, n_sym, 0);
-    return rc != GFDM_HIP_OK ? rc : row_bytes_of(m->k, n_sym);
+    const int rc = mapper_check(1 << m->c.k, n_sym, 0);
+    return rc != GFDM_HIP_OK ? rc : row_bytes_of(m->c.k, n_sym);
 }
 int gfdm_hip_symbol_mapper_check(int n_points, int64_t n_sym, int64_t n_rows) { return mapper_check(n_points, n_sym, n_rows); }
 

@@ -135,6 +135,8 @@ long live_allocations();
 void set_device_count(int n);
 // hipPointerGetAttributes on memory the layer has never seen: true = hipErrorInvalidValue (ROCm <= 5), false (default) = hipSuccess + hipMemoryTypeUnregistered
 void set_unknown_pointer_is_error(bool on);
+// how many hip* runtime calls the process has made so far, of any kind (hipGetLastError, hipGetDevice and hipSetDevice included)
+long runtime_calls();
 }  // namespace loopback
 
 static inline void __threadfence_system() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }

@@ -82,6 +82,7 @@ struct State {
     std::atomic<long> launches{ 0 }, async_copies{ 0 }, streams_created{ 0 }, streams_destroyed{ 0 }, host_allocs{ 0 }, host_frees{ 0 }, dev_allocs{ 0 },
         dev_frees{ 0 }, registers{ 0 }, unregisters{ 0 }, modules_loaded{ 0 }, compiles{ 0 };
     std::atomic<int> compile_lo{ 2 }, compile_hi{ 20 };
+    std::atomic<long> runtime_calls{ 0 };                // every hip* entry of this layer, whatever it then does
 };
 State& S()
 {
@@ -89,6 +90,7 @@ State& S()
     return *s;
 }
 
+#define LB_CALL() S().runtime_calls.fetch_add(1, std::memory_order_relaxed)
 thread_local int t_device = 0;
 thread_local hipError_t t_last = hipSuccess;
 
@@ -206,6 +208,7 @@ void set_device_count(int n) { S().ndev.store(n); }
 void set_unknown_pointer_is_error(bool on) { S().unknown_is_error.store(on); }
 void set_compile_ms(int lo, int hi) { S().compile_lo.store(lo); S().compile_hi.store(hi < lo ? lo : hi); }
 long compiles() { return S().compiles.load(); }
+long runtime_calls() { return S().runtime_calls.load(); }
 
 }  // namespace loopback
 
@@ -231,6 +234,7 @@ const char* hipGetErrorString(hipError_t e)
 
 hipError_t hipGetLastError(void)
 {
+    LB_CALL();
     const hipError_t e = t_last;
     t_last = hipSuccess;
     return e;
@@ -238,13 +242,15 @@ hipError_t hipGetLastError(void)
 
 hipError_t hipGetDeviceCount(int* n)
 {
+    LB_CALL();
     LB_INJECT("hipGetDeviceCount");
     *n = S().ndev.load();
     return hipSuccess;
 }
-hipError_t hipGetDevice(int* d) { *d = t_device; return hipSuccess; }
+hipError_t hipGetDevice(int* d) { LB_CALL(); *d = t_device; return hipSuccess; }
 hipError_t hipSetDevice(int d)
 {
+    LB_CALL();
     LB_INJECT("hipSetDevice");
     if (d < 0 || d >= S().ndev.load()) return ret(hipErrorInvalidDevice);
     t_device = d;
@@ -253,10 +259,11 @@ hipError_t hipSetDevice(int d)
 
 hipError_t hipMalloc(void** p, size_t bytes)
 {
+    LB_CALL();
     *p = nullptr;
     LB_INJECT("hipMalloc");
-    void* m = malloc(bytes ? bytes : 1);
-    if (!m) return ret(hipErrorOutOfMemory);
+    void* m = nullptr;                               // 256-byte aligned, as hipMalloc's results are; the size stays exact for AddressSanitizer
+    if (posix_memalign(&m, 256, bytes ? bytes : 1) != 0) return ret(hipErrorOutOfMemory);
     memset(m, 0xD5, bytes);                          // device memory is not zero-initialised: poison it
     State& s = S();
     std::lock_guard<std::mutex> lk(s.mem_m);
@@ -268,6 +275,7 @@ hipError_t hipMalloc(void** p, size_t bytes)
 
 hipError_t hipFree(void* p)
 {
+    LB_CALL();
     if (!p) return hipSuccess;
     State& s = S();
     int device;
@@ -289,6 +297,7 @@ hipError_t hipFree(void* p)
 
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned)
 {
+    LB_CALL();
     *p = nullptr;
     LB_INJECT("hipHostMalloc");
     void* m = nullptr;
@@ -304,6 +313,7 @@ hipError_t hipHostMalloc(void** p, size_t bytes, unsigned)
 
 hipError_t hipHostFree(void* p)
 {
+    LB_CALL();
     if (!p) return hipSuccess;
     State& s = S();
     {
@@ -319,6 +329,7 @@ hipError_t hipHostFree(void* p)
 
 hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned)
 {
+    LB_CALL();
     LB_INJECT("hipHostGetDevicePointer");
     State& s = S();
     std::lock_guard<std::mutex> lk(s.mem_m);
@@ -330,6 +341,7 @@ hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned)
 
 hipError_t hipHostRegister(void* p, size_t bytes, unsigned)
 {
+    LB_CALL();
     LB_INJECT("hipHostRegister");
     if (!p || !bytes) return ret(hipErrorInvalidValue);
     State& s = S();
@@ -345,6 +357,7 @@ hipError_t hipHostRegister(void* p, size_t bytes, unsigned)
 
 hipError_t hipHostUnregister(void* p)
 {
+    LB_CALL();
     LB_INJECT("hipHostUnregister");
     State& s = S();
     std::lock_guard<std::mutex> lk(s.mem_m);
@@ -357,6 +370,7 @@ hipError_t hipHostUnregister(void* p)
 
 hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* p)
 {
+    LB_CALL();
     memset(a, 0, sizeof *a);
     LB_INJECT("hipPointerGetAttributes");
     State& s = S();
@@ -376,6 +390,7 @@ hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* p)
 
 hipError_t hipMemGetAddressRange(hipDeviceptr_t* base, size_t* size, hipDeviceptr_t p)
 {
+    LB_CALL();
     LB_INJECT("hipMemGetAddressRange");
     State& s = S();
     std::lock_guard<std::mutex> lk(s.mem_m);
@@ -388,6 +403,7 @@ hipError_t hipMemGetAddressRange(hipDeviceptr_t* base, size_t* size, hipDevicept
 
 hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind)
 {
+    LB_CALL();
     LB_INJECT("hipMemcpy");
     memcpy(dst, src, bytes);
     return hipSuccess;
@@ -395,6 +411,7 @@ hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind)
 
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t s)
 {
+    LB_CALL();
     LB_INJECT("hipMemcpyAsync");
     S().async_copies.fetch_add(1, std::memory_order_relaxed);
     loopback_stream* st = resolve(s);
@@ -409,6 +426,7 @@ hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKin
 
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned)
 {
+    LB_CALL();
     *s = nullptr;
     LB_INJECT("hipStreamCreateWithFlags");
     loopback_stream* st = new_stream(t_device);
@@ -424,6 +442,7 @@ hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned)
 
 hipError_t hipStreamDestroy(hipStream_t s)
 {
+    LB_CALL();
     if (!s) return ret(hipErrorInvalidValue);
     State& g = S();
     {
@@ -442,6 +461,7 @@ hipError_t hipStreamDestroy(hipStream_t s)
 
 hipError_t hipStreamSynchronize(hipStream_t s)
 {
+    LB_CALL();
     LB_INJECT("hipStreamSynchronize");
     stream_sync(resolve(s));
     return hipSuccess;
@@ -449,6 +469,7 @@ hipError_t hipStreamSynchronize(hipStream_t s)
 
 hipError_t hipStreamQuery(hipStream_t s)
 {
+    LB_CALL();
     LB_INJECT("hipStreamQuery");
     loopback_stream* st = resolve(s);
     std::lock_guard<std::mutex> lk(st->m);
@@ -457,6 +478,7 @@ hipError_t hipStreamQuery(hipStream_t s)
 
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned)
 {
+    LB_CALL();
     *e = nullptr;
     LB_INJECT("hipEventCreateWithFlags");
     *e = new loopback_event();
@@ -465,6 +487,7 @@ hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned)
 
 hipError_t hipEventDestroy(hipEvent_t e)
 {
+    LB_CALL();
     if (!e) return ret(hipErrorInvalidValue);
     delete e;                                        // queued records / waits keep the state alive (shared_ptr), as HIP does for a busy event
     return hipSuccess;
@@ -472,6 +495,7 @@ hipError_t hipEventDestroy(hipEvent_t e)
 
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
 {
+    LB_CALL();
     LB_INJECT("hipEventRecord");
     if (!e) return ret(hipErrorInvalidValue);
     std::shared_ptr<loopback_event_state> st = e->st;
@@ -498,6 +522,7 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
 
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned)
 {
+    LB_CALL();
     LB_INJECT("hipStreamWaitEvent");
     if (!e) return ret(hipErrorInvalidValue);
     std::shared_ptr<loopback_event_state> st = e->st;
@@ -522,6 +547,7 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned)
 
 hipError_t hipDeviceSynchronize(void)
 {
+    LB_CALL();
     device_sync(t_device);
     return hipSuccess;
 }
@@ -531,6 +557,7 @@ static const char kMagic[] = "LOOPBACK-HSACO ";
 
 hipError_t hipModuleLoadData(hipModule_t* m, const void* image)
 {
+    LB_CALL();
     *m = nullptr;
     LB_INJECT("hipModuleLoadData");
     const char* c = static_cast<const char*>(image);
@@ -554,12 +581,14 @@ hipError_t hipModuleLoadData(hipModule_t* m, const void* image)
 
 hipError_t hipModuleUnload(hipModule_t m)
 {
+    LB_CALL();
     delete m;
     return hipSuccess;
 }
 
 hipError_t hipModuleGetFunction(hipFunction_t* f, hipModule_t m, const char* name)
 {
+    LB_CALL();
     *f = nullptr;
     LB_INJECT("hipModuleGetFunction");
     for (const auto& n : m->names)
@@ -573,11 +602,12 @@ hipError_t hipModuleGetFunction(hipFunction_t* f, hipModule_t m, const char* nam
 
 hipError_t hipModuleLaunchKernel(hipFunction_t f, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t s, void** args, void**)
 {
+    LB_CALL();
     if (!f) return ret(hipErrorInvalidValue);
     return ret(loopback::module_launch(f->name, args, s));
 }
 
-hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { LB_CALL(); return hipSuccess; }
 
 }  // extern "C"
 

@@ -319,6 +319,13 @@ def test_host_flavour_equals_device_flavour_and_calls_repeat():
         assert np.array_equal(coded_h, _h(cc.encode(_t(data), n_info, out_row_bytes=coded_h.shape[1])))
         assert np.array_equal(cc.decode_hard(coded_h, n_info), V.clean(data, n_info))
         assert np.array_equal(cc.decode(llr[0], n_info, 16.0), want[0])
+        # the host flavours with the optional operands the calls above leave out: encode with a count, decode_hard with a count and a path_metric
+        enc_h = cc.encode(data, n_info, count=4)
+        assert isinstance(enc_h, np.ndarray) and np.array_equal(enc_h, _h(cc.encode(_t(data), n_info, count=4))) and enc_h[:4].any() and not enc_h[4:].any()
+        pm_h, pm_d = np.full(n_rows, -1, np.int32), _t(np.full(n_rows, -1, np.int32))
+        hard_h = cc.decode_hard(coded_h, n_info, count=4, path_metric=pm_h)
+        assert np.array_equal(hard_h, _h(cc.decode_hard(_t(coded_h), n_info, count=4, path_metric=pm_d))) and np.array_equal(pm_h, _h(pm_d))
+        assert np.array_equal(hard_h[:4], V.clean(data, n_info)[:4]) and not hard_h[4:].any()
 
 
 def test_graph_of_soft_and_decode_replays_with_a_changed_count():

@@ -356,6 +356,31 @@ def test_host_flavour_equals_device_flavour(meters):
             for key in h:
                 assert isinstance(h[key], np.ndarray) and np.array_equal(h[key].view(np.uint8), _h(d[key]).view(np.uint8)), key
     assert host["bit_errors"].dtype == np.int32 and host["err_power"].dtype == np.float32 and host_m["ref_row"].dtype == np.int64
+    # the raw C calls with single outputs left out (the wrapper always passes both powers and both rows of match): what is asked for equals
+    # the all-outputs call above (count = 5) bit for bit, and so do the totals
+    import gfdm_amd
+    L = gfdm_amd.lib()
+    x, data, cnt = np.ascontiguousarray(c["x"]), np.ascontiguousarray(c["data"]), np.array([5], np.int64)
+    fs, sent = np.ascontiguousarray(fs, np.int64), np.ascontiguousarray(sent, np.int64)
+    lm.reset()
+    lm.measure(c["x"], c["data"], ref_row=ref, count=5)
+    t_measure = lm.totals()
+    lm.reset()
+    lm.match(fs, sent, tol, offset=offset, count=5)
+    t_match = lm.totals()
+    for keep in ("bit_errors", "err_power", "ref_power"):
+        got = np.zeros(7, host[keep].dtype)
+        ptr = {k: got.ctypes.data if k == keep else None for k in ("bit_errors", "err_power", "ref_power")}
+        lm.reset()
+        assert L.gfdm_hip_link_meter_measure_host(lm._h, ptr["bit_errors"], ptr["err_power"], ptr["ref_power"], x.ctypes.data, data.ctypes.data, 7,
+                                                  ref.ctypes.data, cnt.ctypes.data, 4097, 7) == 0
+        assert np.array_equal(got.view(np.uint8), host[keep].view(np.uint8)) and lm.totals() == t_measure, keep
+    for keep in ("ref_row", "sent_row"):
+        got = np.zeros(host_m[keep].size, np.int64)
+        lm.reset()
+        assert L.gfdm_hip_link_meter_match_host(lm._h, got.ctypes.data if keep == "ref_row" else None, got.ctypes.data if keep == "sent_row" else None,
+                                                fs.ctypes.data, cnt.ctypes.data, fs.size, sent.ctypes.data, sent.size, offset, tol) == 0
+        assert np.array_equal(got, host_m[keep]) and lm.totals() == t_match, keep
     assert lm.measure(c["x"][:0], c["data"][:0])["err_power"].shape == (0,)
     with pytest.raises(TypeError):
         lm.measure(_t(c["x"]), c["data"])

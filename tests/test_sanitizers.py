@@ -5,6 +5,8 @@ quiesce, the exit path), csrc/gfdm_hip_api.hip (handles, family pin, every *_hos
 batched_work.h are compiled UNCHANGED as plain C++ against the test-only loop-back HIP layer of tests/sanitize/loopback (streams = worker threads, a launch = a
 host function that copies in -> out) and driven by tests/sanitize/host_fuzz.cc: the call mix of scratch/fuzz_host_path.py on several threads at once, quiesce
 while calls are in flight, every runtime call failing once, the process ending with builds in flight.  Recipe: tests/sanitize/Makefile.
+The staged host call of csrc/gfdm_hostcall.h (gfdm::HostCall: the *_host entry points of the device modules, whose kernels share a file with their
+host code and so cannot be compiled against the loop-back layer) has a small driver of its own, tests/sanitize/hostcall_check.cc, under ASan + UBSan.
 
 Findings of the first runs (fixed in the product): a stale sticky hipGetLastError() of an earlier failed call failing the next launch, hipEvents leaked when
 their creation failed half way, a device operand with an unmapped tail bounced on the CPU instead of refused.
@@ -53,6 +55,31 @@ def test_host_side_is_clean_under_address_and_ub_sanitizer(tmp_path):
     exe = build("asan", tmp_path / "build")
     rc, out = run(exe, 6, 12, ASAN_ENV, tmp_path)
     assert rc == 0 and "host fuzz OK" in out and "Sanitizer" not in out and "runtime error" not in out, out[-6000:]
+
+
+def build_hostcall(out, pkg=None):
+    cmd = ["make", "-C", SAN, "-j4", "hostcall", "OUT=" + str(out)]
+    if pkg:
+        cmd.append("PKG=" + str(pkg))
+    subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    return os.path.join(str(out), "hostcall_check_asan")
+
+
+def run_hostcall(exe, tmp_path):
+    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, **ASAN_ENV), timeout=300, cwd=str(tmp_path))
+    return p.returncode, p.stdout.decode(errors="replace")
+
+
+def test_staged_host_call_is_clean_under_address_and_ub_sanitizer(tmp_path):
+    """gfdm::HostCall (csrc/gfdm_hostcall.h), which every *_host entry point of the device modules goes through, driven by tests/sanitize/hostcall_check.cc:
+    round trip of present, absent and empty operands, piece extents and alignment, every runtime call and the callable failing once, no leak; and
+    gfdm::create_handle: a constructor refused for its arguments makes no runtime call at all, one whose runtime calls fail leaves nothing behind.
+    Sensitivity: with the call's one allocation made 16 bytes short the same program is an AddressSanitizer report."""
+    rc, out = run_hostcall(build_hostcall(tmp_path / "build"), tmp_path)
+    assert rc == 0 and "hostcall check OK" in out and "Sanitizer" not in out and "runtime error" not in out, out[-6000:]
+    pkg = mutated_package(tmp_path, "csrc/gfdm_hostcall.h", "GFDM_TRY(hipMalloc(&base_, size_));", "GFDM_TRY(hipMalloc(&base_, size_ - 16));")
+    rc, out = run_hostcall(build_hostcall(tmp_path / "b2", pkg), tmp_path)
+    assert rc != 0 and "AddressSanitizer: heap-buffer-overflow" in out, out[-3000:]
 
 
 def mutated_package(tmp_path, path, old, new):
