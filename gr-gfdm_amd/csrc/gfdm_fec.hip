@@ -21,8 +21,8 @@
 // encode: element-wise; the flat OUTPUT is tiled as in gfdm_symbols.hip (the grid depends on the total size, never on n_rows), 16-byte
 //   stores where the output is aligned.  Output byte o of a row needs the information bits 4 o - 6 .. 4 o + 3: two bytes, read through the
 //   cache.  The zero padding behind the 2 T coded bits and the spare rows are written by the same kernel.
-// Not here: puncturing (a caller depunctures by writing LLR 0), interleaving, tail-biting and streaming modes, other constraint lengths or
-// rates, int8 LLR input.
+// Not here: tail-biting and streaming modes, other constraint lengths or mother-code rates, int8 LLR input.  Puncturing and interleaving
+// are gfdm_ratematch.hip's.
 #include "../../include/gfdm_hip.h"
 #include "gfdm_decide.h"
 #include "gfdm_hostcall.h"
@@ -34,6 +34,7 @@
 using gfdm::RowPos;
 using gfdm::advance;
 using gfdm::api_fail;
+using gfdm::check_width;
 using gfdm::live_rows;
 using gfdm::misaligned;
 
@@ -303,15 +304,6 @@ int check_handle(const gfdm_hip_conv_code* h, int64_t n_info, int64_t n_rows)
 {
     if (!h) return api_fail(GFDM_HIP_EINVAL, "NULL handle");
     return code_check(h->g[0], h->g[1], h->mode, n_info, n_rows);
-}
-
-// a row width in elements of `elem` bytes: at least `least`, and n_rows rows of it inside int64
-int check_width(int64_t width, int64_t least, int64_t elem, int64_t n_rows, const char* what)
-{
-    if (width < least) return api_fail(GFDM_HIP_EINVAL, std::string(what) + " is below the row's minimum");
-    if (width > INT64_MAX / elem || (n_rows > 0 && width * elem > INT64_MAX / n_rows))
-        return api_fail(GFDM_HIP_EINVAL, "the byte size of the rows overflows int64");
-    return GFDM_HIP_OK;
 }
 
 int check_encode(const gfdm_hip_conv_code* h, const void* out, const void* data, int64_t n_info, int64_t out_row_bytes, int64_t n_rows)

@@ -107,6 +107,15 @@ inline size_t sample_bytes(int fmt) { return fmt == SAMPLES_SC16 ? 2 * sizeof(in
 
 inline bool misaligned(const void* p, size_t to) { return ((uintptr_t)p % to) != 0; }
 
+// a row width in elements of `elem` bytes: at least `least`, and n_rows rows of it inside int64
+inline int check_width(int64_t width, int64_t least, int64_t elem, int64_t n_rows, const char* what)
+{
+    if (width < least) return api_fail(GFDM_HIP_EINVAL, std::string(what) + " is below the row's minimum");
+    if (width > INT64_MAX / elem || (n_rows > 0 && width * elem > INT64_MAX / n_rows))
+        return api_fail(GFDM_HIP_EINVAL, "the byte size of the rows overflows int64");
+    return GFDM_HIP_OK;
+}
+
 // The *_device flavour of an entry point, after its checks: make the handle's device current, refuse if that failed, enqueue on the caller's stream.
 template <class F>
 int on_device(int device, void* stream, F enqueue)

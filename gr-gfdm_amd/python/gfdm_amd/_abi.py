@@ -178,6 +178,16 @@ def _signatures():
     call("conv_code_encode", vp, vp, vp, i64, i64, i64)
     call("conv_code_decode", vp, vp, vp, vp, i64, i64, f32, i64, device=ws_stream)
     call("conv_code_decode_hard", vp, vp, vp, vp, i64, i64, i64, device=ws_stream)
+
+    # ---- rate matcher ----
+    fn("rate_matcher_create", i32, out(vp), i64, vp, i32, vp, i64, i32)
+    getters("rate_matcher", "destroy")
+    getters("rate_matcher", "coded_bits tx_bits tx_bytes", i64)
+    fn("rate_matcher_source_index", i32, vp, vp)
+    fn("rate_matcher_tx_bits_of", i64, i64, vp, i32)
+    fn("rate_matcher_check", i32, i64, vp, i32, vp, i64, i64)
+    for name in ("match", "unmatch", "unmatch_hard"):
+        call("rate_matcher_" + name, vp, vp, vp, i64, i64, i64)
     return sig
 
 

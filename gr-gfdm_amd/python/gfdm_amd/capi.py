@@ -1359,3 +1359,114 @@ class ConvolutionalCode(_Kernel):
         """coded bytes (n_rows, in_row_bytes >= coded_bytes(n_info)) uint8 -- encode's output, SymbolMapper.decode's bytes -> information
         bytes (n_rows, info_bytes(n_info)) uint8: the same decoder on +1 / -1"""
         return self._decode("gfdm_hip_conv_code_decode_hard", coded, U8, "coded", n_info, (), count, out, path_metric, workspace, stream)
+
+
+PUNCTURE_PATTERNS = {"1/2": (1, 1), "2/3": (1, 1, 1, 0), "3/4": (1, 1, 1, 0, 0, 1), "5/6": (1, 1, 1, 0, 0, 1, 1, 0, 0, 1)}
+
+
+def puncture_pattern(rate):
+    """The keep pattern (uint8) of a code rate over the coded row c_{0,0} c_{0,1} c_{1,0} c_{1,1} ...: "1/2", "2/3", "3/4" or "5/6" -- IEEE
+    802.11a's patterns for the 171 / 133 code (include/gfdm_hip.h, gfdm_hip_rate_matcher: bit-compatibility with that standard is
+    unpinned).  Pure host code."""
+    if rate not in PUNCTURE_PATTERNS:
+        raise ValueError("no puncturing pattern for rate %r: one of %s" % (rate, ", ".join(sorted(PUNCTURE_PATTERNS))))
+    return np.array(PUNCTURE_PATTERNS[rate], np.uint8)
+
+
+def block_interleaver(n, columns):
+    """The permutation (int32, n entries) of a block interleaver: 0 .. rows * columns - 1 written row-wise into rows = ceil(n / columns)
+    rows, read column-wise, the indices >= n dropped.  Pure host code."""
+    n, columns = int(n), int(columns)
+    if n < 1 or columns < 1:
+        raise ValueError("a block interleaver needs n >= 1 and columns >= 1")
+    rows = -(-n // columns)
+    a = np.arange(rows * columns, dtype=np.int64).reshape(rows, columns).T.ravel()
+    return a[a < n].astype(np.int32)
+
+
+class RateMatcher(_Kernel):
+    """Puncturing and interleaving of coded bits (contract in include/gfdm_hip.h, gfdm_hip_rate_matcher): match() between
+    ConvolutionalCode.encode and SymbolMapper.map, unmatch() between SymbolMapper.soft and ConvolutionalCode.decode, unmatch_hard()
+    between SymbolMapper.decode and ConvolutionalCode.decode(gain=1).  n_coded: the bits of a mother-code row (coded_bits(n_info) of the
+    code).  keep: the puncturing pattern, bit i is transmitted iff keep[i % len(keep)] != 0 (None: every bit; puncture_pattern(rate) has
+    the usual ones).  perm: a permutation of range(tx_bits()), transmitted bit j is punctured bit perm[j] (None: identity;
+    block_interleaver(n, columns) makes one; RateMatcher.tx_bits_of(n_coded, keep) sizes it).  Rows are frames or bursts: coded bytes
+    (n_rows, >= ceil(n_coded / 8)), transmitted bytes (n_rows, >= tx_bytes()), LLRs in (n_rows, >= tx_bits()) and out
+    (n_rows, >= coded_bits()) float32; a 1-D input is one row and gives a 1-D result.  numpy arrays run the host flavour; torch device
+    tensors the device flavour on the current stream unless given.  count (an int, or on the device path a one-element int64 tensor such
+    as detect's) limits the call to the first count rows, the rest is written as zeros; it is clamped to [0, n_rows]."""
+    _destroy = "gfdm_hip_rate_matcher_destroy"
+
+    @staticmethod
+    def _pattern(keep):
+        return np.ones(1, U8) if keep is None else np.ascontiguousarray(np.asarray(keep).ravel() != 0, dtype=U8)
+
+    @staticmethod
+    def _perm(perm):
+        if perm is None:
+            return None
+        p = np.asarray(perm).ravel()
+        if p.size and not np.issubdtype(p.dtype, np.integer):
+            raise TypeError("perm must hold integers, not %s" % p.dtype)
+        if p.size and (p.min() < 0 or p.max() >= 2 ** 31):
+            raise ValueError("perm is not a permutation of 0 .. n_tx - 1")
+        return np.ascontiguousarray(p, dtype=I32)
+
+    @classmethod
+    def tx_bits_of(cls, n_coded, keep=None):
+        """transmitted bits of a row of n_coded coded bits under the pattern: no handle, no device"""
+        keep = cls._pattern(keep)
+        return _bytes(lib().gfdm_hip_rate_matcher_tx_bits_of(int(n_coded), keep.ctypes.data, keep.size))
+
+    def __init__(self, n_coded, keep=None, perm=None, device=0):
+        keep, perm = self._pattern(keep), self._perm(perm)
+        h = ctypes.c_void_p()
+        _check(lib().gfdm_hip_rate_matcher_create(ctypes.byref(h), int(n_coded), keep.ctypes.data, keep.size, ops.ptr(perm),
+                                                  0 if perm is None else perm.size, device))
+        self._h = h
+        self._dev = int(device)
+        self._n_coded, self._n_tx = (_bytes(getattr(lib(), "gfdm_hip_rate_matcher_" + name)(h)) for name in ("coded_bits", "tx_bits"))
+
+    def coded_bits(self):
+        return self._n_coded
+
+    def tx_bits(self):
+        return self._n_tx
+
+    def tx_bytes(self):
+        """bytes of a packed transmitted row: ceil(tx_bits() / 8)"""
+        return _bytes(lib().gfdm_hip_rate_matcher_tx_bytes(self._h))
+
+    def source_index(self):
+        """src (int32, tx_bits() entries): transmitted bit j is coded bit src[j] -- the pattern and the permutation composed"""
+        src = np.empty(self._n_tx, I32)
+        _check(lib().gfdm_hip_rate_matcher_source_index(self._h, src.ctypes.data))
+        return src
+
+    def _call(self, name, x, dtype, what, least_in, out_dtype, least_out, out_width, out_what, count, out, stream):
+        x, n_rows, width, flat = ops.rows(x, dtype, what, self._dev)
+        out_width = least_out if out_width is None else int(out_width)
+        if width < least_in or out_width < least_out:
+            raise ValueError("%s has rows of %d, below the minimum %d" % ((what, width, least_in) if width < least_in else (out_what, out_width, least_out)))
+        res = ops.result(x, (out_width,) if flat else (n_rows, out_width), out_dtype, self._dev, out, as_what=what, off_device=RuntimeError)
+        cnt = ops.count_arg(count, x, self._dev)
+        self._run("gfdm_hip_rate_matcher_" + name, x, (ops.ptr(res), ops.ptr(x), ops.ptr(cnt), width, out_width, n_rows), stream)
+        return res
+
+    def match(self, coded, out_row_bytes=None, count=None, out=None, stream=None):
+        """coded bytes (n_rows, in_row_bytes >= ceil(coded_bits() / 8)) uint8 -- encode's output at any width -> transmitted bytes
+        (n_rows, out_row_bytes) uint8; out_row_bytes (default tx_bytes()) may be wider, e.g. SymbolMapper.row_bytes(n_sym): what lies
+        behind the transmitted bits is written as 0"""
+        return self._call("match", coded, U8, "coded", (self._n_coded + 7) // 8, U8, self.tx_bytes(), out_row_bytes, "out_row_bytes", count, out, stream)
+
+    def unmatch(self, llr, out_stride=None, count=None, out=None, stream=None):
+        """LLRs (n_rows, in_stride >= tx_bits()) float32 -- SymbolMapper.soft's output as it is -> LLRs of the coded row
+        (n_rows, out_stride) float32, out_stride >= coded_bits() (the default): a bit copy of every transmitted value at its coded
+        position, +0.0 at the punctured positions and behind coded_bits().  What ConvolutionalCode.decode takes."""
+        return self._call("unmatch", llr, F32, "llr", self._n_tx, F32, self._n_coded, out_stride, "out_stride", count, out, stream)
+
+    def unmatch_hard(self, tx, out_stride=None, count=None, out=None, stream=None):
+        """transmitted bytes (n_rows, in_row_bytes >= tx_bytes()) uint8 -- SymbolMapper.decode's output -> float32 rows laid out as
+        unmatch's: +1.0 for a 0 bit, -1.0 for a 1 bit, +0.0 at the punctured positions.  ConvolutionalCode.decode with gain 1 on them is
+        hard-decision decoding with erasures."""
+        return self._call("unmatch_hard", tx, U8, "tx", self.tx_bytes(), F32, self._n_coded, out_stride, "out_stride", count, out, stream)

@@ -952,8 +952,8 @@ int gfdm_hip_link_meter_measure_device(gfdm_hip_link_meter* m, void* bit_errors,
  *   width below the minimum; gain non-finite or <= 0; a NULL buffer the call would touch (the workspace where one is needed).
  *   n_rows == 0 returns GFDM_HIP_OK without a launch.  The size getters return int64, negative values are status codes; poly returns
  *   0 for a bad handle or index.
- * Not here: puncturing (a caller depunctures by writing LLR 0), interleaving, tail-biting and streaming modes, other constraint
- *   lengths or rates, int8 LLR input.
+ * Not here: tail-biting and streaming modes, other constraint lengths or mother-code rates, int8 LLR input.  Puncturing (rates above
+ *   1/2: a depunctured position is an LLR of 0) and interleaving are gfdm_hip_rate_matcher's, below.
  * Tested range (bit for bit, path_metric included, against the numpy restatement of the above in tests/conv_code_ref.py): both modes;
  *   n_info 1, 2, 5, 6, 7, 8, 57, 58, 59, 122, 456, the last three that keep T <= GFDM_HIP_CC_LDS_STEPS and the two after, one row of
  *   2^16 + 3; 1, 3, 4, 5, 7, 5000 (n_info 3) and 32768 + 7 (n_info 2) rows per call; polys (109, 79), (109, -79), (91, 121), (55, 79);
@@ -987,6 +987,77 @@ int gfdm_hip_conv_code_decode_hard_host(gfdm_hip_conv_code* c, uint8_t* out, int
                                         int64_t n_info, int64_t in_row_bytes, int64_t n_rows);
 int gfdm_hip_conv_code_decode_hard_device(gfdm_hip_conv_code* c, void* out, void* path_metric, const void* coded, const void* count, int64_t n_info,
                                           int64_t in_row_bytes, int64_t n_rows, void* workspace, void* stream);
+
+/* ---- gfdm_hip_rate_matcher: puncture and interleave coded bits, depuncture and deinterleave LLRs --------------------------------------
+ * Between gfdm_hip_conv_code_encode and gfdm_hip_symbol_mapper_map on the transmit side (match), between ..._soft and
+ * gfdm_hip_conv_code_decode (unmatch), or between ..._symbol_mapper_decode and ..._conv_code_decode (unmatch_hard), on the receive side.
+ * Everything is integer index arithmetic, so every result is exact.  With c_0 .. c_{n_coded-1} the bits of a mother-code row
+ * (n_coded = gfdm_hip_conv_code_coded_bits; 1 <= n_coded <= 2^21, the code's T <= 2^20):
+ *   Puncturing: keep[0 .. period-1] is a pattern of bytes, 1 <= period <= 4096; bit i of the coded row is transmitted iff
+ *     keep[i mod period] != 0.  The kept positions in ascending order are k_0 < ... < k_{n_tx-1}; n_tx >= 1 is required
+ *     (tx_bits_of gives n_tx without a handle).  The punctured sequence is p_a = c[k_a].
+ *   Interleaving: perm[0 .. n_tx-1] is a permutation of 0 .. n_tx-1, NULL for the identity (n_perm is then ignored).  The gather
+ *     convention: transmitted bit j is t_j = p[perm[j]] = c[src[j]] with src[j] = k_{perm[j]}.
+ *   create composes both on the host into src (n_tx entries; source_index copies it out) and its inverse inv (n_coded entries, -1 at
+ *   the punctured positions) and keeps the two tables on the device.  A handle serves one (n_coded, keep, perm).
+ *   The patterns in use for the 171 / 133 code over c_{0,0} c_{0,1} c_{1,0} c_{1,1} ... are [1,1] (rate 1/2), [1,1,1,0] (2/3),
+ *   [1,1,1,0,0,1] (3/4) and [1,1,1,0,0,1,1,0,0,1] (5/6): those of IEEE 802.11a.  That standard is not part of this project's test
+ *   bed; bit-compatibility with it is unpinned.
+ * Packing is the symbol mapper's: MSB first, every row starts on a byte.  tx_bytes = ceil(n_tx / 8).
+ * match: coded bytes [n_rows][in_row_bytes], in_row_bytes >= ceil(n_coded / 8) (encode's output at any width; what lies behind the
+ *   n_coded bits of a row is never looked at) -> transmitted bytes [n_rows][out_row_bytes], out_row_bytes >= tx_bytes.  Everything behind
+ *   the n_tx bits of a row is written as 0, so a row may have the width gfdm_hip_symbol_mapper_row_bytes(n_sym) and go straight into map.
+ * unmatch: float32 LLRs [n_rows][in_stride], in_stride >= n_tx (the floats behind n_tx are never read: soft's rows go in as they are)
+ *   -> float32 [n_rows][out_stride], out_stride >= n_coded: out[i] = in[inv[i]] as a BIT copy (NaN payloads and the sign of zero are
+ *   preserved), +0.0f where inv[i] < 0 and in the floats behind n_coded.  The output is what gfdm_hip_conv_code_decode takes, with
+ *   llr_stride = out_stride.
+ * unmatch_hard: transmitted bytes [n_rows][in_row_bytes], in_row_bytes >= tx_bytes (gfdm_hip_symbol_mapper_decode's output) -> float32
+ *   rows laid out as unmatch's: +1.0f for a 0 bit, -1.0f for a 1 bit, +0.0f at the punctured positions and behind n_coded.  Fed to
+ *   gfdm_hip_conv_code_decode with gain 1 this is q = +1 / -1 / 0: decode_hard's metric with erasures, which decode_hard cannot express.
+ * count, *_device, *_host: as for gfdm_hip_conv_code.  Rows from n_live = clamp(*count, 0, n_rows) on are written as zeros and their
+ *   input is never read; every output element is written exactly once by the one kernel of the call, with no memset in front, so a
+ *   graph replay with a changed count is correct.  The device flavours neither allocate nor synchronise and are hipGraph-capturable.
+ *   Buffers need the alignment of one element and no more: 1 byte for bytes, 4 bytes for floats (8 for count); byte offsets are 64-bit.
+ *   The host flavours upload, run the device call and download: a convenience, not a pipeline.
+ * Rows of at most GFDM_HIP_RM_LDS_BITS coded bits have their table copied into LDS once per workgroup; longer rows read it through the
+ *   cache.  The results are the same.
+ * GFDM_HIP_EINVAL from check (the argument table alone, without a handle or a device), from create (before any device is touched) and
+ *   where it applies from tx_bits_of: n_coded < 1 or > 2^21; period < 1 or > 4096; a NULL keep; a pattern that keeps no bit within
+ *   n_coded; with a perm, n_perm != n_tx or a perm that is not a permutation of 0 .. n_tx-1; n_rows < 0; byte sizes that overflow int64.
+ *   From the calls: a NULL handle; n_rows < 0; a width or stride below the minimum; byte sizes that overflow int64; a NULL buffer the
+ *   call would touch.  n_rows == 0 returns GFDM_HIP_OK without a launch.  The size getters return int64, negative values are status
+ *   codes.
+ * Not here: fusing unmatch into decode's LLR fetch (it would change the decode kernel; profiles/r17/rate_matcher_kernel_durations.txt
+ *   is the measurement to decide it by), per-row patterns, repetition (rates below 1/2).
+ * Tested range (bit for bit against the numpy restatement of the above in tests/rate_match_ref.py): n_coded 1, 2, 7, 8, 9, 15, 16, 17,
+ *   63, 64, 65, 127, 128, 129, 924, 1388, GFDM_HIP_RM_LDS_BITS + 0, 1, 2, one row of 2^17 + 6; the patterns all ones, the four rates
+ *   above, [0,1], the period-7 pattern [1,0,1,1,0,1,1], a period above n_coded, one kept bit; perm identity, reversal, block
+ *   interleavers of 18 and n_tx columns, a random permutation; 1, 3, 4, 5, 7, 5000 (n_coded 6) and 32768 + 7 (n_coded 4) rows per
+ *   call; widths and strides of the minimum + 0, 1, 12; buffers at every alignment of one element; NaN payloads, infinities, -0.0 and
+ *   denormals; count below, at and beyond n_rows. */
+#define GFDM_HIP_RM_LDS_BITS 8192 /* rows of up to this many coded bits keep their index table in LDS (32 KiB per workgroup) */
+typedef struct gfdm_hip_rate_matcher gfdm_hip_rate_matcher;
+int gfdm_hip_rate_matcher_create(gfdm_hip_rate_matcher** out, int64_t n_coded, const uint8_t* keep, int period, const int32_t* perm, int64_t n_perm,
+                                 int device);
+int gfdm_hip_rate_matcher_destroy(gfdm_hip_rate_matcher* r);
+int64_t gfdm_hip_rate_matcher_coded_bits(const gfdm_hip_rate_matcher* r);
+int64_t gfdm_hip_rate_matcher_tx_bits(const gfdm_hip_rate_matcher* r);
+int64_t gfdm_hip_rate_matcher_tx_bytes(const gfdm_hip_rate_matcher* r);
+int gfdm_hip_rate_matcher_source_index(const gfdm_hip_rate_matcher* r, int32_t* src);
+int64_t gfdm_hip_rate_matcher_tx_bits_of(int64_t n_coded, const uint8_t* keep, int period);
+int gfdm_hip_rate_matcher_check(int64_t n_coded, const uint8_t* keep, int period, const int32_t* perm, int64_t n_perm, int64_t n_rows);
+int gfdm_hip_rate_matcher_match_host(gfdm_hip_rate_matcher* r, uint8_t* out, const uint8_t* coded, const int64_t* count, int64_t in_row_bytes,
+                                     int64_t out_row_bytes, int64_t n_rows);
+int gfdm_hip_rate_matcher_match_device(gfdm_hip_rate_matcher* r, void* out, const void* coded, const void* count, int64_t in_row_bytes,
+                                       int64_t out_row_bytes, int64_t n_rows, void* stream);
+int gfdm_hip_rate_matcher_unmatch_host(gfdm_hip_rate_matcher* r, float* out, const float* llr, const int64_t* count, int64_t in_stride,
+                                       int64_t out_stride, int64_t n_rows);
+int gfdm_hip_rate_matcher_unmatch_device(gfdm_hip_rate_matcher* r, void* out, const void* llr, const void* count, int64_t in_stride,
+                                         int64_t out_stride, int64_t n_rows, void* stream);
+int gfdm_hip_rate_matcher_unmatch_hard_host(gfdm_hip_rate_matcher* r, float* out, const uint8_t* tx, const int64_t* count, int64_t in_row_bytes,
+                                            int64_t out_stride, int64_t n_rows);
+int gfdm_hip_rate_matcher_unmatch_hard_device(gfdm_hip_rate_matcher* r, void* out, const void* tx, const void* count, int64_t in_row_bytes,
+                                              int64_t out_stride, int64_t n_rows, void* stream);
 
 #ifdef __cplusplus
 }
