@@ -188,6 +188,15 @@ def _signatures():
     fn("rate_matcher_check", i32, i64, vp, i32, vp, i64, i64)
     for name in ("match", "unmatch", "unmatch_hard"):
         call("rate_matcher_" + name, vp, vp, vp, i64, i64, i64)
+
+    # ---- frame check ----
+    fn("frame_check_create", i32, out(vp), i64, u64, u64, i32, i32)
+    getters("frame_check", "destroy")
+    getters("frame_check", "payload_bytes frame_bytes frame_bits", i64)
+    fn("frame_check_whitening", i32, vp, vp)
+    fn("frame_check_check", i32, i64, u64, u64, i32, i64)
+    call("frame_check_attach", vp, vp, vp, i64, i64, i64)
+    call("frame_check_verify", vp, vp, vp, vp, vp, vp, i64, i64, i64)
     return sig
 
 

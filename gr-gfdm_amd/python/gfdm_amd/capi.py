@@ -1470,3 +1470,110 @@ class RateMatcher(_Kernel):
         unmatch's: +1.0 for a 0 bit, -1.0 for a 1 bit, +0.0 at the punctured positions.  ConvolutionalCode.decode with gain 1 on them is
         hard-decision decoding with erasures."""
         return self._call("unmatch_hard", tx, U8, "tx", self.tx_bytes(), F32, self._n_coded, out_stride, "out_stride", count, out, stream)
+
+
+class FrameCheck(_Kernel):
+    """Frame check sequence and whitening of payload rows (contract in include/gfdm_hip.h, gfdm_hip_frame_check): attach() in front of
+    ConvolutionalCode.encode, verify() behind ConvolutionalCode.decode at n_info = frame_bits -- the receiver's keep-or-drop verdict on a
+    row.  n_payload: the bytes of a payload row; a frame row is frame_bytes = n_payload + 4: the payload, its CRC-32 (zlib.crc32) least
+    significant byte first, and over both the whitening sequence of the Fibonacci LFSR (mask, seed, degree), MSB first; degree=0
+    switches whitening off (mask and seed are then ignored).  The default is x^7 + x^4 + 1 from the all-ones state.  Rows are frames or
+    bursts: payload bytes (n_rows, >= payload_bytes), frame bytes (n_rows, >= frame_bytes); a 1-D input is one row and gives a 1-D
+    result.  numpy arrays run the host flavour; torch device tensors the device flavour on the current stream unless given.  count (an
+    int, or on the device path a one-element int64 tensor such as detect's) limits the call to the first count rows, the rest is written
+    as zeros (ok 0); it is clamped to [0, n_rows]."""
+    _destroy = "gfdm_hip_frame_check_destroy"
+
+    @staticmethod
+    def _lfsr(mask, seed, degree):
+        mask, seed, degree = int(mask), int(seed), int(degree)
+        if degree == 0:
+            return 0, 0, 0
+        if not (0 <= mask < 2 ** 64 and 0 <= seed < 2 ** 64):
+            raise ValueError("mask and seed must satisfy 1 <= value < 2^degree")
+        return mask, seed, degree
+
+    @classmethod
+    def check(cls, n_payload, mask=0x11, seed=0x7F, degree=7, n_rows=0):
+        """the argument table of the constructor and the calls (ValueError): no handle, no device"""
+        _check(lib().gfdm_hip_frame_check_check(int(n_payload), *cls._lfsr(mask, seed, degree), int(n_rows)))
+
+    def __init__(self, n_payload, mask=0x11, seed=0x7F, degree=7, device=0):
+        h = ctypes.c_void_p()
+        _check(lib().gfdm_hip_frame_check_create(ctypes.byref(h), int(n_payload), *self._lfsr(mask, seed, degree), device))
+        self._h = h
+        self._dev = int(device)
+        self._n_payload, self._n_frame = (_bytes(getattr(lib(), "gfdm_hip_frame_check_" + name)(h)) for name in ("payload_bytes", "frame_bytes"))
+
+    @property
+    def payload_bytes(self):
+        return self._n_payload
+
+    @property
+    def frame_bytes(self):
+        """payload_bytes + 4"""
+        return self._n_frame
+
+    @property
+    def frame_bits(self):
+        """8 * frame_bytes: the n_info of ConvolutionalCode.encode / decode"""
+        return _bytes(lib().gfdm_hip_frame_check_frame_bits(self._h))
+
+    @property
+    def whitening(self):
+        """the packed whitening sequence of a frame row (uint8, frame_bytes entries; zeros with degree=0)"""
+        seq = np.empty(self._n_frame, U8)
+        _check(lib().gfdm_hip_frame_check_whitening(self._h, seq.ctypes.data))
+        return seq
+
+    @staticmethod
+    def _width(width, least, what):
+        width = least if width is None else int(width)
+        if width < least:
+            raise ValueError("%s is %d, below the minimum %d" % (what, width, least))
+        return width
+
+    def attach(self, payload, count=None, out=None, stream=None, out_row_bytes=None):
+        """payload bytes (n_rows, in_row_bytes >= payload_bytes) uint8 -> frame bytes (n_rows, out_row_bytes) uint8; out_row_bytes
+        (default frame_bytes) may be wider: what lies behind the frame is written as 0.  What ConvolutionalCode.encode takes at
+        n_info = frame_bits."""
+        x, n_rows, width, flat = ops.rows(payload, U8, "payload", self._dev)
+        self._width(width, self._n_payload, "the width of payload")
+        out_width = self._width(out_row_bytes, self._n_frame, "out_row_bytes")
+        res = ops.result(x, (out_width,) if flat else (n_rows, out_width), U8, self._dev, out, as_what="payload", off_device=RuntimeError)
+        cnt = ops.count_arg(count, x, self._dev)
+        self._run("gfdm_hip_frame_check_attach", x, (ops.ptr(res), ops.ptr(x), ops.ptr(cnt), width, out_width, n_rows), stream)
+        return res
+
+    def verify(self, frames, count=None, good_rows=False, out=None, stream=None, out_row_bytes=None, payload=True):
+        """frame bytes (n_rows, in_row_bytes >= frame_bytes) uint8 -- ConvolutionalCode.decode's output as it is -> (payload, ok), or with
+        good_rows (payload, ok, good_row, n_good): payload (n_rows, out_row_bytes >= payload_bytes, the default) uint8, the dewhitened
+        payload of every live row, good or not; ok (n_rows,) uint8, 1 where the row's CRC holds; good_row (n_rows,) int64, the indices
+        of the good rows in ascending order, then -1; n_good (1,) int64.  payload=False checks only (the first result is None).  out: a
+        dict with any of "payload", "ok", "good_row", "n_good" to write into."""
+        x, n_rows, width, flat = ops.rows(frames, U8, "frames", self._dev)
+        self._width(width, self._n_frame, "the width of frames")
+        out = out or {}
+
+        def result(key, shape, dtype):
+            return ops.result(x, shape, dtype, self._dev, out.get(key), "out[%r]" % key, "frames", off_device=RuntimeError)
+
+        res_p, out_width = None, 0
+        if payload:
+            out_width = self._width(out_row_bytes, self._n_payload, "out_row_bytes")
+            res_p = result("payload", (out_width,) if flat else (n_rows, out_width), U8)
+        elif out.get("payload") is not None:
+            raise ValueError("payload=False writes no payload")
+        ok = result("ok", (n_rows,), U8)
+        good = n_good = None
+        if good_rows:
+            good, n_good = result("good_row", (n_rows,), I64), result("n_good", (1,), I64)
+            if n_rows == 0:                                    # a call without rows launches nothing
+                n_good[...] = 0
+        elif out.get("good_row") is not None or out.get("n_good") is not None:
+            raise ValueError("good_row and n_good need good_rows=True")
+        cnt = ops.count_arg(count, x, self._dev)
+        if n_rows:                                             # (an empty tensor has no address: its good_row would read as "not asked for")
+            self._run("gfdm_hip_frame_check_verify", x, (ops.ptr(res_p), ops.ptr(ok), ops.ptr(good), ops.ptr(n_good), ops.ptr(x), ops.ptr(cnt), width,
+                                                          out_width, n_rows), stream)
+        return (res_p, ok, good, n_good) if good_rows else (res_p, ok)

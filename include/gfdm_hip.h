@@ -1059,6 +1059,64 @@ int gfdm_hip_rate_matcher_unmatch_hard_host(gfdm_hip_rate_matcher* r, float* out
 int gfdm_hip_rate_matcher_unmatch_hard_device(gfdm_hip_rate_matcher* r, void* out, const void* tx, const void* count, int64_t in_row_bytes,
                                               int64_t out_stride, int64_t n_rows, void* stream);
 
+/* ---- gfdm_hip_frame_check: CRC-32 and whitening of payload rows, attach before the code and verify behind it --------------------------
+ * The two ends of the chain: attach in front of gfdm_hip_conv_code_encode, verify behind gfdm_hip_conv_code_decode -- the receiver's
+ * verdict on a row (keep or drop) without the payload that was sent.  GNU Radio's digital.crc32_bb / crc_append / crc_check and
+ * digital.additive_scrambler_bb do the same work; GNU Radio is not part of this project's test bed: the pair is DEFINED by the formulas
+ * below, and bit-compatibility with GNU Radio's blocks is unpinned.  All arithmetic is integer, so every result is exact.
+ * Frame: a payload row is n_payload bytes, 1 <= n_payload <= 2^17 - 4.  A frame row is frame_bytes = n_payload + 4 bytes: the payload,
+ *   then the CRC, least significant byte first.  frame_bits = 8 frame_bytes is what goes into gfdm_hip_conv_code_encode as n_info; 2^17
+ *   bytes keeps it at the code's T <= 2^20.
+ * CRC: CRC-32 of IEEE 802.3, by the bitwise formula: r = 0xFFFFFFFF; for every byte b of the payload, in order: r ^= b, then eight times
+ *   r = (r >> 1) ^ (r & 1 ? 0xEDB88320 : 0); the CRC is r ^ 0xFFFFFFFF.  This is zlib's crc32; its value for "123456789" is 0xCBF43926.
+ * Whitening: an additive sequence from a Fibonacci LFSR.  degree d is 0 (no whitening; mask and seed are ignored) or 1 .. 32, with
+ *   1 <= mask < 2^d and 1 <= seed < 2^d.  s_0 = seed; whitening bit w_i = s_i & 1; s_{i+1} = (s_i >> 1) | (parity(s_i & mask) << (d - 1)),
+ *   so w_{i+d} = XOR over the set bits j of mask of w_{i+j}; d = 7, mask = 0x11 is x^7 + x^4 + 1.  Bit i of the sequence is XORed onto
+ *   bit i of the frame row in the symbol mapper's order (MSB first), over all frame_bits, CRC included; every row starts at s_0.  create
+ *   computes the packed sequence (frame_bytes bytes) on the host and keeps it on the device; whitening copies it out.
+ * attach: payload bytes [n_rows][in_row_bytes], in_row_bytes >= n_payload (the bytes behind the payload are never read) -> frame bytes
+ *   [n_rows][out_row_bytes], out_row_bytes >= frame_bytes: the payload, then the CRC of the unwhitened payload, the whitening over both,
+ *   and zeros behind frame_bytes.
+ * verify: frame bytes [n_rows][in_row_bytes], in_row_bytes >= frame_bytes (decode's output at n_info = frame_bits, as it is) ->
+ *   payload [n_rows][out_row_bytes], out_row_bytes >= n_payload: the dewhitened payload of every live row, good or not, and zeros
+ *   behind it; ok uint8 [n_rows]: 1 where the CRC of the dewhitened payload equals the dewhitened four bytes behind it, else 0;
+ *   good_row int64 [n_rows]: the indices of the rows with ok = 1 in ascending order, then -1; n_good: one int64.  payload may be NULL
+ *   (check only; out_row_bytes is then ignored); good_row and n_good may both be NULL.  verify never looks at anything but the frame.
+ * count, *_device, *_host: as for gfdm_hip_rate_matcher.  Rows from n_live = clamp(*count, 0, n_rows) on are written as zeros (ok 0,
+ *   not in good_row) and their input is never read; every output element is written exactly once per call with no memset in front, so
+ *   a graph replay with a changed count is correct.  A call is one kernel, and a second, small one where good_row is asked for; no
+ *   workspace.  The device flavours neither allocate nor synchronise and are hipGraph-capturable.  Buffers need the alignment of one
+ *   element and no more: 1 byte for bytes, 8 bytes for good_row, n_good and count; byte offsets are 64-bit.  The host flavours upload,
+ *   run the device call and download: a convenience, not a pipeline.
+ * GFDM_HIP_EINVAL from check (the argument table alone, without a handle or a device), from create (before any device is touched) and
+ *   from every call: n_payload out of range; degree outside 0 .. 32; a mask or seed of 0 or >= 2^d when d > 0; n_rows < 0; byte sizes
+ *   that overflow int64.  From the calls also: a NULL handle; a width below the minimum; a NULL buffer the call would touch; exactly
+ *   one of good_row / n_good.  n_rows == 0 returns GFDM_HIP_OK without a launch.  The size getters return int64, negative values are
+ *   status codes.
+ * Not here: a per-row seed (802.11's random scrambler initialisation); other CRC polynomials or widths; moving the good rows' payloads
+ *   to the front (good_row is the index list such a gather would take); fusing verify into decode's traceback.
+ * Tested range (bit for bit against the numpy restatement of the above in tests/frame_check_ref.py): n_payload 1, 2, 11, 12, 13, 27, 28,
+ *   29, 57, 60, 61, 124, 1019, 1020, 1021, 1024, 2044, 2045 and one row of 2^17 - 4; 1, 3, 4, 5, 7, 63, 64, 65 rows per call at every
+ *   group size, 5000, 32768 + 7, 65536 + 5 and 2^20 + 4101 short rows, 8197 rows of 1025 bytes; widths of the minimum + 0, 1, 12; buffers
+ *   at every byte alignment; whitening off, (7, 0x11, 0x7F) and a degree-32 mask; single-bit errors in the payload, the CRC and the last
+ *   byte, all rows good, no row good; count below, at and beyond n_rows; decode -> verify in a captured graph. */
+typedef struct gfdm_hip_frame_check gfdm_hip_frame_check;
+int gfdm_hip_frame_check_create(gfdm_hip_frame_check** out, int64_t n_payload, uint64_t mask, uint64_t seed, int degree, int device);
+int gfdm_hip_frame_check_destroy(gfdm_hip_frame_check* c);
+int64_t gfdm_hip_frame_check_payload_bytes(const gfdm_hip_frame_check* c);
+int64_t gfdm_hip_frame_check_frame_bytes(const gfdm_hip_frame_check* c);
+int64_t gfdm_hip_frame_check_frame_bits(const gfdm_hip_frame_check* c);
+int gfdm_hip_frame_check_whitening(const gfdm_hip_frame_check* c, uint8_t* seq);
+int gfdm_hip_frame_check_check(int64_t n_payload, uint64_t mask, uint64_t seed, int degree, int64_t n_rows);
+int gfdm_hip_frame_check_attach_host(gfdm_hip_frame_check* c, uint8_t* out, const uint8_t* payload, const int64_t* count, int64_t in_row_bytes,
+                                     int64_t out_row_bytes, int64_t n_rows);
+int gfdm_hip_frame_check_attach_device(gfdm_hip_frame_check* c, void* out, const void* payload, const void* count, int64_t in_row_bytes,
+                                       int64_t out_row_bytes, int64_t n_rows, void* stream);
+int gfdm_hip_frame_check_verify_host(gfdm_hip_frame_check* c, uint8_t* payload, uint8_t* ok, int64_t* good_row, int64_t* n_good, const uint8_t* frames,
+                                     const int64_t* count, int64_t in_row_bytes, int64_t out_row_bytes, int64_t n_rows);
+int gfdm_hip_frame_check_verify_device(gfdm_hip_frame_check* c, void* payload, void* ok, void* good_row, void* n_good, const void* frames,
+                                       const void* count, int64_t in_row_bytes, int64_t out_row_bytes, int64_t n_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
