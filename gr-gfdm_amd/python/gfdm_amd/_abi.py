@@ -149,6 +149,16 @@ def _signatures():
     fn("channel_model_check", i32, i32, f64, f64, i64, i64, i64, f64)
     call("channel_model_apply", vp, vp, i64, i64, i64, sc16=(f64,))
 
+    # ---- resampler: the sc16 twins read int16 I/Q and take their sibling's arguments ----
+    fn("resampler_create", i32, out(vp), vp, i32, i32, i32, u64, i32)
+    getters("resampler", "destroy n_taps n_phases interp")
+    fn("resampler_taps", i32, vp, vp)
+    fn("resampler_step", i32, vp, out(u64))
+    fn("resampler_set_step", i32, vp, u64)
+    fn("resampler_check", i32, i32, i32, i32, u64, i64, i64, i64, i64)
+    fn("resampler_plan", i32, u64, i32, i64, i64, i32, out(i64), out(i64), out(i64))
+    call("resampler_resample", vp, vp, i64, i64, i64, i64, sc16=())
+
     # ---- symbol mapper and link meter ----
     for kind in ("symbol_mapper", "link_meter"):
         fn(kind + "_create", i32, out(vp), vp, i32, i32, i32)

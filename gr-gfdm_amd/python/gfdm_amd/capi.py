@@ -1100,7 +1100,7 @@ class ChannelModel(_Kernel):
     """Multipath, frequency offset and noise on a stream, on the device (contract in include/gfdm_hip.h, gfdm_hip_channel_model): GNU
     Radio's channels.channel_model in its argument order, between BurstShaper.place and BurstSync.detect.  y = FIR(taps) of x, times
     exp(j 2 pi frequency_offset n), plus white Gaussian noise of power noise_voltage^2 that is a pure function of (noise_seed, absolute
-    sample index).  epsilon (the timing offset) must be 1.0: resampling is not part of this.  The taps are fixed; frequency_offset,
+    sample index).  epsilon (the timing offset) must be 1.0: resampling is not part of this, Resampler in front of apply is.  The taps are fixed; frequency_offset,
     noise_voltage and seed have setters, and a captured graph keeps the values it was captured with."""
     _destroy = "gfdm_hip_channel_model_destroy"
 
@@ -1166,6 +1166,142 @@ class ChannelModel(_Kernel):
         res = ops.stream_result(x, n, sc16, self._dev, out, "x")
         self._run("gfdm_hip_channel_model_apply" + ("_sc16" if sc16 else ""), x,
                   (ops.ptr(res), ops.ptr(x) + 8 * history, n, history, offset) + ((float(gain),) if sc16 else ()), stream)
+        return res
+
+
+def resampler_step(x):
+    """Resampler's step for a rate `x` (input samples per output sample, a float or a fractions.Fraction): x * 2^32 rounded to the nearest
+    integer (ties to even), the unsigned Q32.32 of the contract.  1.0 -> 2^32.  A Fraction is converted exactly."""
+    import fractions
+    q = round(fractions.Fraction(x) * (1 << 32))
+    if not (1 << 29) <= q <= (1 << 35):
+        raise ValueError("the rate(%s) must lie in 1/8 .. 8" % (x,))
+    return int(q)
+
+
+def resampler_taps(n_phases=128, n_taps=16, cutoff=1.0, beta=8.0):
+    """The default table of Resampler: float32 of shape (n_phases + 1, n_taps).  Row p, tap t is the Kaiser-windowed sinc
+    cutoff * sinc(cutoff * u) * I0(beta * sqrt(1 - (u / W)^2)) / I0(beta) at u = t - D - p / n_phases (D = (n_taps - 1) // 2, W = D + 1, zero
+    from |u| = W on), computed in float64, every row normalised to unit DC gain, then rounded to float32.  Where cutoff * u is an integer
+    the sinc is exactly 0 or 1, so with cutoff = 1 row 0 is exactly the unit impulse at tap D; row n_phases is exactly row 0 moved by one tap.
+    cutoff is a fraction of the input's Nyquist band: below 1 for decimation (step > 1).  The table is this project's own:
+    bit-compatibility with GNU Radio's MMSE table is unpinned."""
+    L, T = int(n_phases), int(n_taps)
+    if T < 2 or T > 64:
+        raise ValueError("n_taps(%d) must lie in 2 .. 64: one tap cannot hold row 0 moved by one tap" % T)
+    if L < 1 or L > 1024 or L & (L - 1):
+        raise ValueError("n_phases(%d) must be a power of two in 1 .. 1024" % L)
+    if not 0.0 < float(cutoff) <= 1.0:
+        raise ValueError("cutoff must lie in (0, 1]")
+    if not float(beta) >= 0.0:
+        raise ValueError("beta must be >= 0")
+    D = (T - 1) // 2
+    W = D + 1
+    num = L * (np.arange(T)[None, :] - D) - np.arange(L + 1)[:, None]              # u * L, exact
+    u = num / float(L)
+    v = float(cutoff) * u
+    s = np.sinc(v)
+    whole = v == np.rint(v)
+    s[whole] = (v[whole] == 0).astype(np.float64)
+    inside = np.abs(num) < W * L
+    win = np.where(inside, np.i0(float(beta) * np.sqrt(np.where(inside, 1.0 - (u / W) ** 2, 0.0))) / np.i0(float(beta)), 0.0)
+    h = float(cutoff) * s * win
+    h /= h.sum(axis=1, keepdims=True)
+    h = h.astype(np.float32)
+    h[L, 1:] = h[0, :-1]
+    h[L, 0] = 0.0
+    return h
+
+
+class Resampler(_Kernel):
+    """Fractional-rate resampling of a stream, on the device (contract in include/gfdm_hip.h, gfdm_hip_resampler): the resampler GNU
+    Radio's channels.channel_model drives with epsilon (place -> resample -> ChannelModel.apply), and the conversion of a capture at a
+    radio's rate in front of BurstSync.detect.  step_or_ratio: a Python int is the step itself (unsigned Q32.32: input samples per
+    output sample times 2^32), a float or fractions.Fraction goes through resampler_step.  taps: a float32 table of shape
+    (n_phases + 1, n_taps), row n_phases being row 0 moved by one sample; None: resampler_taps(n_phases, n_taps, cutoff) with cutoff =
+    min(1, 1 / rate).  interp: "linear" between neighbouring rows or "nearest" (GNU Radio's mmse rule).  The table and interp are fixed;
+    the step has a setter, and a captured graph keeps the step it was captured with.  The table does not follow set_step: the default
+    table's cutoff is that of the step given here, so a later, larger step aliases what lies above 1 / rate -- build a new Resampler (or
+    pass a table of the smaller cutoff) for a larger rate."""
+    _destroy = "gfdm_hip_resampler_destroy"
+    INTERP = {"nearest": 0, "linear": 1}
+
+    def __init__(self, step_or_ratio, taps=None, n_phases=128, n_taps=16, interp="linear", device=None):
+        if interp not in self.INTERP:
+            raise ValueError("interp must be 'nearest' or 'linear', not %r" % (interp,))
+        step = self._step_of(step_or_ratio)
+        if taps is None:
+            taps = resampler_taps(n_phases, n_taps, min(1.0, float(1 << 32) / step))
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        if t.ndim != 2 or t.shape[0] < 2:
+            raise ValueError("taps must have shape (n_phases + 1, n_taps), not %s" % (tuple(t.shape),))
+        h = ctypes.c_void_p()
+        dev = 0 if device is None else int(device)
+        _check(lib().gfdm_hip_resampler_create(ctypes.byref(h), t.ctypes.data, t.shape[1], t.shape[0] - 1, self.INTERP[interp], step, dev))
+        self._h = h
+        self._dev = dev
+        self._T = int(t.shape[1])
+
+    @staticmethod
+    def _step_of(step_or_ratio):
+        if isinstance(step_or_ratio, (int, np.integer)) and not isinstance(step_or_ratio, bool):
+            step = int(step_or_ratio)
+            if not (1 << 29) <= step <= (1 << 35):
+                raise ValueError("step(%d) must lie in 2^29 .. 2^35 (Q32.32: 1/8 .. 8)" % step)
+            return step
+        return resampler_step(step_or_ratio)
+
+    def n_taps(self):
+        return lib().gfdm_hip_resampler_n_taps(self._h)
+
+    def n_phases(self):
+        return lib().gfdm_hip_resampler_n_phases(self._h)
+
+    def interp(self):
+        return "linear" if lib().gfdm_hip_resampler_interp(self._h) else "nearest"
+
+    def taps(self):
+        """the table as given to the constructor (float32 (n_phases + 1, n_taps), bit for bit)"""
+        t = np.empty((self.n_phases() + 1, self.n_taps()), np.float32)
+        _check(lib().gfdm_hip_resampler_taps(self._h, t.ctypes.data))
+        return t
+
+    def step(self):
+        v = ctypes.c_uint64()
+        _check(lib().gfdm_hip_resampler_step(self._h, ctypes.byref(v)))
+        return v.value
+
+    def set_step(self, step_or_ratio):
+        _check(lib().gfdm_hip_resampler_set_step(self._h, self._step_of(step_or_ratio)))
+
+    def plan(self, n_in, pos=0, flush=True):
+        """(n_out, advance, next_pos) of a piece of n_in samples read from position pos (Q32.32, relative to its first sample): the outputs
+        whose whole window lies inside the piece -- with flush those up to its end, zeros behind it --, how many samples the next piece
+        starts further on, and its pos; the next piece passes history = min((n_taps - 1) // 2, samples in front of it).  Host arithmetic."""
+        n_out, adv, nxt = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().gfdm_hip_resampler_plan(self.step(), self._T, int(pos), int(n_in), int(bool(flush)), ctypes.byref(n_out), ctypes.byref(adv),
+                                             ctypes.byref(nxt)))
+        return n_out.value, adv.value, nxt.value
+
+    def resample(self, x, history=0, pos=0, n_out=None, flush=True, out=None, stream=None):
+        """x holds history + n_in samples; output i is the interpolated value at input position (pos + i * step) / 2^32, counted from
+        x[history]; what lies in front of x and behind it is zeros.  n_out: None takes plan(n_in, pos, flush)'s.  numpy x -> numpy result
+        (host path); a torch device tensor -> a tensor on its device (device path, current stream unless given).  complex64 samples, or
+        int16 I/Q of shape (n, 2) or (2n,) (sc16, read as it is).  The result is complex64 always."""
+        x, size, infix = ops.capture(x, self._dev, "x")
+        ops.check_result(out, x, C64, self._dev, as_what="x")
+        history, pos = int(history), int(pos)
+        if history < 0 or history > size:
+            raise ValueError("history(%d) must lie in 0 .. the size of x(%d)" % (history, size))
+        n_in = size - history
+        if n_out is None:
+            n_out = self.plan(n_in, pos, flush)[0]
+        n_out = int(n_out)
+        if n_out < 0:
+            raise ValueError("n_out(%d) must be >= 0" % n_out)
+        res = ops.stream_result(x, n_out, False, self._dev, out, "x")
+        sb = 4 if infix else 8
+        self._run("gfdm_hip_resampler_resample" + infix, x, (ops.ptr(res), ops.ptr(x) + sb * history, n_out, n_in, history, pos), stream)
         return res
 
 

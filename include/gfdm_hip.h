@@ -759,7 +759,7 @@ int gfdm_hip_symbol_mapper_soft_device(gfdm_hip_symbol_mapper* m, void* out, con
 /* ---- gfdm_hip_channel_model: multipath, frequency offset and noise on a stream, complex64 or sc16 out ------------------------------
  * The link between the burst shaper's TX stream and the synchroniser's capture: GNU Radio's channels.channel_model(noise_voltage,
  * frequency_offset, epsilon, taps, noise_seed) as the reference's end-to-end flowgraph places it (examples/gfdm_simulation_demo.grc),
- * with epsilon = 1 (the demo's value; resampling is not part of this).  Order as in GNU Radio: FIR, then mixer, then noise.  The taps
+ * with epsilon = 1 (the demo's value; resampling is not part of this: gfdm_hip_resampler below).  Order as in GNU Radio: FIR, then mixer, then noise.  The taps
  * are fixed at create; frequency_offset, noise_voltage and seed are host state with setters, read when a call is enqueued -- a captured
  * graph keeps the values it was captured with.
  * With T = n_taps, h the taps as given (complex64), f = frequency_offset in cycles per sample, s = noise_voltage, a = offset + i the
@@ -822,6 +822,82 @@ int gfdm_hip_channel_model_apply_sc16_host(gfdm_hip_channel_model* c, int16_t* o
                                            double gain);
 int gfdm_hip_channel_model_apply_sc16_device(gfdm_hip_channel_model* c, void* out, const void* in, int64_t n, int64_t history, int64_t offset,
                                              double gain, void* stream);
+
+/* ---- gfdm_hip_resampler: fractional-rate resampling of a stream, complex64 or sc16 in, complex64 out -------------------------------
+ * The stage the channel model above leaves out (GNU Radio's channels.channel_model starts with a fractional resampler driven by
+ * epsilon), and the conversion of a capture taken at a radio's rate to the GFDM rate in front of detect: place -> resample -> apply,
+ * capture -> resample -> detect.  A polyphase interpolator that does the work of GNU Radio's mmse_resampler_cc /
+ * pfb_arb_resampler_ccf.  Positions are integers (unsigned Q32.32), so every result is a pure function of its arguments and a stream
+ * cut into calls at any point gives the same samples to the bit.  Bit-compatibility with GNU Radio's MMSE tap table is unpinned: the
+ * table is the caller's (gfdm_amd.resampler_taps builds a Kaiser-windowed sinc).
+ * create: T = n_taps in 1 .. 64; L = n_phases a power of two in 1 .. 1024, lg = log2 L; taps: (L + 1) * T real fp32 values, row p, tap
+ *   t, h[p][t] = taps[p * T + t], row L being row 0 moved by one sample as in GNU Radio's table; (L + 1) * T <= 8256; interp 0 (the
+ *   nearest row, GNU Radio's mmse rule) or 1 (linear between neighbouring rows); step = the input advance per output sample as unsigned
+ *   Q32.32, 2^29 <= step <= 2^35 (1/8 .. 8).  Table and interp are fixed at create; step is host state with a setter, read when a call
+ *   is enqueued -- a captured graph keeps the value it was captured with.
+ * With D = (T - 1) / 2 in integer division and pos the Q32.32 position of output 0 relative to in[0], for 0 <= i < n_out:
+ *     P(i)   = pos + i * step                 an exact integer below 2^94: the product from mul-hi / mul-lo, there is no float
+ *     idx    = P >> 32,   frac = P & (2^32 - 1)
+ *     interp 0:  p = (frac + 2^(31 - lg)) >> (32 - lg)  in 0 .. L     (in 64 bits, so that L = 1 shifts by 32: p = frac >> 31),
+ *                c[t] = h[p][t]
+ *     interp 1:  q = frac >> (32 - lg)  in 0 .. L - 1                   (in 64 bits; L = 1: q = 0),
+ *                w = fp32 of ((frac << lg) mod 2^32) >> 8, times 2^-24   (the next 24 bits of frac below q's bits -- for lg > 8 the
+ *                    last lg - 8 of them lie below frac's end and are zeros; exact; L = 1: the top 24 bits of frac),
+ *                c[t] = fmaf(w, d[q][t], h[q][t]),   d[q][t] = fp32(h[q + 1][t] - h[q][t])   (one rounding; the kernel forms it from
+ *                    the two rows where it needs it, which is that same rounding, so there is no second table)
+ *     x[j]   = in[j] for -history <= j < n_in,  0 elsewhere              (as the extractor reads zeros past the capture)
+ *     y[i]   = sum_{t < T} c[t] * x[idx - D + t]      fp32 per component: the first term a product, then one fma per tap, t ascending
+ *   So T = 1, h = 1, step = 2^32, pos = 0 copies x bit for bit, and a table whose row 0 is the unit impulse at tap D copies every
+ *   finite non-zero component bit for bit at step = 2^32, pos = 0 (a zero component may come out as +0: the chain starts from 0 * x).
+ * plan(step, n_taps, pos, n_in, flush, &n_out, &advance, &next_pos): host arithmetic alone, no handle and no device.  n_out = the
+ *   number of i >= 0 with idx(i) - D + T - 1 < n_in (every sample of the window is there), with flush != 0 with idx(i) < n_in (the last
+ *   piece: zeros lie behind the end); advance = min(n_in, idx(n_out)); next_pos = pos + n_out * step - advance * 2^32.  The next piece
+ *   passes in + advance, next_pos and history = min(D, samples in front of it).  Any of the three result pointers may be NULL.
+ * resample_*: `in` points at sample 0; the `history` samples in front of it are readable.  The sc16 twins read interleaved int16 I/Q,
+ *   widened exactly, one 4-byte load per sample: bit-equal to the complex64 call on the widened capture.  Output is always complex64.
+ * *_device: element alignment only (out 8 bytes; in 8, sc16 4) with 64-bit byte offsets; out overlapping [in - history, in + n_in) is
+ *   GFDM_HIP_EINVAL; n_out == 0 returns GFDM_HIP_OK without a launch; no workspace, no allocation, no synchronisation: one kernel,
+ *   hipGraph-capturable.  A workgroup owns tiles of consecutive outputs cut at 16-byte boundaries of memory; per tile the input span
+ *   [idx(first) - D, idx(last) - D + T) goes to LDS once (zeros and the widening applied there), the table once per workgroup; the
+ *   stream is written in 16-byte stores aligned in memory whatever the alignment of out, its first and last sample alone if need be.
+ * *_host: a convenience, not a pipeline: uploads history + n_in samples, runs the device call, downloads n_out.
+ * Error budget against the same formulas with Python integers for P, idx, frac, p, q, w and float64 for c and the sum, on the same
+ *   fp32 table and samples, with S_i = sum_t |c[t]| |x[idx - D + t]|:
+ *     |y - y64| <= (T + 4) * 2^-23 * S_i       (one fma for c, the length-T chain, the final rounding).  Derived, not measured.
+ * GFDM_HIP_EINVAL from check (the argument table alone, without a handle or a device), from create, set_step, plan and every call:
+ *   n_taps outside 1 .. 64; n_phases no power of two in 1 .. 1024; (L + 1) * T > 8256; interp not 0 or 1; step outside 2^29 .. 2^35; a
+ *   non-finite tap (create); n_out, n_in, history or pos negative; pos >= 2^62; pos + n_out * step >= 2^94; a byte size (8 n_out,
+ *   8 (history + n_in)) that overflows int64 -- in plan: an n_out whose 8 n_out would.  Also: a NULL buffer that the call would touch
+ *   (`in` may be NULL when history + n_in == 0: every x is zero).
+ * Tested range (against the restatement of tests/resampler_ref.py): T 1, 2, 3, 8, 16, 64; L 1, 2, 128, 1024 within the cap; both
+ *   interp; n_out 1, 2, 3, 255, 256, 257, 4097, 65539; step 2^29, 2^32, 2^32 + 1, round(1.0001 * 2^32), 3 * 2^31, 2^35; pos with
+ *   fraction 0, 2^31, 2^32 - 1 and integer part 0 and 5; history 0, 1, D - 1, D, D + 5; n_in short of the last windows; in and out at
+ *   every alignment of one element, complex64 and sc16 in -- 24 cases per T that go round these values with the case number, not their
+ *   cross product: every value occurs with every T, not with every other value.  End to end: a clock offset of 100 ppm with half a
+ *   sample of static offset between place and apply, and a 4/5 - 5/4 rate change around apply (8 taps, complex64 and sc16 between).
+ *   Accuracy of the default table (gfdm_amd.resampler_taps) on a tone, measured on the restatement: linear is never worse than nearest,
+ *   and T = 16 is not worse than T = 8 with linear; with the nearest row the error is the row's position error, about pi f / L whatever
+ *   T is, and T = 16 measured 0.07 % ABOVE T = 8 at L = 32 (1.0801e-2 against 1.0794e-2): "more taps are not worse" is tested for linear
+ *   alone, and nearest is held to pi f / L + the linear error instead.  Worst measured share of the error budget: 0.163 over the table of shapes (T = 1;
+ *   0.157, 0.138, 0.106, 0.064, 0.021 for T = 2, 3, 8, 16, 64), 0.113 on sc16 input (profiles/r19/resampler_accuracy.json). */
+typedef struct gfdm_hip_resampler gfdm_hip_resampler;
+int gfdm_hip_resampler_create(gfdm_hip_resampler** out, const float* taps, int n_taps, int n_phases, int interp, uint64_t step, int device);
+int gfdm_hip_resampler_destroy(gfdm_hip_resampler* c);
+int gfdm_hip_resampler_n_taps(const gfdm_hip_resampler* c);
+int gfdm_hip_resampler_n_phases(const gfdm_hip_resampler* c);
+int gfdm_hip_resampler_interp(const gfdm_hip_resampler* c);
+int gfdm_hip_resampler_taps(const gfdm_hip_resampler* c, float* taps);          /* (n_phases + 1) * n_taps floats */
+int gfdm_hip_resampler_step(const gfdm_hip_resampler* c, uint64_t* step);
+int gfdm_hip_resampler_set_step(gfdm_hip_resampler* c, uint64_t step);
+int gfdm_hip_resampler_check(int n_taps, int n_phases, int interp, uint64_t step, int64_t n_out, int64_t n_in, int64_t history, int64_t pos);
+int gfdm_hip_resampler_plan(uint64_t step, int n_taps, int64_t pos, int64_t n_in, int flush, int64_t* n_out, int64_t* advance, int64_t* next_pos);
+int gfdm_hip_resampler_resample_host(gfdm_hip_resampler* c, float* out, const float* in, int64_t n_out, int64_t n_in, int64_t history, int64_t pos);
+int gfdm_hip_resampler_resample_device(gfdm_hip_resampler* c, void* out, const void* in, int64_t n_out, int64_t n_in, int64_t history, int64_t pos,
+                                       void* stream);
+int gfdm_hip_resampler_resample_sc16_host(gfdm_hip_resampler* c, float* out, const int16_t* in, int64_t n_out, int64_t n_in, int64_t history,
+                                          int64_t pos);
+int gfdm_hip_resampler_resample_sc16_device(gfdm_hip_resampler* c, void* out, const void* in, int64_t n_out, int64_t n_in, int64_t history,
+                                            int64_t pos, void* stream);
 
 /* ---- gfdm_hip_link_meter: which burst a detection is, bit errors and error-vector power per row, counters on the device ------------
  * Behind the receivers and beside the symbol mapper's decode: what a BER or EVM curve point needs so that it is one fixed-shape,
