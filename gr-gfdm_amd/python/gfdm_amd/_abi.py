@@ -159,6 +159,14 @@ def _signatures():
     fn("resampler_plan", i32, u64, i32, i64, i64, i32, out(i64), out(i64), out(i64))
     call("resampler_resample", vp, vp, i64, i64, i64, i64, sc16=())
 
+    # ---- fading model: four tables at create, the channel model's call ----
+    fn("fading_model_create", i32, out(vp), vp, vp, vp, vp, i32, i32, i32, i32)
+    getters("fading_model", "destroy n_paths n_sinusoids n_taps")
+    for name in ("taps", "amplitudes", "frequencies", "phases"):
+        fn("fading_model_" + name, i32, vp, vp)
+    fn("fading_model_check", i32, i32, i32, i32, i64, i64, i64, f64)
+    call("fading_model_apply", vp, vp, i64, i64, i64, sc16=(f64,))
+
     # ---- symbol mapper and link meter ----
     for kind in ("symbol_mapper", "link_meter"):
         fn(kind + "_create", i32, out(vp), vp, i32, i32, i32)

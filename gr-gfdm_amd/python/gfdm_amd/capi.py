@@ -1169,6 +1169,167 @@ class ChannelModel(_Kernel):
         return res
 
 
+_U64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _mix64(z):
+    """the splitmix64 finaliser on a Python int below 2^64 (what synth._mix64 does on tensors)"""
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
+    return z ^ (z >> 31)
+
+
+def _fading_hash(seed, p, s, w):
+    return _mix64((_mix64(((int(seed) & _U64) * _GOLDEN + (p << 40 | s << 8 | w)) & _U64) + _GOLDEN) & _U64)
+
+
+def fading_taps(delays, mags, ntaps):
+    """FadingModel's delay-line table: c[p][k] = mags[p] * sinc(k - delays[p]), float32 of shape (len(delays), ntaps), computed in float64;
+    delays in samples within [0, ntaps - 1] (an integer delay gives a one-hot row times mags[p] exactly).  The truncated sinc of GNU
+    Radio's selective_fading_model, without its window; numpy alone, no device."""
+    d = np.atleast_1d(np.asarray(delays, np.float64))
+    m = np.atleast_1d(np.asarray(mags, np.float64))
+    T = int(ntaps)
+    if d.ndim != 1 or m.shape != d.shape or d.size < 1:
+        raise ValueError("delays and mags must be two vectors of one length >= 1")
+    if T < 1 or T > 64:
+        raise ValueError("ntaps(%d) must lie in 1 .. 64" % T)
+    if not (np.all(np.isfinite(d)) and np.all(np.isfinite(m))) or d.min() < 0 or d.max() > T - 1:
+        raise ValueError("delays must be finite and lie in [0, ntaps - 1], mags must be finite")
+    u = np.arange(T)[None, :] - d[:, None]
+    s = np.sinc(u)
+    whole = u == np.rint(u)
+    s[whole] = (u[whole] == 0).astype(np.float64)
+    return (m[:, None] * s).astype(np.float32)
+
+
+def fading_sinusoids(n_paths, N, fDTs, seed, los=False, k_factor=0.0):
+    """FadingModel's sinusoid tables (A float32, F int64, phase0 uint64), each of shape (n_paths, N + (1 if los else 0)): a stratified
+    Monte-Carlo Clarke model.  With hash(seed, p, s, w) = mix(mix(seed * 0x9E3779B97F4A7C15 + (p << 40 | s << 8 | w)) + 0x9E3779B97F4A7C15)
+    in uint64 wrap-around, mix the splitmix64 finaliser: scatter sinusoid s of path p arrives at alpha = 2 pi (s + u) / N with
+    u = hash(seed, p, s, 0) 2^-64, F = rint(fDTs cos(alpha) 2^64), phase0 = hash(seed, p, s, 1), A = sqrt(1 / (N (1 + k))), k = k_factor on
+    path 0 when los is set and 0 otherwise.  With los every path has sinusoid number N: on path 0 at the angle 2 pi hash(seed, 0, N, 0) 2^-64
+    with phase hash(seed, 0, N, 1) and A = sqrt(k / (k + 1)), on the other paths A = 0.  The ensemble autocorrelation of a path is
+    J0(2 pi fDTs tau) and E|g|^2 = 1.  Not bit-compatible with GNU Radio's fader (unpinned); numpy alone, no device."""
+    P, N, fd, k_factor = int(n_paths), int(N), float(fDTs), float(k_factor)
+    S = N + (1 if los else 0)
+    if P < 1 or P > 8:
+        raise ValueError("n_paths(%d) must lie in 1 .. 8" % P)
+    if N < 1 or S > 17:
+        raise ValueError("N(%d) must be >= 1 and give at most 17 sinusoids a path" % N)
+    if not np.isfinite(fd) or abs(fd) > 0.5:
+        raise ValueError("fDTs must be finite and lie in [-0.5, 0.5] cycles per sample")
+    if not np.isfinite(k_factor) or k_factor < 0:
+        raise ValueError("k_factor must be finite and >= 0")
+    A, F, ph = np.zeros((P, S), np.float32), np.zeros((P, S), np.int64), np.zeros((P, S), np.uint64)
+
+    def freq(alpha):
+        return min(int(np.rint(fd * np.cos(alpha) * 2.0 ** 64)), (1 << 63) - 1)          # float64; +0.5 cycles is the one value past int64
+
+    for p in range(P):
+        k = k_factor if (los and p == 0) else 0.0
+        for s in range(N):
+            u = _fading_hash(seed, p, s, 0) * 2.0 ** -64
+            F[p, s] = freq(2 * np.pi * (s + u) / N)
+            ph[p, s] = _fading_hash(seed, p, s, 1)
+            A[p, s] = np.sqrt(1.0 / (N * (1.0 + k)))
+        if los and p == 0:
+            F[p, N] = freq(2 * np.pi * (_fading_hash(seed, 0, N, 0) * 2.0 ** -64))
+            ph[p, N] = _fading_hash(seed, 0, N, 1)
+            A[p, N] = np.sqrt(k / (k + 1.0))
+    return A, F, ph
+
+
+class FadingModel(_Kernel):
+    """Time-varying multipath on a stream, on the device (contract in include/gfdm_hip.h, gfdm_hip_fading_model): GNU Radio's
+    channels.selective_fading_model in its argument order -- N sinusoids a path, fDTs the maximum Doppler in cycles per sample, LOS / K a
+    Rician first path, delays and mags of the paths, ntaps of the delay lines -- in front of ChannelModel.apply(taps = [1]), which keeps
+    the frequency offset and the noise.  y[i] = sum_p g_p(offset + i) * sum_k c[p][k] x[i - k] with g_p a sum of sinusoids of the absolute
+    index, from fading_sinusoids(len(delays), N, fDTs, seed, LOS, K) and fading_taps(delays, mags, ntaps); from_tables takes the four
+    tables as they are.  Everything is fixed at create: another Doppler is another FadingModel.  Not bit-compatible with GNU Radio's
+    fader (unpinned)."""
+    _destroy = "gfdm_hip_fading_model_destroy"
+
+    def __init__(self, N=8, fDTs=0.0, LOS=False, K=4.0, seed=0, delays=(0.0,), mags=(1.0,), ntaps=1, device=None):
+        c = fading_taps(delays, mags, ntaps)
+        A, F, ph = fading_sinusoids(c.shape[0], N, fDTs, seed, bool(LOS), K)
+        self._create(c, A, F, ph, device)
+
+    @classmethod
+    def from_tables(cls, c, A, F, phase0, device=None):
+        """c float32 (P, T), A float32 (P, S), F int64 (P, S) in 2^-64 cycles per sample, phase0 uint64 (P, S) in 2^-64 turns"""
+        self = object.__new__(cls)
+        self._create(c, A, F, phase0, device)
+        return self
+
+    def _create(self, c, A, F, ph, device):
+        c, A = np.ascontiguousarray(c, dtype=np.float32), np.ascontiguousarray(A, dtype=np.float32)
+        F, ph = np.asarray(F), np.asarray(ph)
+        if F.dtype.kind not in "iu" or ph.dtype.kind not in "iu":
+            raise TypeError("F and phase0 must be integers (2^-64 cycles per sample, 2^-64 turns), not %s and %s" % (F.dtype, ph.dtype))
+        F, ph = np.ascontiguousarray(F.astype(np.int64)), np.ascontiguousarray(ph.astype(np.uint64))       # (two's complement either way)
+        if c.ndim != 2 or A.ndim != 2 or c.shape[0] != A.shape[0] or F.shape != A.shape or ph.shape != A.shape:
+            raise ValueError("the tables must have the shapes c (P, T) and A, F, phase0 (P, S), not %s, %s, %s, %s"
+                             % (tuple(c.shape), tuple(A.shape), tuple(F.shape), tuple(ph.shape)))
+        h = ctypes.c_void_p()
+        dev = 0 if device is None else int(device)
+        _check(lib().gfdm_hip_fading_model_create(ctypes.byref(h), c.ctypes.data, A.ctypes.data, F.ctypes.data, ph.ctypes.data, A.shape[0], A.shape[1],
+                                                  c.shape[1], dev))
+        self._h = h
+        self._dev = dev
+
+    def n_paths(self):
+        return lib().gfdm_hip_fading_model_n_paths(self._h)
+
+    def n_sinusoids(self):
+        return lib().gfdm_hip_fading_model_n_sinusoids(self._h)
+
+    def n_taps(self):
+        return lib().gfdm_hip_fading_model_n_taps(self._h)
+
+    def _table(self, name, width, dtype):
+        t = np.empty((self.n_paths(), width), dtype)
+        _check(getattr(lib(), "gfdm_hip_fading_model_" + name)(self._h, t.ctypes.data))
+        return t
+
+    def taps(self):
+        """c as given at create (float32 (P, T), bit for bit)"""
+        return self._table("taps", self.n_taps(), np.float32)
+
+    def amplitudes(self):
+        return self._table("amplitudes", self.n_sinusoids(), np.float32)
+
+    def frequencies(self):
+        return self._table("frequencies", self.n_sinusoids(), np.int64)
+
+    def phases(self):
+        return self._table("phases", self.n_sinusoids(), np.uint64)
+
+    def apply(self, x, history=0, offset=0, out=None, gain=1.0, sc16=None, stream=None):
+        """x holds history + n samples, the result has n: sample i of the result is the faded x[history + i], whose absolute index is
+        offset + i; the first `history` samples are the delay lines' past (what lies before them is zeros).  A stream cut into calls
+        gives the samples of one call, to the bit, when each piece passes history = min(n_taps - 1, samples before it) and its offset.
+        numpy x -> numpy result (host path); a torch complex64 device tensor -> a tensor on its device (device path, current stream
+        unless given).  An int16 `out` (or sc16=True) selects int16 I/Q of shape (n, 2), truncated and saturated, of y * gain."""
+        if sc16 is None:
+            sc16 = out is not None and str(getattr(out, "dtype", "")).replace("torch.", "") == "int16"
+        sc16 = bool(sc16)
+        if not sc16 and float(gain) != 1.0:
+            raise ValueError("gain scales sc16 output: pass an int16 out or sc16=True (complex64 output is not scaled)")
+        x = ops.operand(x, C64, "x", self._dev, floating=True)
+        ops.check_result(out, x, I16 if sc16 else C64, self._dev, as_what="x")
+        history, offset = int(history), int(offset)
+        size = ops.size(x)
+        if history < 0 or history > size:
+            raise ValueError("history(%d) must lie in 0 .. the size of x(%d)" % (history, size))
+        n = size - history
+        res = ops.stream_result(x, n, sc16, self._dev, out, "x")
+        self._run("gfdm_hip_fading_model_apply" + ("_sc16" if sc16 else ""), x,
+                  (ops.ptr(res), ops.ptr(x) + 8 * history, n, history, offset) + ((float(gain),) if sc16 else ()), stream)
+        return res
+
+
 def resampler_step(x):
     """Resampler's step for a rate `x` (input samples per output sample, a float or a fractions.Fraction): x * 2^32 rounded to the nearest
     integer (ties to even), the unsigned Q32.32 of the contract.  1.0 -> 2^32.  A Fraction is converted exactly."""

@@ -899,6 +899,86 @@ int gfdm_hip_resampler_resample_sc16_host(gfdm_hip_resampler* c, float* out, con
 int gfdm_hip_resampler_resample_sc16_device(gfdm_hip_resampler* c, void* out, const void* in, int64_t n_out, int64_t n_in, int64_t history,
                                             int64_t pos, void* stream);
 
+/* ---- gfdm_hip_fading_model: time-varying multipath on a stream, complex64 or sc16 out ------------------------------------------------
+ * The channel that changes from burst to burst, in front of the channel model above (whose FIR is fixed at create and which keeps the
+ * frequency offset and the noise): place -> [resample] -> fade -> apply(taps = [1], f, noise) -> detect.  What GNU Radio's
+ * channels.fading_model / channels.selective_fading_model do in a flowgraph: P paths, each a real delay line (a fractional delay times
+ * a magnitude) times a complex gain that is a sum of sinusoids (Clarke's model, a line-of-sight term being one more sinusoid).  The
+ * phases are 64-bit integers, so every output is a pure function of the tables and the ABSOLUTE sample index and a stream cut into calls
+ * at any point gives the same samples to the bit.  Bit-compatibility with GNU Radio's fader is unpinned: its arrival angles walk
+ * randomly from sample to sample and so cannot be a function of the index; the tables are the caller's (gfdm_amd.fading_taps and
+ * gfdm_amd.fading_sinusoids build a stratified Monte-Carlo Clarke model from a seed).
+ * create: P = n_paths in 1 .. 8, S = n_sinusoids in 1 .. 17, T = n_taps in 1 .. 64; four tables, fixed at create, copied to the device
+ *   there, read back by the getters bit for bit:
+ *     c   [P][T] fp32      real delay-line coefficients of path p
+ *     A   [P][S] fp32      amplitude of sinusoid s of path p
+ *     F   [P][S] int64     frequency, signed, in units of 2^-64 cycles per sample
+ *     Ph0 [P][S] uint64    start phase in units of 2^-64 turns
+ *   There are no setters: another Doppler is another handle.
+ * With a = offset + i the ABSOLUTE index of sample i of the call, for 0 <= i < n:
+ *     x[j]         = in[j] for -history <= j < n,  0 for j < -history           (history as in the channel model)
+ *     Phi[p][s](a) = (F[p][s] * a + Ph0[p][s]) mod 2^64                         64-bit wrap-around integers, exact
+ *     e[p][s](a)   = exp(j 2 pi (Phi >> 32) / 2^32)                             the top 32 bits are the phase
+ *     g[p](a)      = sum_s A[p][s] * e[p][s](a)
+ *     v[p][i]      = sum_{k < T} c[p][k] * x[i - k]
+ *     y[i]         = sum_p g[p](a) * v[p][i]
+ * In fp32, no fp64 on the device.  The phasors are formed per aligned run of eight absolute indices 8 r .. 8 r + 7: at 8 r from the
+ *   integer phase (its nearest 24 bits through sincospif, whose argument is then exact, the remaining 8 by a first-order turn), times A;
+ *   at 8 r + m by at most three complex products with exp(j 2 pi F m' / 2^64), m' = 1, 2, 4, which create tabulates from fp64.  The runs
+ *   are aligned in a, not in i, so the value of a sample does not depend on where a call or a tile begins.  g sums s ascending from 0;
+ *   v is one fma per tap and component, k ascending from 0; y sums p ascending from 0, two fmas per component.  Every step is linear in x,
+ *   so scaling x by a power of two scales y exactly; A = 1, F = 0, Ph0 = 0, c = 1 returns x equal in every finite component.
+ * sc16 twin: interleaved int16 q(y.re * gain), q(y.im * gain), the products in fp32 from the same fp32 y as the complex64 call, q the
+ *   burst shaper's rule (truncate toward zero, saturate, NaN -> 0).
+ * Error budget against the same formulas in float64 on the same complex64 inputs, with Abar_p = sum_s |A[p][s]| and
+ *   S_pi = sum_k |c[p][k]| |x[i - k]|:
+ *     |y - y64| <= (T + P + 16) * 2^-23 * sum_p Abar_p * S_pi
+ *   (the length-T real-by-complex fma chain per path; a phasor per sinusoid -- the phase's last bits, <= 2 ulp sincospi, the product with
+ *   A -- with its rotations behind it; the sums over s and p).  Counted from roundings, not from what the kernel gives.
+ * *_device: in and out are device arrays with the alignment of one element and no more (8 bytes, sc16 out 4 bytes); byte offsets are
+ *   64-bit.  out overlapping [in - history, in + n) is GFDM_HIP_EINVAL: the delay lines read neighbours, there is no in-place call.  No
+ *   workspace, no allocation, no synchronisation: one kernel, hipGraph-capturable.  Every input sample is read from memory once per tile
+ *   of 2040 output samples (plus the T + 14 samples around the tile); the stream is written in 16-byte stores aligned in memory whatever
+ *   the alignment of out and the value of offset are, the first and last samples of an unaligned stream one by one.  At most 2048
+ *   workgroups per launch, which stride over the tiles beyond.
+ * *_host: a convenience, not a pipeline: uploads history + n samples, runs the device call, downloads n.
+ * GFDM_HIP_EINVAL from check (the argument table alone, without a handle or a device), from create and every call: n_paths outside
+ *   1 .. 8, n_sinusoids outside 1 .. 17, n_taps outside 1 .. 64; a NULL table, a non-finite c or A (create); a non-finite gain; n,
+ *   history or offset negative; offset + n > 2^62; a byte size (8 (history + n)) that overflows int64.  Also: a NULL buffer that the
+ *   call would touch.  n == 0 returns GFDM_HIP_OK without a launch.
+ * Tested range (against the float64 numpy restatement of tests/fading_model_ref.py, whose phases are held to Python integers):
+ *   (P, S, T) (1, 1, 1), (1, 8, 1), (2, 3, 3), (4, 8, 16), (8, 17, 64); n 1, 2, 7, 8, 9, 255, 256, 257, 4097, 65539; history 0, 1,
+ *   T - 2, T - 1, T + 5; offset 0, 1, 7, 2^31 - 1, 2^33 - 3, 2^40 + 1; in and out at every alignment of one element, complex64 and
+ *   sc16 -- 20 cases per shape that go round these values with the case number; 2 * 2048 + 3 tiles in one launch.
+ *   Bit for bit: a stream in one call against the same stream cut at 1, 7, 8, 9 and at a seeded ragged list of points; sc16 against
+ *   q(fp32 y * gain) of the complex64 call; apply(4 x) against 4 apply(x); host flavour against device flavour; a graph replay against
+ *   the eager call.  Against the channel model: every F = 0 against its FIR with the taps sum_p g_p c[p][:], and P = S = T = 1 against
+ *   its mixer at f = 0.002, 1/3, -0.5 and offsets up to 2^33, within the two budgets added (worst 0.31 of them, at f = 1/3 and 2^33,
+ *   where the channel model's float64 product f * a carries 2^-22 of a cycle).  Worst measured share of the error budget: 0.119 over the
+ *   table of shapes (P = S = T = 1; 0.074, 0.054, 0.016, 0.006 for the other four shapes in the order above), 0.055 past the bounded
+ *   grid, 0.020 on the faded stream of the end-to-end loop; a float32 numpy emulation of the same scheme without fused multiply-adds
+ *   reaches 0.134, and its gains alone 1.7 * 2^-23 * Abar of the 12 that the budget grants them.  sc16 differs from q of the float64
+ *   value only inside gain * budget of a step of q (at most 0.6 % of the components of a tested case), by one LSB
+ *   (profiles/r20/fading_accuracy.json). */
+typedef struct gfdm_hip_fading_model gfdm_hip_fading_model;
+int gfdm_hip_fading_model_create(gfdm_hip_fading_model** out, const float* c, const float* A, const int64_t* F, const uint64_t* Ph0, int n_paths,
+                                 int n_sinusoids, int n_taps, int device);
+int gfdm_hip_fading_model_destroy(gfdm_hip_fading_model* m);
+int gfdm_hip_fading_model_n_paths(const gfdm_hip_fading_model* m);
+int gfdm_hip_fading_model_n_sinusoids(const gfdm_hip_fading_model* m);
+int gfdm_hip_fading_model_n_taps(const gfdm_hip_fading_model* m);
+int gfdm_hip_fading_model_taps(const gfdm_hip_fading_model* m, float* c);                 /* n_paths * n_taps */
+int gfdm_hip_fading_model_amplitudes(const gfdm_hip_fading_model* m, float* A);          /* n_paths * n_sinusoids, as the two below */
+int gfdm_hip_fading_model_frequencies(const gfdm_hip_fading_model* m, int64_t* F);
+int gfdm_hip_fading_model_phases(const gfdm_hip_fading_model* m, uint64_t* Ph0);
+int gfdm_hip_fading_model_check(int n_paths, int n_sinusoids, int n_taps, int64_t n, int64_t history, int64_t offset, double gain);
+int gfdm_hip_fading_model_apply_host(gfdm_hip_fading_model* m, float* out, const float* in, int64_t n, int64_t history, int64_t offset);
+int gfdm_hip_fading_model_apply_device(gfdm_hip_fading_model* m, void* out, const void* in, int64_t n, int64_t history, int64_t offset, void* stream);
+int gfdm_hip_fading_model_apply_sc16_host(gfdm_hip_fading_model* m, int16_t* out, const float* in, int64_t n, int64_t history, int64_t offset,
+                                          double gain);
+int gfdm_hip_fading_model_apply_sc16_device(gfdm_hip_fading_model* m, void* out, const void* in, int64_t n, int64_t history, int64_t offset,
+                                            double gain, void* stream);
+
 /* ---- gfdm_hip_link_meter: which burst a detection is, bit errors and error-vector power per row, counters on the device ------------
  * Behind the receivers and beside the symbol mapper's decode: what a BER or EVM curve point needs so that it is one fixed-shape,
  * hipGraph-capturable sequence of launches with one 96-byte read at the end.  Rows are bursts or frames as for the symbol mapper.
