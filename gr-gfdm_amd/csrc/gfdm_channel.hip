@@ -2,38 +2,33 @@
 // continuous stream, complex64 or interleaved int16 I/Q out (GNU Radio's channels.channel_model with epsilon = 1, as the reference's
 // end-to-end flowgraph uses it: examples/gfdm_simulation_demo.grc).  The contract is written out in include/gfdm_hip.h.
 //
-// One kernel, k_channel<SC16>.  As in k_shaper_place the OUTPUT is tiled: the stream is cut into 16-byte vectors aligned in memory (2
-// complex64 or 4 sc16 samples), a workgroup takes kTile samples' worth of them.  Per tile
-//   1. the input samples [i_lo - T, i_hi + 1) -- the tile, its T - 1 halo and one more at either end for the pairs of step 2 -- go to
-//      LDS once, in 16-byte loads aligned in memory, sample by sample where history, n or the alignment of `in` cuts a vector;
+// One kernel, k_channel<SC16>, a stream stage (gfdm_streamtile.h: the output tiles, step 1 and step 3) with tiles of kTile samples.
+//   1. the halo: the input samples [i_lo - T, i_hi + 1) -- the tile, its T - 1 past samples and one more at either end for the pairs of step 2;
 //   2. a lane owns aligned PAIRS of absolute sample indices (2p, 2p + 1): one Philox call serves both.  Whatever the parity of `offset`
-//      and the alignment of `out` are, a tile meets at most kTile / 2 + 1 pairs, which is why kTile is 2044 and not 2048: four pairs a
-//      lane.  FIR (LDS reads shared by the two samples), mixer, noise, and the results go to a second LDS array in output format;
-//   3. the tile leaves in 16-byte stores aligned in memory; the first and last samples of an unaligned stream go out one by one.
+//      and the alignment of `out` are, a tile meets at most max_groups(kTile, 2) pairs, which is why kTile is 2044 and not 2048: four
+//      pairs a lane.  FIR (LDS reads shared by the two samples), mixer, noise, and the results go to a second LDS array in output format.
 // T, the all-real-taps case, f == 0 and s == 0 are launch-uniform branches; the taps are kernel arguments.
 #include "../../include/gfdm_hip.h"
 #include "gfdm_hostcall.h"
 #include "gfdm_philox.h"
-#include "gfdm_sc16out.h"
+#include "gfdm_streamtile.h"
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 
 using gfdm::cf;
 using gfdm::api_fail;
-using gfdm::misaligned;
 
 namespace {
 
 constexpr int kLanes = 256;
 constexpr int kMaxTaps = 64;
-constexpr int kTile = 2044;               // samples per tile: a multiple of 4 with kTile / 2 + 1 <= kPairsPerLane * kLanes
+constexpr int kTile = 2044;               // samples per tile: a multiple of 4 whose pairs fit kPairsPerLane * kLanes
 constexpr int kPairsPerLane = 4;
-constexpr int kStage = kTile + kMaxTaps + 4;      // input samples in LDS: tile + T + 1, + 1 for the alignment of the first vector, rounded up to even
+constexpr int kStage = kTile + kMaxTaps + 4;      // input samples in LDS
 constexpr int kMaxTiles = 8192;           // workgroups per launch; the tiles beyond are strided over
-constexpr int64_t kMaxIndex = (int64_t)1 << 62;
-static_assert(kTile % 4 == 0 && kTile / 2 + 1 <= kPairsPerLane * kLanes && kStage % 2 == 0, "tile geometry");
+static_assert(kTile % 4 == 0 && gfdm::max_groups(kTile, 2) <= kPairsPerLane * kLanes, "tile geometry");
+static_assert(kStage % 2 == 0 && kStage >= gfdm::max_stage(kTile, kMaxTaps, 1, 2), "the stage holds a tile's halo");
 
 struct ChannelArgs {
     const cf* in;            // sample 0; `history` samples in front of it are readable
@@ -115,39 +110,19 @@ template <int SC16>
 __global__ __launch_bounds__(kLanes) void k_channel(ChannelArgs a, void* __restrict__ out)
 {
     constexpr int VPS = SC16 ? 4 : 2;            // samples per 16-byte vector
-    constexpr int SB = 16 / VPS;                 // bytes per sample
-    constexpr int kTileVec = kTile / VPS;
-    using Stored = typename std::conditional<SC16 != 0, unsigned, cf>::type;
     __shared__ __attribute__((aligned(16))) cf xs[kStage];
-    __shared__ __attribute__((aligned(16))) Stored ys[kTile];
-    const int mis = (int)(((uintptr_t)out / SB) % VPS);        // samples between the 16-byte boundary in front of `out` and `out`
-    const int in_mis = (int)(((uintptr_t)a.in / sizeof(cf)) & 1);
-    const int64_t nvec = (a.n + mis + VPS - 1) / VPS;
-    const int64_t ntiles = (nvec + kTileVec - 1) / kTileVec;
-    unsigned char* const base = static_cast<unsigned char*>(out);
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t v0 = tile * kTileVec, v1 = std::min(v0 + kTileVec, nvec);
-        const int64_t s0 = v0 * VPS - mis;                                            // ys[k] is sample s0 + k
-        const int64_t i_lo = std::max(s0, (int64_t)0), i_hi = std::min(v1 * VPS - mis, a.n);
-        // 1. xs[k] = x[j0 + k] for j0 + k < i_hi + 1; j0 <= i_lo - T sits on a 16-byte boundary of the input
-        const int64_t g0 = i_lo - a.T, j0 = g0 - ((g0 + in_mis) & 1);
-        const int nstage = (int)(i_hi + 1 - j0);                                     // <= kTile + T + 2
-        for (int k = 2 * threadIdx.x; k < nstage; k += 2 * kLanes) {
-            const int64_t j = j0 + k;
-            float4 x2;
-            if (j >= -a.history && j + 1 < a.n) {
-                x2 = *reinterpret_cast<const float4*>(a.in + j);
-            } else {
-                const cf xa = (j >= -a.history && j < a.n) ? a.in[j] : make_float2(0.f, 0.f);
-                const cf xb = (j + 1 >= -a.history && j + 1 < a.n) ? a.in[j + 1] : make_float2(0.f, 0.f);
-                x2 = make_float4(xa.x, xa.y, xb.x, xb.y);
-            }
-            *reinterpret_cast<float4*>(xs + k) = x2;
-        }
+    __shared__ __attribute__((aligned(16))) gfdm::stored_t<SC16> ys[kTile];
+    const gfdm::StreamTiles tiles(out, VPS, a.n, kTile / VPS);
+    for (int64_t tile = blockIdx.x; tile < tiles.ntiles; tile += gridDim.x) {
+        const gfdm::TileSpan t = tiles.tile(tile);
+        const int64_t s0 = t.s0, i_lo = t.i_lo, i_hi = t.i_hi;                        // ys[k] is sample s0 + k
+        // 1. xs[k] = x[j0 + k] for j0 + k < i_hi + 1
+        const int64_t j0 = gfdm::stage_first(a.in, i_lo - a.T);
+        gfdm::stage_in<0>(xs, a.in, j0, (int)(i_hi + 1 - j0), a.history, a.n, kLanes);
         __syncthreads();
         // 2. the pairs of absolute indices that meet [i_lo, i_hi)
         const int64_t p_lo = (a.offset + i_lo) >> 1, p_hi = (a.offset + i_hi - 1) >> 1;
-        const int npairs = (int)(p_hi - p_lo + 1);                                   // <= kTile / 2 + 1
+        const int npairs = (int)(p_hi - p_lo + 1);                                   // <= max_groups(kTile, 2)
 #pragma unroll 1
         for (int u = 0; u < kPairsPerLane; ++u) {
             const int q = u * kLanes + threadIdx.x;
@@ -167,27 +142,12 @@ __global__ __launch_bounds__(kLanes) void k_channel(ChannelArgs a, void* __restr
                 y0 = make_float2(fmaf(a.sigma, w0.x, y0.x), fmaf(a.sigma, w0.y, y0.y));
                 y1 = make_float2(fmaf(a.sigma, w1.x, y1.x), fmaf(a.sigma, w1.y, y1.y));
             }
-            if (i0 >= i_lo) {
-                if constexpr (SC16) ys[i0 - s0] = gfdm::pack_sc16(y0, a.gain);
-                else ys[i0 - s0] = y0;
-            }
-            if (i0 + 1 < i_hi) {
-                if constexpr (SC16) ys[i0 + 1 - s0] = gfdm::pack_sc16(y1, a.gain);
-                else ys[i0 + 1 - s0] = y1;
-            }
+            if (i0 >= i_lo) ys[i0 - s0] = gfdm::to_stored<SC16>(y0, a.gain);
+            if (i0 + 1 < i_hi) ys[i0 + 1 - s0] = gfdm::to_stored<SC16>(y1, a.gain);
         }
         __syncthreads();
-        // 3. the tile's vectors; a vector that the stream fills only in part goes out sample by sample
-        for (int64_t v = v0 + threadIdx.x; v < v1; v += kLanes) {
-            const int64_t i = v * VPS - mis;
-            const int k = (int)(i - s0);
-            if (i >= 0 && i + VPS <= a.n) {
-                *reinterpret_cast<uint4*>(base + i * SB) = *reinterpret_cast<const uint4*>(ys + k);
-            } else {
-                for (int e = 0; e < VPS; ++e)
-                    if (i + e >= 0 && i + e < a.n) *reinterpret_cast<Stored*>(base + (i + e) * SB) = ys[k + e];
-            }
-        }
+        // 3.
+        gfdm::store_tile<SC16>(static_cast<unsigned char*>(out), tiles, t, ys, kLanes);
         // (xs is rewritten behind this barrier's predecessor only by lanes that have left step 2; ys is read here and rewritten behind the next tile's first barrier)
     }
 }
@@ -199,13 +159,7 @@ int channel_check(int n_taps, double f, double s, int64_t n, int64_t history, in
     if (!std::isfinite(f) || std::fabs(f) > 0.5) return api_fail(GFDM_HIP_EINVAL, "frequency_offset must be finite and lie in [-0.5, 0.5] cycles per sample");
     if (!std::isfinite(s) || s < 0.0) return api_fail(GFDM_HIP_EINVAL, "noise_voltage must be finite and >= 0");
     if (!std::isfinite(gain)) return api_fail(GFDM_HIP_EINVAL, "gain must be finite");
-    if (n < 0) return api_fail(GFDM_HIP_EINVAL, "n must be >= 0");
-    if (history < 0) return api_fail(GFDM_HIP_EINVAL, "history must be >= 0");
-    if (offset < 0) return api_fail(GFDM_HIP_EINVAL, "offset must be >= 0");
-    if (n > kMaxIndex || offset > kMaxIndex - n) return api_fail(GFDM_HIP_EINVAL, "offset + n must not exceed 2^62");
-    const int64_t lim = INT64_MAX / (int64_t)sizeof(cf);
-    if (n > lim || history > lim - n) return api_fail(GFDM_HIP_EINVAL, "the byte size of the input overflows int64");
-    return GFDM_HIP_OK;
+    return gfdm::check_stream_span(n, history, offset);
 }
 
 int taps_check(const float* taps, int n_taps)
@@ -237,18 +191,15 @@ int check_call(const gfdm_hip_channel_model* h, const void* out, const void* in,
     if (rc != GFDM_HIP_OK) return rc;
     if (n == 0) return GFDM_HIP_OK;
     if (!out || !in) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
-    // the FIR reads neighbours: there is no in-place call
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n * (sc16 ? 4 : 8);
-    const uintptr_t i0 = (uintptr_t)in - (uintptr_t)history * sizeof(cf), i1 = (uintptr_t)in + (uintptr_t)n * sizeof(cf);
-    if (o0 < i1 && i0 < o1) return api_fail(GFDM_HIP_EINVAL, "out overlaps [in - history, in + n): the channel model has no in-place call");
-    return GFDM_HIP_OK;
+    return gfdm::check_no_overlap(out, sc16 ? 4 : 8, n, in, sizeof(cf), n, history, "n", "the channel model");      // the FIR reads neighbours
 }
 
 // the one launch of a call; out and in are device pointers, the handle's setter values are read here
 int channel_enqueue(const gfdm_hip_channel_model* h, int sc16, void* out, const cf* in, int64_t n, int64_t history, int64_t offset, double gain, hipStream_t s)
 {
     if (n == 0) return GFDM_HIP_OK;
-    if (misaligned(out, sc16 ? 4 : 8) || misaligned(in, 8)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
+    const int rc = gfdm::check_sample_alignment(out, sc16 ? 4 : 8, in, sizeof(cf));
+    if (rc != GFDM_HIP_OK) return rc;
     ChannelArgs a;
     a.in = in;
     a.n = n;
@@ -264,33 +215,18 @@ int channel_enqueue(const gfdm_hip_channel_model* h, int sc16, void* out, const 
     a.mix = h->f != 0.0;
     a.noisy = h->s != 0.0;
     std::copy(h->taps, h->taps + kMaxTaps, a.taps);
-    const int vps = sc16 ? 4 : 2, tile_vec = kTile / vps;
-    const int64_t ntiles = ((n + vps - 1) / vps + 1 + tile_vec - 1) / tile_vec;      // + 1: an unaligned `out` adds a vector
-    const dim3 grid((unsigned)std::min<int64_t>(ntiles, kMaxTiles));
+    const int vps = sc16 ? 4 : 2;
+    const dim3 grid((unsigned)std::min<int64_t>(gfdm::StreamTiles(out, vps, n, kTile / vps).ntiles, kMaxTiles));
     if (sc16) hipLaunchKernelGGL(k_channel<1>, grid, dim3(kLanes), 0, s, a, out);
     else hipLaunchKernelGGL(k_channel<0>, grid, dim3(kLanes), 0, s, a, out);
     GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
 
-int channel_device(gfdm_hip_channel_model* h, int sc16, void* out, const void* in, int64_t n, int64_t history, int64_t offset, double gain, void* stream)
+// check_call, then channel_enqueue: on the caller's stream, or between an upload and a download on the handle's (gfdm::stream_call)
+int channel_call(gfdm_hip_channel_model* h, bool host, int sc16, void* out, const void* in, int64_t n, int64_t history, int64_t offset, double gain, void* stream)
 {
-    const int rc = check_call(h, out, in, sc16, n, history, offset, gain);
-    if (rc != GFDM_HIP_OK || n == 0) return rc;
-    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
-        return channel_enqueue(h, sc16, out, static_cast<const cf*>(in), n, history, offset, gain, s);
-    });
-}
-
-// upload history + n samples, one enqueue on the handle's stream, download n
-int channel_host(gfdm_hip_channel_model* h, int sc16, void* out, const float* in, int64_t n, int64_t history, int64_t offset, double gain)
-{
-    const int rc = check_call(h, out, in, sc16, n, history, offset, gain);
-    if (rc != GFDM_HIP_OK || n == 0) return rc;
-    gfdm::HostCall hc(h->ctx);
-    const auto x = hc.in(reinterpret_cast<const cf*>(in) - history, (size_t)(history + n));
-    const auto y = hc.out(static_cast<unsigned char*>(out), (size_t)n * (sc16 ? 2 * sizeof(int16_t) : sizeof(cf)));
-    return hc.run([&](hipStream_t s) { return channel_enqueue(h, sc16, y.dev(), x.dev() + history, n, history, offset, gain, s); });
+    return gfdm::stream_call(h, host, sc16, out, in, n, history, offset, gain, stream, check_call, channel_enqueue);
 }
 
 }  // namespace
@@ -374,20 +310,20 @@ int gfdm_hip_channel_model_check(int n_taps, double frequency_offset, double noi
 
 int gfdm_hip_channel_model_apply_device(gfdm_hip_channel_model* h, void* out, const void* in, int64_t n, int64_t history, int64_t offset, void* stream)
 {
-    return channel_device(h, 0, out, in, n, history, offset, 1.0, stream);
+    return channel_call(h, false, 0, out, in, n, history, offset, 1.0, stream);
 }
 int gfdm_hip_channel_model_apply_sc16_device(gfdm_hip_channel_model* h, void* out, const void* in, int64_t n, int64_t history, int64_t offset, double gain,
                                              void* stream)
 {
-    return channel_device(h, 1, out, in, n, history, offset, gain, stream);
+    return channel_call(h, false, 1, out, in, n, history, offset, gain, stream);
 }
 int gfdm_hip_channel_model_apply_host(gfdm_hip_channel_model* h, float* out, const float* in, int64_t n, int64_t history, int64_t offset)
 {
-    return channel_host(h, 0, out, in, n, history, offset, 1.0);
+    return channel_call(h, true, 0, out, in, n, history, offset, 1.0, nullptr);
 }
 int gfdm_hip_channel_model_apply_sc16_host(gfdm_hip_channel_model* h, int16_t* out, const float* in, int64_t n, int64_t history, int64_t offset, double gain)
 {
-    return channel_host(h, 1, out, in, n, history, offset, gain);
+    return channel_call(h, true, 1, out, in, n, history, offset, gain, nullptr);
 }
 
 }  // extern "C"

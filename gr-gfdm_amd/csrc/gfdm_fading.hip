@@ -3,31 +3,26 @@
 // or interleaved int16 I/Q out.  What GNU Radio's channels.selective_fading_model does in a flowgraph; the phases are 64-bit integers, so
 // every sample is a pure function of the tables and its index.  The contract is written out in include/gfdm_hip.h.
 //
-// One kernel, k_fade<SC16>, in k_channel's shape: the OUTPUT is tiled in 16-byte vectors aligned in memory, a workgroup takes kTile samples'
-// worth of them and strides over the tiles beyond the grid.  Per tile
-//   1. the input samples [i_lo - T - 7, i_hi + 7) -- the tile, its T halo and up to seven more at either end for the runs of step 2 --
-//      go to LDS once, in 16-byte loads aligned in memory, sample by sample where history, n or the alignment of `in` cuts a vector.  Sample
-//      k of the stage lies at xs[k + (k >> 3)]: the lanes of step 2 read samples 8 apart, which one padding sample per eight spreads over
-//      all bank pairs (a stride of 18 dwords) where the plain layout would put sixteen lanes on one;
+// One kernel, k_fade<SC16>, a stream stage (gfdm_streamtile.h: the output tiles, step 1 and step 3) with tiles of kTile samples.
+//   1. the halo: the input samples [i_lo - T - 7, i_hi + 7) -- the tile, its T past samples and up to seven more at either end for the runs
+//      of step 2.  Sample k of the stage lies at xs[k + (k >> 3)]: the lanes of step 2 read samples 8 apart, which one padding sample per
+//      eight spreads over all bank pairs (a stride of 18 dwords) where the plain layout would put sixteen lanes on one;
 //   2. a lane owns one aligned RUN of eight absolute indices 8 r .. 8 r + 7: whatever offset and the alignment of `out` are, a tile meets at
-//      most kTile / 8 + 1 runs, which is why kTile is 2040 and not 2048.  Per path: for every sinusoid the phasor at 8 r (an integer
+//      most max_groups(kTile, 8) runs, which is why kTile is 2040 and not 2048.  Per path: for every sinusoid the phasor at 8 r (an integer
 //      multiply, the top 24 bits through sincospif, the next 8 by a first-order correction, times A), the other seven by at most three fp32
 //      rotations with exp(j 2 pi F m / 2^64), m = 1, 2, 4 (tables made at create in fp64); the delay line with a window of eight samples in
-//      registers, one LDS read per tap for all eight; y += g * v.  The results go to a second LDS array in output format;
-//   3. the tile leaves in 16-byte stores aligned in memory; the first and last samples of an unaligned stream go out one by one.
+//      registers, one LDS read per tap for all eight; y += g * v.  The results go to a second LDS array in output format.
 // The tables (48 bytes a sinusoid, P * T coefficients) go to LDS once per workgroup.  P, S and T are launch-uniform loop bounds.
 #include "../../include/gfdm_hip.h"
 #include "gfdm_hostcall.h"
-#include "gfdm_sc16out.h"
+#include "gfdm_streamtile.h"
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <vector>
 
 using gfdm::cf;
 using gfdm::api_fail;
-using gfdm::misaligned;
 
 namespace {
 
@@ -36,12 +31,12 @@ constexpr int kMaxPaths = 8;
 constexpr int kMaxSinusoids = 17;
 constexpr int kMaxTaps = 64;
 constexpr int kRun = 8;                   // absolute indices per run: one run a lane and tile
-constexpr int kTile = 2040;               // samples per tile: a multiple of 4 with kTile / kRun + 1 <= kLanes
-constexpr int kStage = kTile + kMaxTaps + 16;     // input samples in LDS: tile + T, + 7 at either end, + 1 for the alignment of the first vector, rounded up to even
+constexpr int kTile = 2040;               // samples per tile: a multiple of 4 whose runs fit kLanes
+constexpr int kStage = kTile + kMaxTaps + 16;     // input samples in LDS
 constexpr int kStagePad = kStage + kStage / 8 + 1;        // with one padding sample per eight
 constexpr int kMaxTiles = 2048;           // workgroups per launch; the tiles beyond are strided over
-constexpr int64_t kMaxIndex = (int64_t)1 << 62;
-static_assert(kTile % 4 == 0 && kTile / kRun + 1 <= kLanes && kStage % 2 == 0 && kStage >= kTile + kMaxTaps + 15, "tile geometry");
+static_assert(kTile % 4 == 0 && gfdm::max_groups(kTile, kRun) <= kLanes, "tile geometry");
+static_assert(kStage % 2 == 0 && kStage >= gfdm::max_stage(kTile, kMaxTaps + kRun - 1, kRun - 1, 2), "the stage holds a tile's halo");
 
 // one sinusoid as the kernel reads it: 48 bytes, three 16-byte LDS reads
 struct Sinusoid {
@@ -65,7 +60,8 @@ __device__ __forceinline__ cf cmul(cf a, cf b)
     return make_float2(fmaf(-a.y, b.y, a.x * b.x), fmaf(a.y, b.x, a.x * b.y));
 }
 
-__device__ __forceinline__ int padded(int k) { return k + (k >> 3); }
+constexpr int kPad = 3;                   // one padding sample per 2^kPad = kRun staged ones
+__device__ __forceinline__ int padded(int k) { return gfdm::staged_at<kPad>(k); }
 
 // A * exp(j 2 pi top / 2^32): the 24 bits nearest to `top` go through sincospif exactly (hi * 2^-23, in units of pi), the remainder r in
 // [-128, 127] turns the result by delta = 2 pi r 2^-32 to first order (delta^2 / 2 < 2^-45)
@@ -84,46 +80,23 @@ template <int SC16>
 __global__ __launch_bounds__(kLanes) void k_fade(FadeArgs a, void* __restrict__ out)
 {
     constexpr int VPS = SC16 ? 4 : 2;            // samples per 16-byte vector
-    constexpr int SB = 16 / VPS;                 // bytes per sample
-    constexpr int kTileVec = kTile / VPS;
-    using Stored = typename std::conditional<SC16 != 0, unsigned, cf>::type;
     __shared__ __attribute__((aligned(16))) cf xs[kStagePad];
-    __shared__ __attribute__((aligned(16))) Stored ys[kTile];
+    __shared__ __attribute__((aligned(16))) gfdm::stored_t<SC16> ys[kTile];
     __shared__ __attribute__((aligned(16))) uint32_t tab[kMaxPaths * kMaxSinusoids * kSinWords + kMaxPaths * kMaxTaps];
     const int nsin = a.P * a.S;
     for (int k = threadIdx.x; k < nsin * kSinWords + a.P * a.T; k += kLanes) tab[k] = a.table[k];
     const Sinusoid* const sins = reinterpret_cast<const Sinusoid*>(tab);
     const float* const coef = reinterpret_cast<const float*>(tab + nsin * kSinWords);
     // (the first barrier of the first tile stands between these writes and their readers)
-    const int mis = (int)(((uintptr_t)out / SB) % VPS);        // samples between the 16-byte boundary in front of `out` and `out`
-    const int in_mis = (int)(((uintptr_t)a.in / sizeof(cf)) & 1);
-    const int64_t nvec = (a.n + mis + VPS - 1) / VPS;
-    const int64_t ntiles = (nvec + kTileVec - 1) / kTileVec;
-    unsigned char* const base = static_cast<unsigned char*>(out);
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t v0 = tile * kTileVec, v1 = std::min(v0 + kTileVec, nvec);
-        const int64_t s0 = v0 * VPS - mis;                                            // ys[k] is sample s0 + k
-        const int64_t i_lo = std::max(s0, (int64_t)0), i_hi = std::min(v1 * VPS - mis, a.n);
-        // 1. sample j0 + k at xs[padded(k)] for j0 + k < i_hi + 7; j0 <= i_lo - 7 - T sits on a 16-byte boundary of the input
-        const int64_t g0 = i_lo - a.T - 7, j0 = g0 - ((g0 + in_mis) & 1);
-        const int nstage = (int)(i_hi + 7 - j0);                                     // <= kTile + T + 15
-        for (int k = 2 * threadIdx.x; k < nstage; k += 2 * kLanes) {
-            const int64_t j = j0 + k;
-            cf xa, xb;
-            if (j >= -a.history && j + 1 < a.n) {
-                const float4 x2 = *reinterpret_cast<const float4*>(a.in + j);
-                xa = make_float2(x2.x, x2.y);
-                xb = make_float2(x2.z, x2.w);
-            } else {
-                xa = (j >= -a.history && j < a.n) ? a.in[j] : make_float2(0.f, 0.f);
-                xb = (j + 1 >= -a.history && j + 1 < a.n) ? a.in[j + 1] : make_float2(0.f, 0.f);
-            }
-            const int at = padded(k);                                                 // k is even: k + 1 lies in the same eight
-            xs[at] = xa;
-            xs[at + 1] = xb;
-        }
+    const gfdm::StreamTiles tiles(out, VPS, a.n, kTile / VPS);
+    for (int64_t tile = blockIdx.x; tile < tiles.ntiles; tile += gridDim.x) {
+        const gfdm::TileSpan t = tiles.tile(tile);
+        const int64_t s0 = t.s0, i_lo = t.i_lo, i_hi = t.i_hi;                        // ys[k] is sample s0 + k
+        // 1. sample j0 + k at xs[padded(k)] for j0 + k < i_hi + 7
+        const int64_t j0 = gfdm::stage_first(a.in, i_lo - a.T - (kRun - 1));
+        gfdm::stage_in<kPad>(xs, a.in, j0, (int)(i_hi + (kRun - 1) - j0), a.history, a.n, kLanes);
         __syncthreads();
-        // 2. the runs of absolute indices that meet [i_lo, i_hi): at most kTile / 8 + 1, one a lane
+        // 2. the runs of absolute indices that meet [i_lo, i_hi): at most max_groups(kTile, 8), one a lane
         const int64_t r_lo = (a.offset + i_lo) >> 3, r_hi = (a.offset + i_hi - 1) >> 3;
         if ((int64_t)threadIdx.x <= r_hi - r_lo) {
             const int64_t a0 = (r_lo + threadIdx.x) << 3, i0 = a0 - a.offset;        // samples i0 (>= i_lo - 7) .. i0 + 7 (<= i_hi + 6)
@@ -198,24 +171,12 @@ __global__ __launch_bounds__(kLanes) void k_fade(FadeArgs a, void* __restrict__ 
 #pragma unroll
             for (int j = 0; j < kRun; ++j) {
                 const int64_t i = i0 + j;
-                if (i >= i_lo && i < i_hi) {
-                    if constexpr (SC16) ys[i - s0] = gfdm::pack_sc16(y[j], a.gain);
-                    else ys[i - s0] = y[j];
-                }
+                if (i >= i_lo && i < i_hi) ys[i - s0] = gfdm::to_stored<SC16>(y[j], a.gain);
             }
         }
         __syncthreads();
-        // 3. the tile's vectors; a vector that the stream fills only in part goes out sample by sample
-        for (int64_t v = v0 + threadIdx.x; v < v1; v += kLanes) {
-            const int64_t i = v * VPS - mis;
-            const int k = (int)(i - s0);
-            if (i >= 0 && i + VPS <= a.n) {
-                *reinterpret_cast<uint4*>(base + i * SB) = *reinterpret_cast<const uint4*>(ys + k);
-            } else {
-                for (int e = 0; e < VPS; ++e)
-                    if (i + e >= 0 && i + e < a.n) *reinterpret_cast<Stored*>(base + (i + e) * SB) = ys[k + e];
-            }
-        }
+        // 3.
+        gfdm::store_tile<SC16>(static_cast<unsigned char*>(out), tiles, t, ys, kLanes);
         // (xs is rewritten only behind the barrier above, which every lane passes after step 2; ys is read here and rewritten behind the next tile's first barrier)
     }
 }
@@ -227,13 +188,7 @@ int fading_check(int n_paths, int n_sinusoids, int n_taps, int64_t n, int64_t hi
     if (n_sinusoids < 1 || n_sinusoids > kMaxSinusoids) return api_fail(GFDM_HIP_EINVAL, "n_sinusoids must lie in 1 .. 17");
     if (n_taps < 1 || n_taps > kMaxTaps) return api_fail(GFDM_HIP_EINVAL, "n_taps must lie in 1 .. 64");
     if (!std::isfinite(gain)) return api_fail(GFDM_HIP_EINVAL, "gain must be finite");
-    if (n < 0) return api_fail(GFDM_HIP_EINVAL, "n must be >= 0");
-    if (history < 0) return api_fail(GFDM_HIP_EINVAL, "history must be >= 0");
-    if (offset < 0) return api_fail(GFDM_HIP_EINVAL, "offset must be >= 0");
-    if (n > kMaxIndex || offset > kMaxIndex - n) return api_fail(GFDM_HIP_EINVAL, "offset + n must not exceed 2^62");
-    const int64_t lim = INT64_MAX / (int64_t)sizeof(cf);
-    if (n > lim || history > lim - n) return api_fail(GFDM_HIP_EINVAL, "the byte size of the input overflows int64");
-    return GFDM_HIP_OK;
+    return gfdm::check_stream_span(n, history, offset);
 }
 
 // exp(j 2 pi w / 2^64) of a 64-bit phase, in fp64, rounded to fp32
@@ -269,18 +224,15 @@ int check_call(const gfdm_hip_fading_model* h, const void* out, const void* in, 
     if (rc != GFDM_HIP_OK) return rc;
     if (n == 0) return GFDM_HIP_OK;
     if (!out || !in) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
-    // the delay lines read neighbours: there is no in-place call
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n * (sc16 ? 4 : 8);
-    const uintptr_t i0 = (uintptr_t)in - (uintptr_t)history * sizeof(cf), i1 = (uintptr_t)in + (uintptr_t)n * sizeof(cf);
-    if (o0 < i1 && i0 < o1) return api_fail(GFDM_HIP_EINVAL, "out overlaps [in - history, in + n): the fading model has no in-place call");
-    return GFDM_HIP_OK;
+    return gfdm::check_no_overlap(out, sc16 ? 4 : 8, n, in, sizeof(cf), n, history, "n", "the fading model");       // the delay lines read neighbours
 }
 
 // the one launch of a call; out and in are device pointers
 int fading_enqueue(const gfdm_hip_fading_model* h, int sc16, void* out, const cf* in, int64_t n, int64_t history, int64_t offset, double gain, hipStream_t s)
 {
     if (n == 0) return GFDM_HIP_OK;
-    if (misaligned(out, sc16 ? 4 : 8) || misaligned(in, 8)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
+    const int rc = gfdm::check_sample_alignment(out, sc16 ? 4 : 8, in, sizeof(cf));
+    if (rc != GFDM_HIP_OK) return rc;
     FadeArgs a;
     a.in = in;
     a.table = h->d_table;
@@ -291,33 +243,18 @@ int fading_enqueue(const gfdm_hip_fading_model* h, int sc16, void* out, const cf
     a.P = h->P;
     a.S = h->S;
     a.T = h->T;
-    const int vps = sc16 ? 4 : 2, tile_vec = kTile / vps;
-    const int64_t ntiles = ((n + vps - 1) / vps + 1 + tile_vec - 1) / tile_vec;      // + 1: an unaligned `out` adds a vector
-    const dim3 grid((unsigned)std::min<int64_t>(ntiles, kMaxTiles));
+    const int vps = sc16 ? 4 : 2;
+    const dim3 grid((unsigned)std::min<int64_t>(gfdm::StreamTiles(out, vps, n, kTile / vps).ntiles, kMaxTiles));
     if (sc16) hipLaunchKernelGGL(k_fade<1>, grid, dim3(kLanes), 0, s, a, out);
     else hipLaunchKernelGGL(k_fade<0>, grid, dim3(kLanes), 0, s, a, out);
     GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }
 
-int fading_device(gfdm_hip_fading_model* h, int sc16, void* out, const void* in, int64_t n, int64_t history, int64_t offset, double gain, void* stream)
+// check_call, then fading_enqueue: on the caller's stream, or between an upload and a download on the handle's (gfdm::stream_call)
+int fading_call(gfdm_hip_fading_model* h, bool host, int sc16, void* out, const void* in, int64_t n, int64_t history, int64_t offset, double gain, void* stream)
 {
-    const int rc = check_call(h, out, in, sc16, n, history, offset, gain);
-    if (rc != GFDM_HIP_OK || n == 0) return rc;
-    return gfdm::on_device(h->ctx.device, stream, [&](hipStream_t s) {
-        return fading_enqueue(h, sc16, out, static_cast<const cf*>(in), n, history, offset, gain, s);
-    });
-}
-
-// upload history + n samples, one enqueue on the handle's stream, download n
-int fading_host(gfdm_hip_fading_model* h, int sc16, void* out, const float* in, int64_t n, int64_t history, int64_t offset, double gain)
-{
-    const int rc = check_call(h, out, in, sc16, n, history, offset, gain);
-    if (rc != GFDM_HIP_OK || n == 0) return rc;
-    gfdm::HostCall hc(h->ctx);
-    const auto x = hc.in(reinterpret_cast<const cf*>(in) - history, (size_t)(history + n));
-    const auto y = hc.out(static_cast<unsigned char*>(out), (size_t)n * (sc16 ? 2 * sizeof(int16_t) : sizeof(cf)));
-    return hc.run([&](hipStream_t s) { return fading_enqueue(h, sc16, y.dev(), x.dev() + history, n, history, offset, gain, s); });
+    return gfdm::stream_call(h, host, sc16, out, in, n, history, offset, gain, stream, check_call, fading_enqueue);
 }
 
 template <class V, class E>
@@ -393,20 +330,20 @@ int gfdm_hip_fading_model_check(int n_paths, int n_sinusoids, int n_taps, int64_
 
 int gfdm_hip_fading_model_apply_device(gfdm_hip_fading_model* h, void* out, const void* in, int64_t n, int64_t history, int64_t offset, void* stream)
 {
-    return fading_device(h, 0, out, in, n, history, offset, 1.0, stream);
+    return fading_call(h, false, 0, out, in, n, history, offset, 1.0, stream);
 }
 int gfdm_hip_fading_model_apply_sc16_device(gfdm_hip_fading_model* h, void* out, const void* in, int64_t n, int64_t history, int64_t offset, double gain,
                                             void* stream)
 {
-    return fading_device(h, 1, out, in, n, history, offset, gain, stream);
+    return fading_call(h, false, 1, out, in, n, history, offset, gain, stream);
 }
 int gfdm_hip_fading_model_apply_host(gfdm_hip_fading_model* h, float* out, const float* in, int64_t n, int64_t history, int64_t offset)
 {
-    return fading_host(h, 0, out, in, n, history, offset, 1.0);
+    return fading_call(h, true, 0, out, in, n, history, offset, 1.0, nullptr);
 }
 int gfdm_hip_fading_model_apply_sc16_host(gfdm_hip_fading_model* h, int16_t* out, const float* in, int64_t n, int64_t history, int64_t offset, double gain)
 {
-    return fading_host(h, 1, out, in, n, history, offset, gain);
+    return fading_call(h, true, 1, out, in, n, history, offset, gain, nullptr);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // Internal, host only: what every translation unit of the C-ABI needs around a runtime call -- error reporting, the device guard, the device
 // check, a handle's device + private stream, the skeletons of a constructor (create_handle) and of a *_device call (on_device), the staged
-// *_host call (HostCall: one allocation, uploads, the enqueue, downloads, one synchronise) and the constellation the symbol mapper and the
-// link meter share.  Compiled as plain C++ by tests/sanitize (hostcall_check.cc).  Never seen by hiprtc (not in JIT_HDRS).
+// *_host call (HostCall: one allocation, uploads, the enqueue, downloads, one synchronise), the checks and the call pair of the stream stages
+// and the constellation the symbol mapper and the link meter share.  Compiled as plain C++ by tests/sanitize (hostcall_check.cc).  Never seen by hiprtc (not in JIT_HDRS).
 #pragma once
 #include "../../include/gfdm_hip.h"
 #include "gfdm_plan.h"
@@ -113,6 +113,37 @@ inline int check_width(int64_t width, int64_t least, int64_t elem, int64_t n_row
     if (width < least) return api_fail(GFDM_HIP_EINVAL, std::string(what) + " is below the row's minimum");
     if (width > INT64_MAX / elem || (n_rows > 0 && width * elem > INT64_MAX / n_rows))
         return api_fail(GFDM_HIP_EINVAL, "the byte size of the rows overflows int64");
+    return GFDM_HIP_OK;
+}
+
+// ---- the checks the stream stages share (channel model, fading model, resampler, burst shaper) ----
+// n output samples with absolute indices offset .. offset + n - 1 from history + n complex64 input samples
+inline int check_stream_span(int64_t n, int64_t history, int64_t offset)
+{
+    constexpr int64_t kMaxIndex = (int64_t)1 << 62;
+    if (n < 0) return api_fail(GFDM_HIP_EINVAL, "n must be >= 0");
+    if (history < 0) return api_fail(GFDM_HIP_EINVAL, "history must be >= 0");
+    if (offset < 0) return api_fail(GFDM_HIP_EINVAL, "offset must be >= 0");
+    if (n > kMaxIndex || offset > kMaxIndex - n) return api_fail(GFDM_HIP_EINVAL, "offset + n must not exceed 2^62");
+    const int64_t lim = INT64_MAX / (int64_t)sizeof(cf);
+    if (n > lim || history > lim - n) return api_fail(GFDM_HIP_EINVAL, "the byte size of the input overflows int64");
+    return GFDM_HIP_OK;
+}
+
+// a stage that reads neighbours has no in-place call: n_out samples of out_bytes each at `out` against [in - history, in + n_in) of in_bytes
+// each; `count` is the name of n_in in the caller's contract, `who` the module
+inline int check_no_overlap(const void* out, size_t out_bytes, int64_t n_out, const void* in, size_t in_bytes, int64_t n_in, int64_t history,
+                            const char* count, const char* who)
+{
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n_out * out_bytes;
+    const uintptr_t i0 = (uintptr_t)in - (uintptr_t)history * in_bytes, i1 = (uintptr_t)in + (uintptr_t)n_in * in_bytes;
+    if (o0 < i1 && i0 < o1) return api_fail(GFDM_HIP_EINVAL, std::string("out overlaps [in - history, in + ") + count + "): " + who + " has no in-place call");
+    return GFDM_HIP_OK;
+}
+
+inline int check_sample_alignment(const void* out, size_t out_bytes, const void* in, size_t in_bytes)
+{
+    if (misaligned(out, out_bytes) || misaligned(in, in_bytes)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
     return GFDM_HIP_OK;
 }
 
@@ -230,6 +261,21 @@ private:
     size_t size_ = 0;
     std::vector<Copy> up_, down_;
 };
+
+// Both flavours of a stream stage's call that maps history + n complex64 samples to n samples, complex64 or sc16 (channel model, fading
+// model): `check` is the module's check_call, `enqueue` its one launch.  host: upload history + n samples, the enqueue on the handle's
+// stream, download n; else the enqueue on the caller's stream.
+template <class H, class Check, class Enqueue>
+int stream_call(H* h, bool host, int sc16, void* out, const void* in, int64_t n, int64_t history, int64_t offset, double gain, void* stream, Check check, Enqueue enqueue)
+{
+    const int rc = check(h, out, in, sc16, n, history, offset, gain);
+    if (rc != GFDM_HIP_OK || n == 0) return rc;
+    if (!host) return on_device(h->ctx.device, stream, [&](hipStream_t s) { return enqueue(h, sc16, out, static_cast<const cf*>(in), n, history, offset, gain, s); });
+    HostCall hc(h->ctx);
+    const auto x = hc.in(static_cast<const cf*>(in) - history, (size_t)(history + n));
+    const auto y = hc.out(static_cast<unsigned char*>(out), (size_t)n * (sc16 ? 2 * sizeof(int16_t) : sizeof(cf)));
+    return hc.run([&](hipStream_t s) { return enqueue(h, sc16, y.dev(), x.dev() + history, n, history, offset, gain, s); });
+}
 
 // ---- the constellation of a handle: the symbol mapper and the link meter decide with the same points and the same rule ----
 inline int bits_of(int n_points)

@@ -3,21 +3,20 @@
 // mmse_resampler_cc / pfb_arb_resampler_ccf, and of the resampler that channels.channel_model drives with epsilon).  The contract is
 // written out in include/gfdm_hip.h.
 //
-// One kernel, k_resample<SC16, INTERP, T>.  As in k_channel the OUTPUT is tiled: the stream is cut into 16-byte vectors aligned in memory
-// (2 complex64 samples) and a workgroup takes tile_vec of them at a time; the host chooses tile_vec from `step` so that the input span of
-// a tile, which grows with step, fits kStage samples.  Per workgroup the tap table goes to LDS once (rows padded to an odd stride: lanes
-// on different rows then meet different banks); per tile
-//   1. the input samples [idx(first) - D, idx(last) - D + T) go to LDS once -- complex64 in 16-byte loads aligned in memory, sample by
-//      sample where history, n_in or the alignment of `in` cuts a vector; sc16 in one 4-byte load per sample, widened there;
+// One kernel, k_resample<SC16, INTERP, T>, a stream stage (gfdm_streamtile.h: the output tiles, step 1 of a complex64 input and the
+// store of step 3) whose tile size is a run-time value: the host chooses tile_vec from `step` so that the input span of a tile, which
+// grows with step, fits kStage samples.  Per workgroup the tap table goes to LDS once (rows padded to an odd stride: lanes on different
+// rows then meet different banks); per tile
+//   1. the halo: the input samples [idx(first) - D, idx(last) - D + T); an sc16 input in one 4-byte load per sample, widened there;
 //   2. a lane owns output vectors: two consecutive samples, each with its own position P = pos + i * step (mul-hi / mul-lo, no float),
-//      its own row(s) of the table and its own window of the staged span; the vector leaves in one 16-byte store, the first and last
-//      sample of an unaligned stream alone.
+//      its own row(s) of the table and its own window of the staged span; the vector leaves from registers.
 // In interp 1 the difference h[q + 1][t] - h[q][t] is formed from the two rows in LDS: the same single fp32 rounding as a table made at
 // create, at half the LDS footprint, so every (L, T) of the contract takes this one path (at most 53.8 KB of LDS:
 // 16 928 bytes of samples and the 1025 x 9 floats of L = 1024, T = 8).
 #include "../../include/gfdm_hip.h"
 #include "gfdm_burstfetch.h"
 #include "gfdm_hostcall.h"
+#include "gfdm_streamtile.h"
 
 #include <algorithm>
 #include <climits>
@@ -26,7 +25,6 @@
 
 using gfdm::cf;
 using gfdm::api_fail;
-using gfdm::misaligned;
 
 namespace {
 
@@ -107,19 +105,15 @@ __global__ __launch_bounds__(kLanes) void k_resample(ResampleArgs a, cf* __restr
         const int p = e / T;
         hs[p * TS + (e - p * T)] = a.table[e];
     }
-    const int mis = (int)(((uintptr_t)out / sizeof(cf)) & 1);                       // samples between the 16-byte boundary in front of `out` and `out`
-    const int in_mis = (int)(((uintptr_t)a.in / sizeof(cf)) & 1);
-    const int64_t nvec = (a.n_out + mis + 1) / 2;
-    const int64_t ntiles = (nvec + a.tile_vec - 1) / a.tile_vec;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t v0 = tile * a.tile_vec, v1 = std::min(v0 + a.tile_vec, nvec);
-        const int64_t i_lo = std::max(2 * v0 - mis, (int64_t)0), i_hi = std::min(2 * v1 - mis, a.n_out);
-        // 1. xs[k] = x[j0 + k] for k < nstage; complex64: j0 <= idx(i_lo) - D sits on a 16-byte boundary of the input
+    const gfdm::StreamTiles tiles(out, 2, a.n_out, a.tile_vec);
+    for (int64_t tile = blockIdx.x; tile < tiles.ntiles; tile += gridDim.x) {
+        const gfdm::TileSpan t = tiles.tile(tile);
+        // 1. xs[k] = x[j0 + k] for k < nstage
         int64_t idx_lo, idx_hi;
         uint32_t frac;
-        position(a, i_lo, idx_lo, frac);
-        position(a, i_hi - 1, idx_hi, frac);
-        const int64_t g0 = idx_lo - D, j0 = SC16 ? g0 : g0 - ((g0 + in_mis) & 1);
+        position(a, t.i_lo, idx_lo, frac);
+        position(a, t.i_hi - 1, idx_hi, frac);
+        const int64_t j0 = SC16 ? idx_lo - D : gfdm::stage_first(a.in, idx_lo - D);
         const int nstage = (int)std::min<int64_t>(idx_hi - D + T - j0, kStage);     // <= kStage by the host's choice of tile_vec
         if (SC16) {
             const gfdm::sc16_io* const s = static_cast<const gfdm::sc16_io*>(a.in);
@@ -128,38 +122,23 @@ __global__ __launch_bounds__(kLanes) void k_resample(ResampleArgs a, cf* __restr
                 xs[k] = (j >= -a.history && j < a.n_in) ? gfdm::sc16_to_cf(s[j]) : make_float2(0.f, 0.f);
             }
         } else {
-            const cf* const s = static_cast<const cf*>(a.in);
-            for (int k = 2 * threadIdx.x; k < nstage; k += 2 * kLanes) {
-                const int64_t j = j0 + k;
-                float4 x2;
-                if (j >= -a.history && j + 1 < a.n_in) {
-                    x2 = *reinterpret_cast<const float4*>(s + j);
-                } else {
-                    const cf xa = (j >= -a.history && j < a.n_in) ? s[j] : make_float2(0.f, 0.f);
-                    const cf xb = (j + 1 >= -a.history && j + 1 < a.n_in) ? s[j + 1] : make_float2(0.f, 0.f);
-                    x2 = make_float4(xa.x, xa.y, xb.x, xb.y);
-                }
-                *reinterpret_cast<float4*>(xs + k) = x2;
-            }
+            gfdm::stage_in<0>(xs, static_cast<const cf*>(a.in), j0, nstage, a.history, a.n_in, kLanes);
         }
         __syncthreads();
         // 2. the tile's vectors: samples i (may be -1) and i + 1 (may be n_out)
-        for (int64_t v = v0 + threadIdx.x; v < v1; v += kLanes) {
-            const int64_t i = 2 * v - mis;
-            const bool has0 = i >= 0, has1 = i + 1 < a.n_out;
-            cf y0 = make_float2(0.f, 0.f), y1 = y0;
+        for (int64_t v = t.v0 + threadIdx.x; v < t.v1; v += kLanes) {
+            const int64_t i = tiles.first(v);
+            cf y[2] = { make_float2(0.f, 0.f), make_float2(0.f, 0.f) };
             int64_t idx;
-            if (has0) {
+            if (i >= 0) {
                 position(a, i, idx, frac);
-                y0 = output<INTERP>(xs + (int)(idx - D - j0), hs, frac, a.lg, T, TS);
+                y[0] = output<INTERP>(xs + (int)(idx - D - j0), hs, frac, a.lg, T, TS);
             }
-            if (has1) {
+            if (i + 1 < a.n_out) {
                 position(a, i + 1, idx, frac);
-                y1 = output<INTERP>(xs + (int)(idx - D - j0), hs, frac, a.lg, T, TS);
+                y[1] = output<INTERP>(xs + (int)(idx - D - j0), hs, frac, a.lg, T, TS);
             }
-            if (has0 && has1) *reinterpret_cast<float4*>(out + i) = make_float4(y0.x, y0.y, y1.x, y1.y);
-            else if (has0) out[i] = y0;
-            else if (has1) out[i + 1] = y1;
+            gfdm::store_vector<0>(reinterpret_cast<unsigned char*>(out), tiles, i, y, 1.f);
         }
         __syncthreads();             // xs is rewritten for the next tile
     }
@@ -222,21 +201,18 @@ int check_call(const gfdm_hip_resampler* h, const void* out, const void* in, int
     if (rc != GFDM_HIP_OK) return rc;
     if (n_out == 0) return GFDM_HIP_OK;
     if (!out || (!in && history + n_in > 0)) return api_fail(GFDM_HIP_EINVAL, "NULL buffer");
-    // the interpolator reads neighbours: there is no in-place call
-    const uintptr_t sb = sc16 ? 4 : 8;
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n_out * sizeof(cf);
-    const uintptr_t i0 = (uintptr_t)in - (uintptr_t)history * sb, i1 = (uintptr_t)in + (uintptr_t)n_in * sb;
-    if (o0 < i1 && i0 < o1) return api_fail(GFDM_HIP_EINVAL, "out overlaps [in - history, in + n_in): the resampler has no in-place call");
-    return GFDM_HIP_OK;
+    return gfdm::check_no_overlap(out, sizeof(cf), n_out, in, sc16 ? 4 : 8, n_in, history, "n_in", "the resampler");      // the interpolator reads neighbours
 }
 
 // the largest number of output vectors whose input span fits kStage for any pos and any alignment: the 2 tile_vec outputs of a tile
-// span at most ((2 tile_vec - 1) * step >> 32) + 1 input positions, their windows T - 1 more, the alignment of the first load one more
+// meet at most ((2 tile_vec - 1) * step >> 32) + 2 input positions, their windows add D in front and T - 1 - D behind
 int tile_vec_for(uint64_t step, int T)
 {
-    const uint64_t m = (((uint64_t)(kStage - T - 2)) << 32) / step;                // (m * step >> 32) <= kStage - T - 2
+    const int D = (T - 1) / 2, room = kStage - gfdm::max_stage(2, D, T - 1 - D, 2);
+    const uint64_t m = ((uint64_t)room << 32) / step;                              // (m * step >> 32) <= room
     return (int)std::max<uint64_t>(1, std::min<uint64_t>((m + 1) / 2, kTileVecMax));
 }
+static_assert(gfdm::max_stage(2 + (int)(kStepMax >> 32), 0, kMaxTaps - 1, 2) <= kStage, "the one vector of the smallest tile fits the stage at the largest step and T");
 
 template <int SC16, int INTERP>
 void launch_T(const ResampleArgs& a, cf* out, dim3 grid, size_t lds, hipStream_t s)
@@ -253,7 +229,8 @@ void launch_T(const ResampleArgs& a, cf* out, dim3 grid, size_t lds, hipStream_t
 int resample_enqueue(const gfdm_hip_resampler* h, int sc16, void* out, const void* in, int64_t n_out, int64_t n_in, int64_t history, int64_t pos, hipStream_t s)
 {
     if (n_out == 0) return GFDM_HIP_OK;
-    if (misaligned(out, 8) || misaligned(in, sc16 ? 4 : 8)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
+    const int rc = gfdm::check_sample_alignment(out, sizeof(cf), in, sc16 ? 4 : 8);
+    if (rc != GFDM_HIP_OK) return rc;
     ResampleArgs a;
     a.in = in;
     a.table = h->d_taps;
@@ -266,8 +243,7 @@ int resample_enqueue(const gfdm_hip_resampler* h, int sc16, void* out, const voi
     a.L = h->L;
     a.lg = h->lg;
     a.tile_vec = tile_vec_for(h->step, h->T);
-    const int64_t ntiles = ((n_out + 1) / 2 + 1 + a.tile_vec - 1) / a.tile_vec;          // + 1: an unaligned `out` adds a vector
-    const dim3 grid((unsigned)std::min<int64_t>(ntiles, kMaxGroups));
+    const dim3 grid((unsigned)std::min<int64_t>(gfdm::StreamTiles(out, 2, n_out, a.tile_vec).ntiles, kMaxGroups));
     const size_t lds = kStage * sizeof(cf) + (size_t)(h->L + 1) * (h->T | 1) * sizeof(float);
     cf* const o = static_cast<cf*>(out);
     if (sc16) {

@@ -1,5 +1,6 @@
 // The sc16 output rule (include/gfdm_hip.h: "q truncates toward zero and saturates to [-32768, 32767], NaN gives 0"): ONE definition for
-// every kernel that writes interleaved int16 I/Q -- the burst shaper (gfdm_shaper.hip) and the channel model (gfdm_channel.hip).
+// every kernel that writes interleaved int16 I/Q -- the burst shaper (gfdm_shaper.hip), the channel model (gfdm_channel.hip) and the fading
+// model (gfdm_fading.hip), all three through the stores of gfdm_streamtile.h.
 #pragma once
 #include "gfdm_plan.h"
 

@@ -3,9 +3,9 @@
 // contract is written out in include/gfdm_hip.h.
 //
 // One kernel writes the whole stream, frames and silence alike (no memset in front: gfdm_burst.hip, k_detect_scatter, records what a
-// memset node did under graph replay).  The OUTPUT is tiled, not the bursts: the stream is cut into 16-byte vectors aligned in memory
-// (2 complex64 or 4 sc16 samples; the first and the last may be partial and are stored sample by sample), a workgroup takes kTileVec of
-// them, a lane one at a time, so every store of a wave is 1 KiB contiguous wherever pre_padding or a start puts a frame.  Each sample
+// memset node did under graph replay).  The OUTPUT is tiled, not the bursts, as a stream stage without an input stream (gfdm_streamtile.h:
+// the output tiles and the store of step 3 from registers): a workgroup takes kTileVec 16-byte vectors aligned in memory, a lane one at a
+// time, so every store of a wave is 1 KiB contiguous wherever pre_padding or a start puts a frame.  Each sample
 // looks its burst up -- the last live b with start(b) <= i -- and is y_b[i - start(b)] when that lies inside the frame, else 0.  The
 // workgroup finds the counts for the two ends of its tile (64 probes of the start list per step and wave), copies that window of the list
 // to LDS, and a lane bisects the window once per vector; a tile that holds more than 255 starts looks them up in global memory.  So
@@ -20,7 +20,7 @@
 #include "../../include/gfdm_hip.h"
 #include "gfdm_decide.h"
 #include "gfdm_hostcall.h"
-#include "gfdm_sc16out.h"
+#include "gfdm_streamtile.h"
 
 #include <algorithm>
 #include <climits>
@@ -32,7 +32,6 @@ using gfdm::cf;
 using gfdm::api_fail;
 using gfdm::live_rows;
 using gfdm::misaligned;
-using gfdm::pack_sc16;          // the sc16 output rule: gfdm_sc16out.h
 
 namespace {
 
@@ -140,41 +139,20 @@ __device__ __forceinline__ void vector_from_window(const ShapeArgs& a, int64_t i
     }
 }
 
-template <int SC16>
-__device__ __forceinline__ void store_vector(unsigned char* base, int64_t i0, int64_t out_len, const cf* y, float g)
-{
-    constexpr int VPS = SC16 ? 4 : 2, SB = 16 / VPS;
-    if (i0 >= 0 && i0 + VPS <= out_len) {            // a whole vector: 16-byte aligned by construction
-        if constexpr (SC16) *reinterpret_cast<uint4*>(base + i0 * SB) = make_uint4(pack_sc16(y[0], g), pack_sc16(y[1], g), pack_sc16(y[2], g), pack_sc16(y[3], g));
-        else *reinterpret_cast<float4*>(base + i0 * SB) = make_float4(y[0].x, y[0].y, y[1].x, y[1].y);
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < VPS; ++j) {                  // head or tail of the stream
-        const int64_t i = i0 + j;
-        if (i < 0 || i >= out_len) continue;
-        if constexpr (SC16) *reinterpret_cast<unsigned*>(base + i * SB) = pack_sc16(y[j], g);
-        else *reinterpret_cast<cf*>(base + i * SB) = y[j];
-    }
-}
-
 // SC16 = 0: out is complex64; 1: interleaved int16 I/Q
 template <int SC16>
 __global__ __launch_bounds__(kLanes) void k_shaper_place(ShapeArgs a, void* __restrict__ out)
 {
     constexpr int VPS = SC16 ? 4 : 2;            // samples per 16-byte vector
-    constexpr int SB = 16 / VPS;                 // bytes per sample
     __shared__ int64_t win[kLanes];
     const int64_t n_live = live_rows(a.count, a.n_bursts);
     const float g = a.gain ? *a.gain : 1.f;
-    const int mis = (int)(((uintptr_t)out / SB) % VPS);        // samples between the 16-byte boundary in front of `out` and `out`
-    const int64_t nvec = (a.out_len + mis + VPS - 1) / VPS;
-    const int64_t ntiles = (nvec + kTileVec - 1) / kTileVec;
+    const gfdm::StreamTiles tiles(out, VPS, a.out_len, kTileVec);
     unsigned char* const base = static_cast<unsigned char*>(out);
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t v0 = tile * kTileVec, v1 = std::min(v0 + kTileVec, nvec);
-        const int64_t i_lo = std::max(v0 * VPS - mis, (int64_t)0), i_hi = std::min(v1 * VPS - mis, a.out_len);
-        const int64_t c0 = wave_count_le(a, i_lo, 0, n_live), c1 = wave_count_le(a, i_hi - 1, c0, n_live);
+    for (int64_t tile = blockIdx.x; tile < tiles.ntiles; tile += gridDim.x) {
+        const gfdm::TileSpan t = tiles.tile(tile);
+        const int64_t v0 = t.v0, v1 = t.v1;
+        const int64_t c0 = wave_count_le(a, t.i_lo, 0, n_live), c1 = wave_count_le(a, t.i_hi - 1, c0, n_live);
         const bool windowed = c1 - c0 + 1 <= kLanes;           // the usual case: the tile's starts, and the one before, fit the window
         const int w = windowed ? (int)(c1 - c0 + 1) : 0;
         if ((int)threadIdx.x < w) {
@@ -187,13 +165,13 @@ __global__ __launch_bounds__(kLanes) void k_shaper_place(ShapeArgs a, void* __re
         for (int u = 0; u < kTileVec / kLanes; ++u) {
             const int64_t v = v0 + u * kLanes + threadIdx.x;
             if (v >= v1) continue;
-            if (windowed) vector_from_window<VPS>(a, v * VPS - mis, c0, win, w, y[u]);
-            else vector_from_global<VPS>(a, v * VPS - mis, c0, c1, y[u]);
+            if (windowed) vector_from_window<VPS>(a, tiles.first(v), c0, win, w, y[u]);
+            else vector_from_global<VPS>(a, tiles.first(v), c0, c1, y[u]);
         }
 #pragma unroll
         for (int u = 0; u < kTileVec / kLanes; ++u) {
             const int64_t v = v0 + u * kLanes + threadIdx.x;
-            if (v < v1) store_vector<SC16>(base, v * VPS - mis, a.out_len, y[u], g);
+            if (v < v1) gfdm::store_vector<SC16>(base, tiles, tiles.first(v), y[u], g);
         }
         __syncthreads();                         // win is rewritten for the next tile
     }
@@ -291,7 +269,8 @@ int shaper_enqueue(gfdm_hip_burst_shaper* h, int sc16, void* out, const cf* fram
                    hipStream_t s)
 {
     if (l.out_len == 0) return GFDM_HIP_OK;
-    if (misaligned(out, sc16 ? 4 : 8) || misaligned(frames, 8)) return api_fail(GFDM_HIP_EINVAL, "a buffer lacks the alignment of one sample");
+    const int rc = gfdm::check_sample_alignment(out, sc16 ? 4 : 8, frames, sizeof(cf));
+    if (rc != GFDM_HIP_OK) return rc;
     ShapeArgs a = { frames, h->F, n_bursts, l.count, l.starts, l.first, l.stride, l.out_len, h->sr, h->si, nullptr };
     if (sc16 && peak > 0.0) {
         if (!workspace || misaligned(workspace, 16)) return api_fail(GFDM_HIP_EINVAL, "normalised sc16 output needs a 16-byte aligned workspace");
@@ -305,9 +284,7 @@ int shaper_enqueue(gfdm_hip_burst_shaper* h, int sc16, void* out, const cf* fram
         GFDM_TRY(hipGetLastError());
         a.gain = res;
     }
-    const int vps = sc16 ? 4 : 2;
-    const int64_t ntiles = ((l.out_len + vps - 1) / vps + 1 + kTileVec - 1) / kTileVec;      // + 1: an unaligned `out` adds a vector
-    const dim3 grid((unsigned)std::min<int64_t>(ntiles, kMaxTiles));
+    const dim3 grid((unsigned)std::min<int64_t>(gfdm::StreamTiles(out, sc16 ? 4 : 2, l.out_len, kTileVec).ntiles, kMaxTiles));
     if (sc16) hipLaunchKernelGGL(k_shaper_place<1>, grid, dim3(kLanes), 0, s, a, out);
     else hipLaunchKernelGGL(k_shaper_place<0>, grid, dim3(kLanes), 0, s, a, out);
     GFDM_TRY(hipGetLastError());

@@ -1096,6 +1096,20 @@ def awgn_noise_voltage(signal, snr_db, rate=1.0):
     return float(np.sqrt(2.0 * variance))
 
 
+def _apply_stream(kernel, stem, x, history, offset, sc16, gain, out, stream):
+    """what ChannelModel.apply and FadingModel.apply share: <stem>[_sc16] on the history + n complex64 samples of x, n samples out"""
+    x = ops.operand(x, C64, "x", kernel._dev, floating=True)
+    ops.check_result(out, x, I16 if sc16 else C64, kernel._dev, as_what="x")
+    history, offset = int(history), int(offset)
+    size = ops.size(x)
+    if history < 0 or history > size:
+        raise ValueError("history(%d) must lie in 0 .. the size of x(%d)" % (history, size))
+    n = size - history
+    res = ops.stream_result(x, n, sc16, kernel._dev, out, "x")
+    kernel._run(stem + ("_sc16" if sc16 else ""), x, (ops.ptr(res), ops.ptr(x) + 8 * history, n, history, offset) + ((float(gain),) if sc16 else ()), stream)
+    return res
+
+
 class ChannelModel(_Kernel):
     """Multipath, frequency offset and noise on a stream, on the device (contract in include/gfdm_hip.h, gfdm_hip_channel_model): GNU
     Radio's channels.channel_model in its argument order, between BurstShaper.place and BurstSync.detect.  y = FIR(taps) of x, times
@@ -1156,17 +1170,7 @@ class ChannelModel(_Kernel):
         given).  sc16=True writes int16 I/Q of shape (n, 2), truncated and saturated, of y * gain."""
         if not sc16 and float(gain) != 1.0:
             raise ValueError("gain scales sc16 output: pass sc16=True (complex64 output is not scaled)")
-        x = ops.operand(x, C64, "x", self._dev, floating=True)
-        ops.check_result(out, x, I16 if sc16 else C64, self._dev, as_what="x")
-        history, offset = int(history), int(offset)
-        size = ops.size(x)
-        if history < 0 or history > size:
-            raise ValueError("history(%d) must lie in 0 .. the size of x(%d)" % (history, size))
-        n = size - history
-        res = ops.stream_result(x, n, sc16, self._dev, out, "x")
-        self._run("gfdm_hip_channel_model_apply" + ("_sc16" if sc16 else ""), x,
-                  (ops.ptr(res), ops.ptr(x) + 8 * history, n, history, offset) + ((float(gain),) if sc16 else ()), stream)
-        return res
+        return _apply_stream(self, "gfdm_hip_channel_model_apply", x, history, offset, sc16, gain, out, stream)
 
 
 _U64 = (1 << 64) - 1
@@ -1317,17 +1321,7 @@ class FadingModel(_Kernel):
         sc16 = bool(sc16)
         if not sc16 and float(gain) != 1.0:
             raise ValueError("gain scales sc16 output: pass an int16 out or sc16=True (complex64 output is not scaled)")
-        x = ops.operand(x, C64, "x", self._dev, floating=True)
-        ops.check_result(out, x, I16 if sc16 else C64, self._dev, as_what="x")
-        history, offset = int(history), int(offset)
-        size = ops.size(x)
-        if history < 0 or history > size:
-            raise ValueError("history(%d) must lie in 0 .. the size of x(%d)" % (history, size))
-        n = size - history
-        res = ops.stream_result(x, n, sc16, self._dev, out, "x")
-        self._run("gfdm_hip_fading_model_apply" + ("_sc16" if sc16 else ""), x,
-                  (ops.ptr(res), ops.ptr(x) + 8 * history, n, history, offset) + ((float(gain),) if sc16 else ()), stream)
-        return res
+        return _apply_stream(self, "gfdm_hip_fading_model_apply", x, history, offset, sc16, gain, out, stream)
 
 
 def resampler_step(x):

@@ -7,6 +7,7 @@ host function that copies in -> out) and driven by tests/sanitize/host_fuzz.cc: 
 while calls are in flight, every runtime call failing once, the process ending with builds in flight.  Recipe: tests/sanitize/Makefile.
 The staged host call of csrc/gfdm_hostcall.h (gfdm::HostCall: the *_host entry points of the device modules, whose kernels share a file with their
 host code and so cannot be compiled against the loop-back layer) has a small driver of its own, tests/sanitize/hostcall_check.cc, under ASan + UBSan.
+The tile geometry and the LDS bounds of the stream stages (csrc/gfdm_streamtile.h, host half) are brute-forced by tests/sanitize/streamtile_check.cc, likewise.
 
 Findings of the first runs (fixed in the product): a stale sticky hipGetLastError() of an earlier failed call failing the next launch, hipEvents leaked when
 their creation failed half way, a device operand with an unmapped tail bounced on the CPU instead of refused.
@@ -80,6 +81,16 @@ def test_staged_host_call_is_clean_under_address_and_ub_sanitizer(tmp_path):
     pkg = mutated_package(tmp_path, "csrc/gfdm_hostcall.h", "GFDM_TRY(hipMalloc(&base_, size_));", "GFDM_TRY(hipMalloc(&base_, size_ - 16));")
     rc, out = run_hostcall(build_hostcall(tmp_path / "b2", pkg), tmp_path)
     assert rc != 0 and "AddressSanitizer: heap-buffer-overflow" in out, out[-3000:]
+
+
+def test_stream_tile_geometry_holds_by_brute_force_under_address_and_ub_sanitizer(tmp_path):
+    """The host half of csrc/gfdm_streamtile.h, which the kernels and the enqueue functions of the four stream stages share, driven by
+    tests/sanitize/streamtile_check.cc: the tiles partition the stream for every alignment, tile size and length, the whole-vector predicate is
+    exact, and max_groups / max_stage, which size the lanes' shares and the LDS arrays, are never exceeded and are reached."""
+    out = tmp_path / "build"
+    subprocess.run(["make", "-C", SAN, "-j4", "streamtile", "OUT=" + str(out)], check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    rc, text = run_hostcall(os.path.join(str(out), "streamtile_check_asan"), tmp_path)
+    assert rc == 0 and "streamtile check OK" in text and "Sanitizer" not in text and "runtime error" not in text, text[-6000:]
 
 
 def mutated_package(tmp_path, path, old, new):
