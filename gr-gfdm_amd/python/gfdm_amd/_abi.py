@@ -215,6 +215,19 @@ def _signatures():
     fn("frame_check_check", i32, i64, u64, u64, i32, i64)
     call("frame_check_attach", vp, vp, vp, i64, i64, i64)
     call("frame_check_verify", vp, vp, vp, vp, vp, vp, i64, i64, i64)
+
+    # ---- spectrum meter: every call on samples has an sc16 twin with the same signature ----
+    fn("spectrum_meter_create", i32, out(vp), vp, i32, i64, i32)
+    getters("spectrum_meter", "destroy nfft")
+    getters("spectrum_meter", "hop totals_bytes", i64)
+    fn("spectrum_meter_window", i32, vp, vp)
+    fn("spectrum_meter_plan", i32, i32, i64, i64, out(i64), out(i64))
+    fn("spectrum_meter_totals_device", vp, vp)
+    fn("spectrum_meter_reset", i32, vp, vp)
+    fn("spectrum_meter_read", i32, vp, vp, vp, vp, vp, vp)
+    call("spectrum_meter_accumulate", vp, i64, sc16=())
+    call("spectrum_meter_accumulate_at", vp, i64, vp, vp, i64, i64, i64, sc16=())
+    call("spectrum_meter_power", vp, i64, sc16=())
     return sig
 
 

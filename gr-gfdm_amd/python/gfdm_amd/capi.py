@@ -1564,6 +1564,207 @@ class LinkMeter(_Rows):
         return res
 
 
+SPECTRUM_WINDOWS = {
+    # cosine-sum windows, periodic form (the period is nfft, as scipy.signal.get_window(name, nfft) has it): sum_i (-1)^i a_i cos(2 pi i n / nfft)
+    "rect": (1.0,),
+    "hann": (0.5, 0.5),
+    "blackmanharris": (0.35875, 0.48829, 0.14128, 0.01168),
+    "flattop": (0.21557895, 0.41663158, 0.277263158, 0.083578947, 0.006947368),
+}
+
+
+def spectrum_window(name, nfft):
+    """A window of SpectrumMeter: float32 (nfft,), 'rect' | 'hann' | 'blackmanharris' | 'flattop', the periodic cosine sums of
+    SPECTRUM_WINDOWS computed in float64 and rounded once."""
+    if name not in SPECTRUM_WINDOWS:
+        raise ValueError("window must be one of %s, not %r" % (", ".join(sorted(SPECTRUM_WINDOWS)), name))
+    nfft = int(nfft)
+    if nfft < 1:
+        raise ValueError("nfft(%d) must be >= 1" % nfft)
+    n = np.arange(nfft, dtype=np.float64)
+    w = np.zeros(nfft, np.float64)
+    for i, a in enumerate(SPECTRUM_WINDOWS[name]):
+        w += (-1.0) ** i * a * np.cos(2.0 * np.pi * i * n / nfft)
+    return w.astype(np.float32)
+
+
+def subcarrier_power(P, K):
+    """The power of each of K subcarriers in a PSD P (FFT order, DC at 0, len(P) a multiple of K): the bins of subcarrier k are
+    [(k - 1/2) nfft / K, (k + 1/2) nfft / K), cyclic; where nfft / K is odd the half bin is rounded down (the range starts at
+    ceil((k - 1/2) nfft / K)).  float64 (K,), adding up to sum(P)."""
+    P = np.asarray(P, dtype=np.float64).ravel()
+    K = int(K)
+    if K < 1 or P.size % K:
+        raise ValueError("the PSD's size(%d) must be a multiple of K(%d)" % (P.size, K))
+    per = P.size // K
+    return np.roll(P, per // 2).reshape(K, per).sum(axis=1)
+
+
+def oob_ratio_db(P, K, subcarrier_map):
+    """10 log10(power of the subcarriers outside subcarrier_map / power of those in it) of a PSD P, by subcarrier_power: the out-of-band
+    emission as a ratio to the occupied band.  -inf where nothing lies outside, nan where the map is empty."""
+    sc = subcarrier_power(P, K)
+    inside = np.zeros(int(K), bool)
+    inside[np.asarray(subcarrier_map, dtype=np.int64).ravel() % int(K)] = True
+    if not inside.any():
+        return float("nan")
+    with np.errstate(divide="ignore"):
+        return float(10.0 * np.log10(sc[~inside].sum() / sc[inside].sum()))
+
+
+class SpectrumMeter(_Kernel):
+    """What the waveform looks like on the air, on the device (contract in include/gfdm_hip.h, gfdm_hip_spectrum_meter): update() adds the
+    Welch periodograms of a stream's segments of nfft samples every hop to psd_sum, update_at() those of the bursts BurstSync.detect
+    found in a capture, power() adds every sample's power to a histogram, a sum and a peak; all of it stays on the device until read().
+    window: a name of spectrum_window or a real float32 array (nfft,); hop defaults to nfft // 2; both are fixed.  numpy arrays run the
+    host flavour; torch device tensors the device flavour on the current stream unless given.  complex64 samples, or int16 I/Q of
+    shape (n, 2) or (2n,) (sc16, read as it is, unscaled)."""
+    _destroy = "gfdm_hip_spectrum_meter_destroy"
+    HEAD = ("segments", "bad_segments", "samples", "bad_samples", "peak_bits")
+    HIST_BINS = 512
+
+    def __init__(self, nfft, window="hann", hop=None, device=None):
+        nfft = int(nfft)
+        hop = nfft // 2 if hop is None else int(hop)
+        if isinstance(window, str):
+            if nfft < 1:
+                raise ValueError("nfft must be a power of two in 16 .. 4096")
+            window = spectrum_window(window, nfft)
+        w = np.ascontiguousarray(window, dtype=np.float32).ravel()
+        if w.size != nfft:
+            raise ValueError("the window has %d values, expected nfft(%d)" % (w.size, nfft))
+        h = ctypes.c_void_p()
+        dev = 0 if device is None else int(device)
+        _check(lib().gfdm_hip_spectrum_meter_create(ctypes.byref(h), w.ctypes.data, nfft, hop, dev))
+        self._h = h
+        self._dev = dev
+        self._nfft, self._hop = nfft, hop
+        self._w = w.copy()
+
+    def nfft(self):
+        return lib().gfdm_hip_spectrum_meter_nfft(self._h)
+
+    def hop(self):
+        return lib().gfdm_hip_spectrum_meter_hop(self._h)
+
+    def window(self):
+        """the window as given at create (float32 (nfft,), bit for bit)"""
+        w = np.empty(self._nfft, np.float32)
+        _check(lib().gfdm_hip_spectrum_meter_window(self._h, w.ctypes.data))
+        return w
+
+    @staticmethod
+    def plan_for(nfft, hop, n):
+        """(n_seg, advance) of n samples: gfdm_hip_spectrum_meter_plan, host arithmetic"""
+        n_seg, adv = ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().gfdm_hip_spectrum_meter_plan(int(nfft), int(hop), int(n), ctypes.byref(n_seg), ctypes.byref(adv)))
+        return n_seg.value, adv.value
+
+    def plan(self, n):
+        """(n_seg, advance) of a piece of n samples: the segments that lie inside it, and how many samples further on the next piece of
+        a cut stream starts"""
+        return self.plan_for(self._nfft, self._hop, n)
+
+    def _settle(self, lead):
+        """the host flavours run on the handle's own stream: what torch's current stream still holds for this handle (a reset) goes first"""
+        if ops.on_device(lead):
+            return
+        try:
+            import torch
+        except ImportError:
+            return
+        if torch.cuda.is_available():
+            torch.cuda.current_stream(self._dev).synchronize()
+
+    def update(self, x, stream=None):
+        """add the periodograms of x's segments to psd_sum; returns plan(len(x))'s advance"""
+        x, n, infix = ops.capture(x, self._dev, "x")
+        self._settle(x)
+        self._run("gfdm_hip_spectrum_meter_accumulate" + infix, x, (ops.ptr(x), n), stream)
+        return self.plan(n)[1]
+
+    def update_at(self, x, starts, seg_per_burst, first=0, count=None, stream=None):
+        """add the periodograms of seg_per_burst segments of every burst of the capture x: segment (b, j) starts at starts[b] + first +
+        j hop; starts int64 (n_bursts,) and count as BurstSync.detect gives them (negative starts, bursts from count on and segments that
+        do not lie inside x are skipped)"""
+        x, n, infix = ops.capture(x, self._dev, "x")
+        starts = ops.vector(starts, I64, "starts", self._dev, x, as_what="x")
+        cnt = ops.count_arg(count, x, self._dev)
+        self._settle(x)
+        self._run("gfdm_hip_spectrum_meter_accumulate_at" + infix, x, (ops.ptr(x), n, ops.ptr(starts), ops.ptr(cnt), int(first), int(seg_per_burst),
+                                                                       ops.size(starts)), stream)
+
+    def power(self, x, stream=None):
+        """add every sample's power to the histogram, power_sum, the peak and the sample counters"""
+        x, n, infix = ops.capture(x, self._dev, "x")
+        self._settle(x)
+        self._run("gfdm_hip_spectrum_meter_power" + infix, x, (ops.ptr(x), n), stream)
+
+    def reset(self, stream=None):
+        """enqueue the zeroing of the totals"""
+        _check(lib().gfdm_hip_spectrum_meter_reset(self._h, self._sp(stream)))
+
+    def totals_ptr(self):
+        """device pointer of the totals (gfdm_hip_spectrum_meter_totals_device): int64[8] | float64 | float64[nfft] | int64[512]"""
+        return lib().gfdm_hip_spectrum_meter_totals_device(self._h)
+
+    def totals_bytes(self):
+        return _bytes(lib().gfdm_hip_spectrum_meter_totals_bytes(self._h))
+
+    def read(self, stream=None):
+        """synchronises the stream and reads the totals: dict(segments, bad_segments, samples, bad_samples, peak_bits: ints; power_sum: a
+        float; psd_sum: float64 (nfft,), FFT order; hist: int64 (512,))"""
+        head, ps = np.zeros(8, np.int64), np.zeros(1, np.float64)
+        psd, hist = np.zeros(self._nfft, np.float64), np.zeros(self.HIST_BINS, np.int64)
+        _check(lib().gfdm_hip_spectrum_meter_read(self._h, head.ctypes.data, ps.ctypes.data, psd.ctypes.data, hist.ctypes.data, self._sp(stream)))
+        t = {name: int(head[i]) for i, name in enumerate(self.HEAD)}
+        t.update(power_sum=float(ps[0]), psd_sum=psd, hist=hist)
+        return t
+
+    def psd(self, shift=False, stream=None):
+        """psd_sum / (segments nfft sum(w^2)): for a stationary input its bins add up to the mean |x|^2.  shift: DC in the middle
+        (numpy.fft.fftshift).  nan where no segment was counted."""
+        t = self.read(stream)
+        den = t["segments"] * self._nfft * float(np.sum(self._w.astype(np.float64) ** 2))
+        P = t["psd_sum"] / den if den else np.full(self._nfft, np.nan)
+        return np.fft.fftshift(P) if shift else P
+
+    def band_power(self, lo, hi, stream=None):
+        """the sum of psd() over the bins lo .. hi - 1, cyclic (lo may be negative: band_power(-4, 5) is nine bins around DC)"""
+        P = self.psd(stream=stream)
+        return float(P[np.arange(int(lo), int(hi)) % self._nfft].sum())
+
+    def mean_power(self, stream=None):
+        """power_sum / samples of power(); nan where no sample was counted"""
+        t = self.read(stream)
+        return t["power_sum"] / t["samples"] if t["samples"] else float("nan")
+
+    def peak_power(self, stream=None):
+        """the largest finite sample power power() has seen (peak_bits as the float32 it is)"""
+        return float(np.array([self.read(stream)["peak_bits"]], np.uint32).view(np.float32)[0])
+
+    def papr_db(self, stream=None):
+        """10 log10(peak power / mean power) of power(); nan where no sample was counted or the mean is 0"""
+        t = self.read(stream)
+        if not t["samples"] or not t["power_sum"] > 0.0:
+            return float("nan")
+        peak = float(np.array([t["peak_bits"]], np.uint32).view(np.float32)[0])
+        return float(10.0 * np.log10(peak / (t["power_sum"] / t["samples"])))
+
+    @staticmethod
+    def hist_edges():
+        """the lower edges of the 512 histogram bins, float64: (1 + (i mod 8) / 8) 2^(i // 8 - 32); bin 0 also holds everything below"""
+        i = np.arange(SpectrumMeter.HIST_BINS)
+        return (1.0 + (i % 8) / 8.0) * np.exp2(i // 8 - 32.0)
+
+    def ccdf(self, stream=None):
+        """(edges, tail): the lower edge of every histogram bin relative to the mean power, and the number of counted samples whose power
+        lies in that bin or above -- tail / samples is the CCDF of the instantaneous power at the edges, exact at every edge but bin 0's"""
+        t = self.read(stream)
+        mean = t["power_sum"] / t["samples"] if t["samples"] else float("nan")
+        return self.hist_edges() / mean, np.cumsum(t["hist"][::-1])[::-1]
+
+
 CC_MODES = {"terminated": 0, "truncated": 1}
 CC_TERMINATED, CC_TRUNCATED = "terminated", "truncated"                   # the keys of CC_MODES, as mode() reports them
 

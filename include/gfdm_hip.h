@@ -1273,6 +1273,90 @@ int gfdm_hip_frame_check_verify_host(gfdm_hip_frame_check* c, uint8_t* payload, 
 int gfdm_hip_frame_check_verify_device(gfdm_hip_frame_check* c, void* payload, void* ok, void* good_row, void* n_good, const void* frames,
                                        const void* count, int64_t in_row_bytes, int64_t out_row_bytes, int64_t n_rows, void* stream);
 
+/* ---- gfdm_hip_spectrum_meter: Welch PSD and power statistics (PAPR, CCDF) of a stream or of the bursts of a capture ------------------
+ * The third meter beside the shaper's peak and the link meter: what the waveform looks like on the air.  Two independent accumulators
+ * in totals that stay on the device; a curve point is a fixed-shape, hipGraph-capturable sequence of launches and one read at the end.
+ * create: window real float32[nfft], fixed at create (no setter, neither for the hop); nfft = 2^a, 4 <= a <= 12; 1 <= hop <= nfft.
+ *   GFDM_HIP_EINVAL: any other nfft or hop; a NULL window; a window value that is not finite.  Getters: nfft, hop, window (bit for bit).
+ * totals: the handle owns, on the device, zero at create, contiguous in this order (totals_bytes() = 8 (8 + 1 + nfft + 512) bytes):
+ *     head      int64[8]      0 segments  1 bad_segments  2 samples  3 bad_samples  4 peak_bits  5 .. 7 reserved (stay 0)
+ *     power_sum float64       sum of the counted sample powers
+ *     psd_sum   float64[nfft] FFT order, DC at 0
+ *     hist      int64[512]    power histogram
+ *   totals_device returns the pointer; reset enqueues the zeroing on `stream` (one kernel, capturable); read synchronises `stream` and
+ *   copies the parts out (any of the four outputs may be NULL).  Calls that add to one handle's totals -- and they share the handle's
+ *   partial rows -- are ordered by the caller's streams: the *_host flavours run on the handle's own stream, so a reset or *_device
+ *   call on another stream must have completed before one of them is made, and two calls on one handle never run concurrently.
+ * PSD accumulator (accumulate, accumulate_at): segment s of accumulate is in[s hop .. s hop + nfft), n_seg = n < nfft ? 0 :
+ *   (n - nfft) / hop + 1.  plan(nfft, hop, n, &n_seg, &advance) gives n_seg and advance = n_seg hop, host arithmetic: the next call of a
+ *   cut stream starts at in + advance.  n_seg == 0 returns GFDM_HIP_OK without a launch.  Per segment
+ *       X_s[k] = sum_n x[n] w[n] exp(-2 pi j n k / nfft),   psd_sum[k] += |X_s[k]|^2
+ *   The product x w, the transform and |X|^2 are fp32; the sum over the segments is fp64: a workgroup owns a contiguous run of segments and
+ *   keeps its bins in fp64 registers, the at most 1024 workgroups write one partial row each, and a second kernel adds the rows in ascending
+ *   order into psd_sum and bumps the counters.  The order is a function of (n_seg, nfft) alone -- not of the alignment of `in`, not of
+ *   arrival: no float atomics, two calls on the same input give bit-equal totals.  The handle owns the 1024 x nfft partials (no workspace).
+ *   A segment that holds a non-finite sample, or a sample whose fp32 product with its window value is not finite (an overflow), adds
+ *   nothing to psd_sum and counts in bad_segments, not in segments: psd_sum stays finite whatever the input; every other segment
+ *   counts in segments.  sc16: one 4-byte load per sample, widened unscaled; bit-equal to the complex64 call on the widened capture.
+ *   accumulate_at: the dual of place / find_frame_start_at.  starts int64[n_bursts] and the optional count are device arrays exactly as
+ *   detect writes them (host arrays in the *_host flavour); segment (b, j), j < seg_per_burst, starts at o = starts[b] + first + j hop
+ *   and is LIVE iff b < clamp(*count, 0, n_bursts), 0 <= starts[b] <= 2^61, o >= 0 and o + nfft <= stream_len.  Other segments are
+ *   skipped, never read and not counted.  The shape is fixed by (seg_per_burst, n_bursts): graph-capturable, a replay follows starts and
+ *   count.  The same kernel with another origin map.
+ *   GFDM_HIP_EINVAL: n < 0 or > 2^61; stream_len outside 0 .. 2^61; |first| > 2^60; seg_per_burst or n_bursts < 0; seg_per_burst *
+ *   n_bursts > 2^40; a NULL buffer the call would touch; a buffer without the alignment of one element (8 bytes complex64, 4 sc16,
+ *   8 int64).
+ * Power accumulator (power): over every sample once, p = fadd_rn(fmul_rn(re, re), fmul_rn(im, im)) in fp32, no contraction (numpy's
+ *   float32 reproduces it to the bit).  A non-finite p (an overflow included) counts in bad_samples and nowhere else.  A finite p:
+ *     samples += 1;  peak_bits = max(peak_bits, bits(p)) (p >= +0: floats order as their bits; exact);  power_sum += p;
+ *     hist[clamp((bits(p) >> 20) - 760, 0, 511)] += 1: eight bins per octave from 2^-32 to 2^32, bin 0 also takes everything below
+ *     (zero and denormals: the flush mode cannot matter), bin 511 everything above; the lower edge of bin i is
+ *     (1 + (i mod 8) / 8) 2^(floor(i / 8) - 32): the bins are pure integer rules on the bits of p.
+ *   hist, samples, bad_samples: 64-bit integer atomics (exact, order-free); peak_bits: one atomic max; power_sum: fp64 partials per
+ *   workgroup in tile order (tiles of 2048 samples), then the ordered sum pass.  No float atomics.
+ * Error budget (derived, not measured) against the same formulas in float64 on the same float32 inputs, after any sequence of calls:
+ *     |psd_sum[k] - ref[k]| <= sum_s (2 |X_s[k]| d_s + d_s^2) + 2^-40 ref[k],   d_s = (8 log2 nfft + 8) 2^-24 sqrt(nfft E_s),
+ *     E_s = sum_n |x_n|^2 w_n^2    (Higham, Accuracy and Stability of Numerical Algorithms, Thm 24.2, at 6.7 eps per radix-2 stage, widened
+ *     for the window product and the squared magnitude; the last term covers the fp64 sums)
+ *     |power_sum - ref| <= (tiles + 32) 2^-53 ref, tiles = ceil(n / 2048) summed over the calls (all terms are non-negative)
+ *   segments, bad_segments, samples, bad_samples, peak_bits and hist are exact.
+ * *_device: `in` has the alignment of one sample and no more; the calls neither allocate nor synchronise and are hipGraph-capturable.
+ * *_host: a convenience, not a pipeline: upload, the device call on the handle's stream, one synchronise.
+ * Not here: nfft that is no power of two or above 4096; cross-spectra and coherence; a spectrogram (the PSD is averaged only); a PA
+ *   non-linearity to drive the meter with; per-burst PAPR (power on shaped frames gives the ensemble); setters for window or hop.
+ * Tested range (tests/test_spectrum_meter_gpu.py against the numpy restatement of tests/spectrum_meter_ref.py): every nfft 16 .. 4096
+ *   with a Hann window; hop 1, 3, nfft / 2, nfft - 1, nfft at nfft 16 and 64; n = nfft - 1, nfft, nfft + hop - 1; `in` at every alignment
+ *   of one sample; sc16 against the widened call; repeated and cut streams; a NaN segment; accumulate_at with permuted starts, -1, a burst
+ *   past stream_len and count below, at and beyond n_bursts; a window value of 3e38; power on 100 003 samples spanning 2^-40 .. 2^40; one graph replay;
+ *   2 G + 3 trips past the bounded grid (tests/test_spectrum_grid_bound_gpu.py). */
+typedef struct gfdm_hip_spectrum_meter gfdm_hip_spectrum_meter;
+int gfdm_hip_spectrum_meter_create(gfdm_hip_spectrum_meter** out, const float* window, int nfft, int64_t hop, int device);
+int gfdm_hip_spectrum_meter_destroy(gfdm_hip_spectrum_meter* m);
+int gfdm_hip_spectrum_meter_nfft(const gfdm_hip_spectrum_meter* m);
+int64_t gfdm_hip_spectrum_meter_hop(const gfdm_hip_spectrum_meter* m);
+int gfdm_hip_spectrum_meter_window(const gfdm_hip_spectrum_meter* m, float* window);
+int gfdm_hip_spectrum_meter_plan(int nfft, int64_t hop, int64_t n, int64_t* n_seg, int64_t* advance);
+void* gfdm_hip_spectrum_meter_totals_device(gfdm_hip_spectrum_meter* m);
+int64_t gfdm_hip_spectrum_meter_totals_bytes(const gfdm_hip_spectrum_meter* m);
+int gfdm_hip_spectrum_meter_reset(gfdm_hip_spectrum_meter* m, void* stream);
+int gfdm_hip_spectrum_meter_read(gfdm_hip_spectrum_meter* m, int64_t* head, double* power_sum, double* psd_sum, int64_t* hist, void* stream);
+int gfdm_hip_spectrum_meter_accumulate_host(gfdm_hip_spectrum_meter* m, const float* in, int64_t n);
+int gfdm_hip_spectrum_meter_accumulate_device(gfdm_hip_spectrum_meter* m, const void* in, int64_t n, void* stream);
+int gfdm_hip_spectrum_meter_accumulate_sc16_host(gfdm_hip_spectrum_meter* m, const int16_t* in, int64_t n);
+int gfdm_hip_spectrum_meter_accumulate_sc16_device(gfdm_hip_spectrum_meter* m, const void* in, int64_t n, void* stream);
+int gfdm_hip_spectrum_meter_accumulate_at_host(gfdm_hip_spectrum_meter* m, const float* in, int64_t stream_len, const int64_t* starts, const int64_t* count,
+                                               int64_t first, int64_t seg_per_burst, int64_t n_bursts);
+int gfdm_hip_spectrum_meter_accumulate_at_device(gfdm_hip_spectrum_meter* m, const void* in, int64_t stream_len, const void* starts, const void* count,
+                                                 int64_t first, int64_t seg_per_burst, int64_t n_bursts, void* stream);
+int gfdm_hip_spectrum_meter_accumulate_at_sc16_host(gfdm_hip_spectrum_meter* m, const int16_t* in, int64_t stream_len, const int64_t* starts,
+                                                    const int64_t* count, int64_t first, int64_t seg_per_burst, int64_t n_bursts);
+int gfdm_hip_spectrum_meter_accumulate_at_sc16_device(gfdm_hip_spectrum_meter* m, const void* in, int64_t stream_len, const void* starts, const void* count,
+                                                      int64_t first, int64_t seg_per_burst, int64_t n_bursts, void* stream);
+int gfdm_hip_spectrum_meter_power_host(gfdm_hip_spectrum_meter* m, const float* in, int64_t n);
+int gfdm_hip_spectrum_meter_power_device(gfdm_hip_spectrum_meter* m, const void* in, int64_t n, void* stream);
+int gfdm_hip_spectrum_meter_power_sc16_host(gfdm_hip_spectrum_meter* m, const int16_t* in, int64_t n);
+int gfdm_hip_spectrum_meter_power_sc16_device(gfdm_hip_spectrum_meter* m, const void* in, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
