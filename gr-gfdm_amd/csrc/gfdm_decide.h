@@ -17,24 +17,6 @@ __host__ __device__ __forceinline__ int64_t live_rows(const int64_t* count, int6
     return std::min(std::max(*count, (int64_t)0), n_rows);
 }
 
-// (row, index in the row) of the flat element d behind the one at (r0, i0); rows of n elements, i0 < n.  No 64-bit division: past the
-// first row what is left of d is below 2^32, and so is n where a quotient is needed at all.
-struct RowPos { int64_t r, i; };
-__device__ __forceinline__ RowPos advance(int64_t r0, int64_t i0, uint32_t d, int64_t n)
-{
-    RowPos p = { r0, i0 + (int64_t)d };
-    if (p.i >= n) {
-        p.i -= n;
-        ++p.r;
-        if (p.i >= n) {
-            const uint32_t q = (uint32_t)p.i / (uint32_t)n;
-            p.r += q;
-            p.i -= (int64_t)q * n;
-        }
-    }
-    return p;
-}
-
 // squared distance in the direct form: the contract's d_i
 __device__ __forceinline__ float dist2(cf x, cf p)
 {

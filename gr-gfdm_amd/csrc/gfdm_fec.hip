@@ -18,21 +18,22 @@
 //              The state is wave-uniform.  The 64 information bits of a chunk are assembled in one word and lanes 0 .. 7 store its bytes.
 //   The hard flavour is the same kernel with the other fetch (template parameter): +1 / -1 from a packed coded row.
 //   Deviation from the first sketch: the LDS of a launch is sized by the row (dynamic), not by the budget, so short rows keep the SIMDs full.
-// encode: element-wise; the flat OUTPUT is tiled as in gfdm_symbols.hip (the grid depends on the total size, never on n_rows), 16-byte
-//   stores where the output is aligned.  Output byte o of a row needs the information bits 4 o - 6 .. 4 o + 3: two bytes, read through the
-//   cache.  The zero padding behind the 2 T coded bits and the spare rows are written by the same kernel.
+// encode: element-wise, on the row stages' tile skeleton (gfdm_rowtile.h).  Output byte o of a row needs the information bits 4 o - 6 ..
+//   4 o + 3: two bytes, read through the cache.  The zero padding behind the 2 T coded bits and the spare rows are written by the same kernel.
 // Not here: tail-biting and streaming modes, other constraint lengths or mother-code rates, int8 LLR input.  Puncturing and interleaving
 // are gfdm_ratematch.hip's.
 #include "../../include/gfdm_hip.h"
 #include "gfdm_decide.h"
 #include "gfdm_hostcall.h"
+#include "gfdm_rowtile.h"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
 
-using gfdm::RowPos;
-using gfdm::advance;
+using gfdm::RowCursor;
+using gfdm::StreamTiles;
+using gfdm::write_elems;
 using gfdm::api_fail;
 using gfdm::check_width;
 using gfdm::live_rows;
@@ -48,6 +49,8 @@ constexpr int kMaxGrid = 2048;                       // decode workgroups per la
 constexpr int kWsWaves = 2048;                       // decode waves per launch of the workspace variant: one workspace slot each
 constexpr int kTileVec = kLanes;                     // encode: 16-byte vectors of output per tile (4 KiB): a byte costs two loads and eight parities, so one vector a lane
 constexpr int kMaxTiles = 8192;
+constexpr int kVps = 16;                             // encode: coded bytes per vector
+static_assert(kVps * kTileVec - 1 <= gfdm::kMaxRowReach, "the in-tile distance of RowCursor::at");
 
 struct DecodeArgs {
     const void* in;              // soft: float [n_rows][stride]; hard: uint8 [n_rows][stride]
@@ -216,38 +219,15 @@ __device__ __forceinline__ unsigned encode_byte(const EncodeArgs& a, const unsig
 __global__ __launch_bounds__(kLanes) void k_cc_encode(EncodeArgs a)
 {
     const int64_t n_live = live_rows(a.count, a.n_rows), orb = a.out_row_bytes;
-    const int64_t total = a.n_rows * orb;
-    const int omis = (int)((uintptr_t)a.out & 15);   // bytes between the 16-byte boundary in front of `out` and `out`
-    const int64_t nvec = (total + omis + 15) / 16;
-    const int64_t ntiles = (nvec + kTileVec - 1) / kTileVec;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t w0 = tile * kTileVec, w1 = std::min(w0 + kTileVec, nvec);
-        const int64_t o_lo = std::max(16 * w0 - omis, (int64_t)0);
-        const int64_t r0 = o_lo / orb, i0 = o_lo - r0 * orb;
+    const StreamTiles tl(a.out, kVps, a.n_rows * orb, kTileVec);
+    for (int64_t tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
+        const auto t = tl.tile(tile);
+        const RowCursor first(t.i_lo, orb);
 #pragma unroll
         for (int u = 0; u < kTileVec / kLanes; ++u) {
-            const int64_t w = w0 + u * kLanes + threadIdx.x;
-            if (w >= w1) continue;
-            const int64_t o0 = 16 * w - omis;
-            unsigned y[4] = { 0u, 0u, 0u, 0u };
-            RowPos pos = advance(r0, i0, (uint32_t)(std::max(o0, (int64_t)0) - o_lo), orb);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int64_t o = o0 + e;
-                if (o < 0 || o >= total) continue;
-                if (pos.r < n_live) y[e >> 2] |= encode_byte(a, a.in + pos.r * a.info_bytes, pos.i) << (8 * (e & 3));
-                if (++pos.i == orb) {
-                    pos.i = 0;
-                    ++pos.r;
-                }
-            }
-            if (o0 >= 0 && o0 + 16 <= total) {       // a whole vector: 16-byte aligned by construction
-                *reinterpret_cast<uint4*>(a.out + o0) = make_uint4(y[0], y[1], y[2], y[3]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (o0 + e >= 0 && o0 + e < total) a.out[o0 + e] = (unsigned char)(y[e >> 2] >> (8 * (e & 3)));
-            }
+            const int64_t w = t.v0 + u * kLanes + threadIdx.x;
+            if (w < t.v1)
+                write_elems<unsigned char, kVps>(a.out, tl, t, first, w, n_live, [&](int64_t r, int64_t i) { return encode_byte(a, a.in + r * a.info_bytes, i); });
         }
     }
 }
@@ -337,9 +317,7 @@ int encode_enqueue(const gfdm_hip_conv_code* h, void* out, const void* data, con
     const Geometry geo = geometry_of(h, n_info);
     const EncodeArgs a = { static_cast<const unsigned char*>(data), static_cast<unsigned char*>(out), static_cast<const int64_t*>(count), n_rows,
                            geo.info_bytes, out_row_bytes, (int)n_info, (int)geo.steps, h->g[0], h->g[1] };
-    const int64_t total = n_rows * out_row_bytes;
-    const int64_t ntiles = (total / 16 + 2 + kTileVec - 1) / kTileVec;               // + 2: a ragged tail, and the vector an unaligned `out` adds
-    hipLaunchKernelGGL(k_cc_encode, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, kMaxTiles))), dim3(kLanes), 0, s, a);
+    hipLaunchKernelGGL(k_cc_encode, dim3(gfdm::row_grid(out, kVps, n_rows * out_row_bytes, kTileVec, kMaxTiles)), dim3(kLanes), 0, s, a);
     GFDM_TRY(hipGetLastError());
     return GFDM_HIP_OK;
 }

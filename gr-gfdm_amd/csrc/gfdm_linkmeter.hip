@@ -17,6 +17,7 @@
 #include "../../include/gfdm_hip.h"
 #include "gfdm_decide.h"
 #include "gfdm_hostcall.h"
+#include "gfdm_rowtile.h"
 
 #include <algorithm>
 #include <climits>

@@ -4,14 +4,12 @@
 //
 // create composes the pattern and the permutation ON THE HOST into two tables that are the same for every row: src[j], the coded bit behind
 // transmitted bit j (n_tx entries), and inv[i], the transmitted bit behind coded bit i or -1 (n_coded entries).  Both live on the device in
-// one allocation.  The kernels are pure gathers over the flat OUTPUT, tiled as in gfdm_symbols.hip and gfdm_fec.hip's encode: the grid
-// depends on the total size, never on n_rows; a tile's (row, index) comes from one 64-bit division per tile and gfdm::advance.
+// one allocation.  The kernels are pure gathers over the flat OUTPUT, on the row stages' tile skeleton (gfdm_rowtile.h).
 //   Table reuse: a workgroup copies its table -- src for match, inv for the two unmatch calls -- into LDS once (4 n_coded bytes at most,
 //   sized by the row: dynamic LDS) and then walks its tiles, so the table is fetched once per workgroup, not once per row.  The grid is
 //   bounded by kMaxGrid, which is what gives a workgroup many rows per copy.  Rows of more than GFDM_HIP_RM_LDS_BITS coded bits read the
 //   table through the cache instead (template parameter).
-//   unmatch / unmatch_hard: a lane builds four floats (four lookups, four 4-byte or 1-byte reads) and stores them as one 16-byte vector;
-//   the vectors are aligned to the 16-byte boundary in front of `out`, so only the first and the last of a call are written by element.
+//   unmatch / unmatch_hard: a lane builds four floats (four lookups, four 4-byte or 1-byte reads) and stores them as one 16-byte vector.
 //   match: a lane builds four bytes (32 lookups and 32 byte reads through the cache) and stores one aligned 4-byte word, 256 contiguous
 //   bytes a wave.  Deviation from a 16-byte store per lane: the kernel is bound by its 8 lookups per output byte, not by its stores, and
 //   a frame's transmitted row is some 80 bytes, so 16 bytes a lane would leave a batch of a few thousand rows on a fraction of the CUs.
@@ -20,21 +18,26 @@
 #include "../../include/gfdm_hip.h"
 #include "gfdm_decide.h"
 #include "gfdm_hostcall.h"
+#include "gfdm_rowtile.h"
 
 #include <algorithm>
 #include <climits>
 #include <vector>
 
-using gfdm::RowPos;
-using gfdm::advance;
+using gfdm::RowCursor;
+using gfdm::StreamTiles;
 using gfdm::api_fail;
 using gfdm::check_width;
 using gfdm::live_rows;
 using gfdm::misaligned;
+using gfdm::row_grid;
+using gfdm::write_elems;
 
 namespace {
 
-constexpr int kLanes = 256;
+constexpr int kLanes = 256;                          // lanes of a workgroup, and vectors (match: words) of a tile: one a lane
+constexpr int kVps = 4;                              // elements of a vector: four floats in 16 bytes, four bytes in a word
+static_assert(kVps * kLanes - 1 <= gfdm::kMaxRowReach, "the in-tile distance of RowCursor::at");
 constexpr int kMaxGrid = 1024;                       // workgroups per launch: four per CU, each walks the tiles beyond
 constexpr int64_t kMaxCoded = (int64_t)1 << 21;      // twice the convolutional code's 2^20 trellis steps
 constexpr int kMaxPeriod = 4096;
@@ -90,35 +93,13 @@ __global__ __launch_bounds__(kLanes) void k_rm_match(MatchArgs a)
     extern __shared__ int32_t lds_table[];
     stage_table<LDS>(lds_table, a.src, a.n_tx);
     const int64_t n_live = live_rows(a.count, a.n_rows), orb = a.out_row_bytes;
-    const int64_t total = a.n_rows * orb;
-    const int omis = (int)((uintptr_t)a.out & 3);    // bytes between the 4-byte boundary in front of `out` and `out`
-    const int64_t nwords = (total + omis + 3) / 4;
-    const int64_t ntiles = (nwords + kLanes - 1) / kLanes;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t w = tile * kLanes + threadIdx.x;
-        if (w >= nwords) continue;
-        const int64_t o_lo = std::max(4 * tile * kLanes - omis, (int64_t)0);
-        const int64_t r0 = o_lo / orb, i0 = o_lo - r0 * orb;
-        const int64_t o0 = 4 * w - omis;
-        RowPos pos = advance(r0, i0, (uint32_t)(std::max(o0, (int64_t)0) - o_lo), orb);
-        unsigned y = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t o = o0 + e;
-            if (o < 0 || o >= total) continue;
-            if (pos.r < n_live) y |= match_byte<LDS>(a, lds_table, a.in + pos.r * a.in_row_bytes, pos.i) << (8 * e);
-            if (++pos.i == orb) {
-                pos.i = 0;
-                ++pos.r;
-            }
-        }
-        if (o0 >= 0 && o0 + 4 <= total) {            // a whole word: 4-byte aligned by construction
-            *reinterpret_cast<uint32_t*>(a.out + o0) = y;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (o0 + e >= 0 && o0 + e < total) a.out[o0 + e] = (unsigned char)(y >> (8 * e));
-        }
+    const StreamTiles tl(a.out, kVps, a.n_rows * orb, kLanes, 4);            // 4-byte words (above)
+    for (int64_t tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
+        const auto t = tl.tile(tile);
+        const int64_t w = t.v0 + threadIdx.x;
+        if (w >= t.v1) continue;
+        write_elems<unsigned char, kVps>(a.out, tl, t, RowCursor(t.i_lo, orb), w, n_live,
+                                         [&](int64_t r, int64_t i) { return match_byte<LDS>(a, lds_table, a.in + r * a.in_row_bytes, i); });
     }
 }
 
@@ -143,35 +124,13 @@ __global__ __launch_bounds__(kLanes) void k_rm_unmatch(UnmatchArgs a)
     extern __shared__ int32_t lds_table[];
     stage_table<LDS>(lds_table, a.inv, a.n_coded);
     const int64_t n_live = live_rows(a.count, a.n_rows), os = a.out_stride;
-    const int64_t total = a.n_rows * os;
-    const int omis = (int)(((uintptr_t)a.out & 15) / 4);                 // floats between the 16-byte boundary in front of `out` and `out`
-    const int64_t nvec = (total + omis + 3) / 4;
-    const int64_t ntiles = (nvec + kLanes - 1) / kLanes;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t w = tile * kLanes + threadIdx.x;
-        if (w >= nvec) continue;
-        const int64_t o_lo = std::max(4 * tile * kLanes - omis, (int64_t)0);
-        const int64_t r0 = o_lo / os, i0 = o_lo - r0 * os;
-        const int64_t o0 = 4 * w - omis;
-        RowPos pos = advance(r0, i0, (uint32_t)(std::max(o0, (int64_t)0) - o_lo), os);
-        uint32_t y[4] = { 0u, 0u, 0u, 0u };
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t o = o0 + e;
-            if (o < 0 || o >= total) continue;
-            if (pos.r < n_live) y[e] = unmatch_value<HARD, LDS>(a, lds_table, pos.r, pos.i);
-            if (++pos.i == os) {
-                pos.i = 0;
-                ++pos.r;
-            }
-        }
-        if (o0 >= 0 && o0 + 4 <= total) {            // a whole vector: 16-byte aligned by construction
-            *reinterpret_cast<uint4*>(a.out + o0) = make_uint4(y[0], y[1], y[2], y[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (o0 + e >= 0 && o0 + e < total) a.out[o0 + e] = y[e];
-        }
+    const StreamTiles tl(a.out, kVps, a.n_rows * os, kLanes);
+    for (int64_t tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
+        const auto t = tl.tile(tile);
+        const int64_t w = t.v0 + threadIdx.x;
+        if (w >= t.v1) continue;
+        write_elems<uint32_t, kVps>(a.out, tl, t, RowCursor(t.i_lo, os), w, n_live,
+                                    [&](int64_t r, int64_t i) { return unmatch_value<HARD, LDS>(a, lds_table, r, i); });
     }
 }
 
@@ -294,12 +253,6 @@ int check_call(const gfdm_hip_rate_matcher* h, Op op, const void* out, const voi
     return GFDM_HIP_OK;
 }
 
-unsigned grid_for(int64_t elements_of_four)
-{
-    const int64_t ntiles = (elements_of_four + 2 + kLanes - 1) / kLanes;             // + 2: a ragged tail, and the word / vector an unaligned `out` adds
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, kMaxGrid));
-}
-
 // the one launch of a call.  Everything is a device pointer.
 int enqueue(const gfdm_hip_rate_matcher* h, Op op, void* out, const void* in, const void* count, int64_t in_width, int64_t out_width, int64_t n_rows,
             hipStream_t s)
@@ -312,12 +265,12 @@ int enqueue(const gfdm_hip_rate_matcher* h, Op op, void* out, const void* in, co
     if (op == OP_MATCH) {
         const MatchArgs a = { static_cast<const unsigned char*>(in), static_cast<unsigned char*>(out), static_cast<const int64_t*>(count), h->d_src(),
                               n_rows, in_width, out_width, (int)h->n_tx };
-        const dim3 grid(grid_for(n_rows * out_width / 4));
+        const dim3 grid(row_grid(out, kVps, n_rows * out_width, kLanes, kMaxGrid, 4));
         if (lds) hipLaunchKernelGGL(k_rm_match<true>, grid, block, (size_t)h->n_tx * sizeof(int32_t), s, a);
         else hipLaunchKernelGGL(k_rm_match<false>, grid, block, 0, s, a);
     } else {
         const UnmatchArgs a = { in, static_cast<uint32_t*>(out), static_cast<const int64_t*>(count), h->d_inv(), n_rows, in_width, out_width, (int)h->n_coded };
-        const dim3 grid(grid_for(n_rows * out_width / 4));
+        const dim3 grid(row_grid(out, kVps, n_rows * out_width, kLanes, kMaxGrid));
         const size_t bytes = lds ? (size_t)h->n_coded * sizeof(int32_t) : 0;
         if (op == OP_SOFT) {
             if (lds) hipLaunchKernelGGL((k_rm_unmatch<false, true>), grid, block, bytes, s, a);

@@ -26,15 +26,16 @@ struct TileSpan {
     int64_t v0, v1, s0, i_lo, i_hi;
 };
 
-// the tiles of a stream of n samples at `out`: vps samples per 16-byte vector, tile_vec vectors per tile (a constant folds).  For n >= 1
-// every tile holds a sample; the enqueue functions return before a launch with n = 0 (an unaligned `out` would give one empty tile)
+// the tiles of a stream of n samples at `out`: vps samples per 16-byte vector (vec_bytes: the row stages of gfdm_rowtile.h have one of 4
+// bytes), tile_vec vectors per tile (a constant folds).  For n >= 1 every tile holds a sample; the enqueue functions return before a
+// launch with n = 0 (an unaligned `out` would give one empty tile)
 struct StreamTiles {
     int vps, tile_vec;
-    int mis;                 // samples between the 16-byte boundary in front of `out` and `out`
+    int mis;                 // samples between the vector boundary in front of `out` and `out`
     int64_t n, nvec, ntiles;
 
-    __host__ __device__ __forceinline__ StreamTiles(const void* out, int vps_, int64_t n_, int tile_vec_)
-        : vps(vps_), tile_vec(tile_vec_), mis((int)(((uintptr_t)out / (16 / vps_)) % vps_)), n(n_), nvec((n_ + mis + vps_ - 1) / vps_),
+    __host__ __device__ __forceinline__ StreamTiles(const void* out, int vps_, int64_t n_, int tile_vec_, int vec_bytes = 16)
+        : vps(vps_), tile_vec(tile_vec_), mis((int)(((uintptr_t)out / (vec_bytes / vps_)) % vps_)), n(n_), nvec((n_ + mis + vps_ - 1) / vps_),
           ntiles((nvec + tile_vec_ - 1) / tile_vec_)
     {
     }

@@ -3,9 +3,9 @@
 // constellation_decoder_cb + repack_bits_bb(k -> 8); pygfdm's bits2symbols / symbols2bits).  The contract is written out in
 // include/gfdm_hip.h.
 //
-// Three element-wise kernels, memory bound by design.  As in gfdm_shaper.hip the OUTPUT is tiled, never the rows: a workgroup takes a
-// fixed stretch of the flat output, so the grid depends on the total size alone and 32768 + 7 rows of 5 symbols spread as evenly as one
-// row of 2^20.  A tile finds the row of its first element by one division; every other element steps on from there.
+// Three element-wise kernels, memory bound by design.  The OUTPUT is tiled, never the rows: a workgroup takes a fixed stretch of the flat
+// output, so 32768 + 7 rows of 5 symbols spread as evenly as one row of 2^20.  map and soft stand on the row stages' tile skeleton
+// (gfdm_rowtile.h); decode has byte stores and no aligned output vector, and tiles by itself.
 //   decode: a tile is 256 k packed bytes.  The symbols behind them are ONE contiguous stretch of the input (at most 2048 + 2: rows are
 //           contiguous on both sides); the lanes load it as 16-byte vectors aligned in memory (two symbols a lane, 1 KiB a wave; a head that
 //           is only 8-byte aligned and a ragged tail go element by element), decide at once and leave one index byte per symbol in LDS.
@@ -18,6 +18,7 @@
 #include "../../include/gfdm_hip.h"
 #include "gfdm_decide.h"
 #include "gfdm_hostcall.h"
+#include "gfdm_rowtile.h"
 
 #include <algorithm>
 #include <climits>
@@ -25,6 +26,10 @@
 using gfdm::cf;
 using gfdm::RowPos;
 using gfdm::advance;
+using gfdm::RowCursor;
+using gfdm::StreamTiles;
+using gfdm::row_grid;
+using gfdm::store_elems;
 using gfdm::dist2;
 using gfdm::decide2;                 // gfdm_decide.h: shared with the link meter
 using gfdm::api_fail;
@@ -41,6 +46,7 @@ constexpr int kMaxTiles = 8192;                      // workgroups per launch; t
 constexpr int kDecodeSyms = 8 * kLanes;              // decode: a tile is kLanes * k bytes = 2048 symbols' worth of bits
 constexpr int kDecodeSlots = kDecodeSyms + 16;       // ... + 2 (rows begin on a byte) + 2 (vectors begin on 16 bytes), rounded up
 constexpr int kSoftSlots = 4 * kTileVec + 8 * 8;     // floats: (4096 / k + 2 + 2) symbols of k LLRs
+static_assert(4 * kTileVec - 1 <= gfdm::kMaxRowReach, "RowCursor::at: map steps over a tile's 2 kTileVec symbols, soft over those behind its 4 kTileVec LLRs");
 
 struct MapperArgs {
     const cf* points;        // [1 << k] (device)
@@ -171,19 +177,16 @@ __global__ __launch_bounds__(kLanes) void k_symbols_soft(MapperArgs a, const cf*
     __shared__ float llr[kSoftSlots];
     load_points<K>(pts, a);
     const int64_t n_live = live_rows(a.count, a.n_rows);
-    const int64_t total = a.n_rows * a.n_sym * K, s_live = n_live * a.n_sym, live_f = s_live * K;
+    const int64_t s_live = n_live * a.n_sym, live_f = s_live * K;
     const int mis = (int)(((uintptr_t)in / sizeof(cf)) & 1);
-    const int omis = (int)(((uintptr_t)out / sizeof(float)) & 3);            // floats between the 16-byte boundary in front of `out` and `out`
-    const int64_t nvec = (total + omis + 3) / 4;
-    const int64_t ntiles = (nvec + kTileVec - 1) / kTileVec;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t w0 = tile * kTileVec, w1 = std::min(w0 + kTileVec, nvec);
-        const int64_t f_lo = std::max(4 * w0 - omis, (int64_t)0), f_hi = std::min(4 * w1 - omis, total);
-        const int64_t f_live = std::min(f_hi, live_f);                       // the floats [f_lo, f_live) hold LLRs
+    const StreamTiles tl(out, 4, a.n_rows * a.n_sym * K, kTileVec);
+    for (int64_t tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
+        const auto t = tl.tile(tile);
+        const int64_t f_lo = t.i_lo, f_live = std::min(t.i_hi, live_f);      // the floats [f_lo, f_live) hold LLRs
         int64_t s_base = 0;
         if (f_live > f_lo) {
             const int64_t s_lo = f_lo / K, s_hi = (f_live - 1) / K + 1;      // <= s_live
-            const int64_t r0 = s_lo / a.n_sym, i0 = s_lo - r0 * a.n_sym;
+            const RowCursor first(s_lo, a.n_sym);
             const int64_t v_lo = (s_lo + mis) >> 1, v_end = (s_hi + mis + 1) >> 1;
             s_base = 2 * v_lo - mis;
             for (int64_t v = v_lo + threadIdx.x; v < v_end; v += kLanes) {
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(kLanes) void k_symbols_soft(MapperArgs a, const cf*
                     const int64_t s = 2 * v - mis + e;
                     const int slot = (int)(s - s_base) * K;
                     if (s < s_lo || s >= s_hi || slot + K > kSoftSlots) continue;
-                    const float sc = a.scale ? a.scale[advance(r0, i0, (uint32_t)(s - s_lo), a.n_sym).r] : 1.f;
+                    const float sc = a.scale ? a.scale[first.at((uint32_t)(s - s_lo)).r] : 1.f;
                     float m0[K], m1[K];
                     soft_minima<K>(x[e], pts, m0, m1);
 #pragma unroll
@@ -205,22 +208,16 @@ __global__ __launch_bounds__(kLanes) void k_symbols_soft(MapperArgs a, const cf*
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < kTileVec / kLanes; ++u) {
-            const int64_t w = w0 + u * kLanes + threadIdx.x;
-            if (w >= w1) continue;
-            const int64_t f0 = 4 * w - omis;
-            float y[4];
+            const int64_t w = t.v0 + u * kLanes + threadIdx.x;
+            if (w >= t.v1) continue;
+            const int64_t f0 = tl.first(w);
+            uint32_t y[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int64_t f = f0 + e;
-                y[e] = (f >= f_lo && f < f_live) ? llr[(int)(f - s_base * K)] : 0.f;
+                y[e] = (f >= f_lo && f < f_live) ? __float_as_uint(llr[(int)(f - s_base * K)]) : 0u;
             }
-            if (f0 >= 0 && f0 + 4 <= total) {        // a whole vector: 16-byte aligned by construction
-                *reinterpret_cast<float4*>(out + f0) = make_float4(y[0], y[1], y[2], y[3]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (f0 + e >= 0 && f0 + e < total) out[f0 + e] = y[e];
-            }
+            store_elems<float, 4>(out, tl, f0, y);
         }
         __syncthreads();                             // llr is rewritten for the next tile
     }
@@ -233,42 +230,34 @@ __global__ __launch_bounds__(kLanes) void k_symbols_map(MapperArgs a, const unsi
     for (int i = threadIdx.x; i < (1 << K); i += kLanes) pts[i] = reinterpret_cast<const uint2*>(a.points)[i];
     __syncthreads();
     const int64_t n_live = live_rows(a.count, a.n_rows);
-    const int64_t total = a.n_rows * a.n_sym, s_live = n_live * a.n_sym;
-    const int mis = (int)(((uintptr_t)out / sizeof(cf)) & 1);
-    const int64_t nvec = (total + mis + 1) / 2;
-    const int64_t ntiles = (nvec + kTileVec - 1) / kTileVec;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t w0 = tile * kTileVec, w1 = std::min(w0 + kTileVec, nvec);
-        const int64_t s_lo = std::max(2 * w0 - mis, (int64_t)0);
-        const int64_t r0 = s_lo / a.n_sym, i0 = s_lo - r0 * a.n_sym;
-        uint2 y[kTileVec / kLanes][2];               // all loads of a lane's vectors before its stores, so that their latencies overlap
+    const int64_t s_live = n_live * a.n_sym;
+    const StreamTiles tl(out, 2, a.n_rows * a.n_sym, kTileVec);
+    for (int64_t tile = blockIdx.x; tile < tl.ntiles; tile += gridDim.x) {
+        const auto t = tl.tile(tile);
+        const RowCursor first(t.i_lo, a.n_sym);
+        uint32_t y[kTileVec / kLanes][4];            // all loads of a lane's vectors before its stores, so that their latencies overlap
 #pragma unroll
         for (int u = 0; u < kTileVec / kLanes; ++u) {
-            const int64_t w = w0 + u * kLanes + threadIdx.x;
+            const int64_t w = t.v0 + u * kLanes + threadIdx.x;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                const int64_t s = 2 * w - mis + e;
-                y[u][e] = make_uint2(0u, 0u);
-                if (w >= w1 || s < 0 || s >= s_live) continue;
-                const RowPos pos = advance(r0, i0, (uint32_t)(s - s_lo), a.n_sym);
+                const int64_t s = tl.first(w) + e;
+                y[u][2 * e] = y[u][2 * e + 1] = 0u;
+                if (w >= t.v1 || s < 0 || s >= s_live) continue;
+                const RowCursor pos = first.at((uint32_t)(s - t.i_lo));
                 const int64_t q = pos.i * K, at = pos.r * a.row_bytes + (q >> 3);
                 const int sh = (int)(q & 7);
                 unsigned bits = (unsigned)in[at] << 8;
                 if (sh + K > 8) bits |= in[at + 1];  // the symbol's own bits reach into that byte: it is inside the row
-                y[u][e] = pts[(bits >> (16 - sh - K)) & ((1u << K) - 1u)];
+                const uint2 p = pts[(bits >> (16 - sh - K)) & ((1u << K) - 1u)];
+                y[u][2 * e] = p.x;
+                y[u][2 * e + 1] = p.y;
             }
         }
 #pragma unroll
         for (int u = 0; u < kTileVec / kLanes; ++u) {
-            const int64_t w = w0 + u * kLanes + threadIdx.x;
-            if (w >= w1) continue;
-            const int64_t s = 2 * w - mis;
-            if (s >= 0 && s + 2 <= total) {          // a whole vector: 16-byte aligned by construction
-                *reinterpret_cast<uint4*>(out + s) = make_uint4(y[u][0].x, y[u][0].y, y[u][1].x, y[u][1].y);
-            } else {
-                if (s >= 0 && s < total) *reinterpret_cast<uint2*>(out + s) = y[u][0];
-                if (s + 1 >= 0 && s + 1 < total) *reinterpret_cast<uint2*>(out + s + 1) = y[u][1];
-            }
+            const int64_t w = t.v0 + u * kLanes + threadIdx.x;
+            if (w < t.v1) store_elems<uint2, 2>(reinterpret_cast<uint2*>(out), tl, tl.first(w), y[u]);
         }
     }
 }
@@ -303,20 +292,19 @@ namespace {
 
 enum Op { OP_MAP, OP_DECODE, OP_SOFT };
 
-unsigned grid_for(int64_t ntiles) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, kMaxTiles)); }
-
 template <int K>
 void launch_k(const gfdm_hip_symbol_mapper* h, Op op, const MapperArgs& a, void* out, const void* in, hipStream_t s)
 {
     const dim3 block(kLanes);
     if (op == OP_MAP) {
-        const int64_t ntiles = ((a.n_rows * a.n_sym + 1) / 2 + 1 + kTileVec - 1) / kTileVec;            // + 1: an unaligned `out` adds a vector
-        hipLaunchKernelGGL(k_symbols_map<K>, dim3(grid_for(ntiles)), block, 0, s, a, static_cast<const unsigned char*>(in), static_cast<cf*>(out));
+        const dim3 grid(row_grid(out, 2, a.n_rows * a.n_sym, kTileVec, kMaxTiles));
+        hipLaunchKernelGGL(k_symbols_map<K>, grid, block, 0, s, a, static_cast<const unsigned char*>(in), static_cast<cf*>(out));
     } else if (op == OP_SOFT) {
-        const int64_t ntiles = ((a.n_rows * a.n_sym * K + 3) / 4 + 1 + kTileVec - 1) / kTileVec;
-        hipLaunchKernelGGL(k_symbols_soft<K>, dim3(grid_for(ntiles)), block, 0, s, a, static_cast<const cf*>(in), static_cast<float*>(out));
+        const dim3 grid(row_grid(out, 4, a.n_rows * a.n_sym * K, kTileVec, kMaxTiles));
+        hipLaunchKernelGGL(k_symbols_soft<K>, grid, block, 0, s, a, static_cast<const cf*>(in), static_cast<float*>(out));
     } else {
-        const dim3 grid(grid_for((a.n_rows * a.row_bytes + kLanes * K - 1) / (kLanes * K)));
+        const int64_t ntiles = (a.n_rows * a.row_bytes + kLanes * K - 1) / (kLanes * K);
+        const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, kMaxTiles)));
         const cf* x = static_cast<const cf*>(in);
         unsigned char* y = static_cast<unsigned char*>(out);
         gfdm::with_rule<K>(h->c.rule, [&](auto k, auto rule) {

@@ -166,6 +166,9 @@ def test_rows_per_call(n_rows, n_info):
         data = V.random_info(rng, n_rows, n_info)
         got = _h(cc.encode(_t(data), n_info))
         assert np.array_equal(got, V.encode(data, n_info, V.POLYS, mode))
+        out = Window(got.shape, np.uint8, 5)                 # the many rows are more than a tile's 4096 coded bytes: a tile seam in an unaligned output
+        cc.encode(_t(data), n_info, out=out.view)
+        assert np.array_equal(out.result(), V.encode(data, n_info, V.POLYS, mode)), "encode at byte 5"
         check_decode(cc, noisy_llr(rng, data, n_info, V.POLYS, mode), n_info, 16.0, V.POLYS, mode, "%d rows" % n_rows)
         pm = Window(n_rows, np.int32, 1)
         bad = flip(rng, got, V.coded_bits(n_info, mode), 2)

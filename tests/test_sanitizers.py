@@ -7,7 +7,8 @@ host function that copies in -> out) and driven by tests/sanitize/host_fuzz.cc: 
 while calls are in flight, every runtime call failing once, the process ending with builds in flight.  Recipe: tests/sanitize/Makefile.
 The staged host call of csrc/gfdm_hostcall.h (gfdm::HostCall: the *_host entry points of the device modules, whose kernels share a file with their
 host code and so cannot be compiled against the loop-back layer) has a small driver of its own, tests/sanitize/hostcall_check.cc, under ASan + UBSan.
-The tile geometry and the LDS bounds of the stream stages (csrc/gfdm_streamtile.h, host half) are brute-forced by tests/sanitize/streamtile_check.cc, likewise.
+The tile geometry and the LDS bounds of the stream stages (csrc/gfdm_streamtile.h, host half) are brute-forced by tests/sanitize/streamtile_check.cc, likewise,
+and the tile geometry, the grid and the row cursor of the row stages (csrc/gfdm_rowtile.h, host half) by tests/sanitize/rowtile_check.cc.
 
 Findings of the first runs (fixed in the product): a stale sticky hipGetLastError() of an earlier failed call failing the next launch, hipEvents leaked when
 their creation failed half way, a device operand with an unmapped tail bounced on the CPU instead of refused.
@@ -91,6 +92,16 @@ def test_stream_tile_geometry_holds_by_brute_force_under_address_and_ub_sanitize
     subprocess.run(["make", "-C", SAN, "-j4", "streamtile", "OUT=" + str(out)], check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     rc, text = run_hostcall(os.path.join(str(out), "streamtile_check_asan"), tmp_path)
     assert rc == 0 and "streamtile check OK" in text and "Sanitizer" not in text and "runtime error" not in text, text[-6000:]
+
+
+def test_row_tile_geometry_holds_by_brute_force_under_address_and_ub_sanitizer(tmp_path):
+    """The host half of csrc/gfdm_rowtile.h, which the kernels and the enqueue functions of the five row stages share, driven by
+    tests/sanitize/rowtile_check.cc: the tiles partition the output for the stages' four vector shapes at every alignment, the whole-vector
+    predicate is exact, row_grid is the number of tiles the bytes touch (capped), and the row cursor agrees with plain / and %."""
+    out = tmp_path / "build"
+    subprocess.run(["make", "-C", SAN, "-j4", "rowtile", "OUT=" + str(out)], check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    rc, text = run_hostcall(os.path.join(str(out), "rowtile_check_asan"), tmp_path)
+    assert rc == 0 and "rowtile check OK" in text and "Sanitizer" not in text and "runtime error" not in text, text[-6000:]
 
 
 def mutated_package(tmp_path, path, old, new):
