@@ -1,5 +1,5 @@
-// Internal: the tile skeleton of the stream stages -- k_shaper_place, k_channel, k_resample, k_fade -- ONE definition of what they share, so
-// that the four cannot drift ("Stream stages").  Never seen by hiprtc (not in JIT_HDRS).
+// Internal: the tile skeleton of the stream stages -- k_shaper_place, k_channel, k_resample, k_fade, k_amplify -- ONE definition of what they
+// share, so that the five cannot drift ("Stream stages").  Never seen by hiprtc (not in JIT_HDRS).
 //
 // A stage tiles its OUTPUT: the stream is cut into 16-byte vectors aligned in memory (VPS = 2 complex64 or 4 sc16 samples), a workgroup takes
 // tile_vec of them and strides over the tiles beyond the grid.  Per tile

@@ -167,6 +167,16 @@ def _signatures():
     fn("fading_model_check", i32, i32, i32, i32, i64, i64, i64, f64)
     call("fading_model_apply", vp, vp, i64, i64, i64, sc16=(f64,))
 
+    # ---- amplifier model: the kind's parameters or a coefficient table at create, the channel model's call without an offset ----
+    fn("amplifier_model_create", i32, out(vp), i32, vp, i32, vp, i32, i32, f64, i32)
+    getters("amplifier_model", "destroy kind n_params n_delays n_orders")
+    fn("amplifier_model_params", i32, vp, vp)
+    fn("amplifier_model_coefficients", i32, vp, vp)
+    fn("amplifier_model_drive", i32, vp, out(f64))
+    fn("amplifier_model_set_drive", i32, vp, f64)
+    fn("amplifier_model_check", i32, i32, vp, i32, i32, i32, f64, i64, i64, f64)
+    call("amplifier_model_apply", vp, vp, i64, i64, sc16=(f64,))
+
     # ---- symbol mapper and link meter ----
     for kind in ("symbol_mapper", "link_meter"):
         fn(kind + "_create", i32, out(vp), vp, i32, i32, i32)

@@ -1097,16 +1097,18 @@ def awgn_noise_voltage(signal, snr_db, rate=1.0):
 
 
 def _apply_stream(kernel, stem, x, history, offset, sc16, gain, out, stream):
-    """what ChannelModel.apply and FadingModel.apply share: <stem>[_sc16] on the history + n complex64 samples of x, n samples out"""
+    """what ChannelModel.apply, FadingModel.apply and AmplifierModel.apply share: <stem>[_sc16] on the history + n complex64 samples of x,
+    n samples out; offset None: the call takes none"""
     x = ops.operand(x, C64, "x", kernel._dev, floating=True)
     ops.check_result(out, x, I16 if sc16 else C64, kernel._dev, as_what="x")
-    history, offset = int(history), int(offset)
+    history = int(history)
     size = ops.size(x)
     if history < 0 or history > size:
         raise ValueError("history(%d) must lie in 0 .. the size of x(%d)" % (history, size))
     n = size - history
     res = ops.stream_result(x, n, sc16, kernel._dev, out, "x")
-    kernel._run(stem + ("_sc16" if sc16 else ""), x, (ops.ptr(res), ops.ptr(x) + 8 * history, n, history, offset) + ((float(gain),) if sc16 else ()), stream)
+    where = () if offset is None else (int(offset),)
+    kernel._run(stem + ("_sc16" if sc16 else ""), x, (ops.ptr(res), ops.ptr(x) + 8 * history, n, history) + where + ((float(gain),) if sc16 else ()), stream)
     return res
 
 
@@ -1322,6 +1324,157 @@ class FadingModel(_Kernel):
         if not sc16 and float(gain) != 1.0:
             raise ValueError("gain scales sc16 output: pass an int16 out or sc16=True (complex64 output is not scaled)")
         return _apply_stream(self, "gfdm_hip_fading_model_apply", x, history, offset, sc16, gain, out, stream)
+
+
+AMPLIFIER_KINDS = {"clip": 0, "rapp": 1, "saleh": 2, "poly": 3}
+_AMPLIFIER_PARAMS = {"clip": ("A",), "rapp": ("g", "A", "p"), "saleh": ("aa", "ba", "ap", "bp"), "poly": ()}
+
+
+def _amplifier_spec(kind, params, c):
+    """(kind name, float64 params as the handle keeps them (rounded to float32), complex64 c (Q, K) or None), checked as far as numpy can"""
+    name = {v: k for k, v in AMPLIFIER_KINDS.items()}.get(kind, kind)
+    if name not in AMPLIFIER_KINDS:
+        raise ValueError("kind must be one of %s" % ", ".join(sorted(AMPLIFIER_KINDS)))
+    p = np.asarray(params, dtype=np.float64).ravel()
+    if p.size != len(_AMPLIFIER_PARAMS[name]):
+        raise ValueError("kind %s takes the parameters (%s), got %d" % (name, ", ".join(_AMPLIFIER_PARAMS[name]), p.size))
+    with np.errstate(over="ignore"):
+        p = p.astype(np.float32).astype(np.float64)
+    if name != "poly":
+        if c is not None:
+            raise ValueError("kind %s takes no coefficients" % name)
+        return name, p, None
+    c = np.asarray(c)
+    if c.ndim == 1:
+        c = c[None, :]                                   # one delay: the memoryless polynomial
+    if c.ndim != 2:
+        raise ValueError("c must have the shape (n_delays, n_orders)")
+    return name, p, _c64(c).reshape(c.shape)
+
+
+def amplifier_curve(model_or_params, amplitudes):
+    """(am, pm): the output amplitude and the phase shift in radians of a kind for the input amplitudes |u| (behind the drive), float64
+    arrays of amplitudes' shape; numpy alone, no device.  model_or_params: an AmplifierModel, or (kind, *params) with kind "clip" (A),
+    "rapp" (g, A, p), "saleh" (aa, ba, ap, bp) or ("poly", c) -- for a memory polynomial the curve of a constant envelope, where every
+    delay sees the same sample."""
+    if isinstance(model_or_params, AmplifierModel):
+        name, p, c = model_or_params.kind(), model_or_params.params(), model_or_params.coefficients()
+    else:
+        kind, rest = model_or_params[0], tuple(model_or_params[1:])
+        name, p, c = _amplifier_spec(kind, () if kind in ("poly", 3) else rest, rest[0] if kind in ("poly", 3) and rest else None)
+    a = np.asarray(amplitudes, dtype=np.float64)
+    r = a * a
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        if name == "clip":
+            y = np.minimum(a, p[0]) + 0j
+        elif name == "rapp":
+            t = p[0] ** 2 * r / p[1] ** 2
+            low = p[0] * a * (1.0 + np.minimum(t, 1.0) ** p[2]) ** (-0.5 / p[2])
+            high = p[1] * (1.0 + np.maximum(t, 1.0) ** -p[2]) ** (-0.5 / p[2])
+            y = np.where(t <= 1.0, low, high) + 0j
+        elif name == "saleh":
+            y = a * p[0] / (1.0 + p[1] * r) * np.exp(1j * p[2] * r / (1.0 + p[3] * r))
+        else:
+            c = c.astype(np.complex128)
+            y = sum(c[:, k].sum() * a * r ** k for k in range(c.shape[1]))
+    return np.abs(y), np.angle(y)
+
+
+def amplifier_drive(mean_power, backoff_db, A=1.0):
+    """AmplifierModel's drive d that puts mean |d x|^2 backoff_db below A^2, for a stream of mean power mean_power (SpectrumMeter.power then
+    mean_power() supplies it): A sqrt(10^(-backoff_db / 10) / mean_power)"""
+    mean_power, A = float(mean_power), float(A)
+    if not (np.isfinite(mean_power) and mean_power > 0.0):
+        raise ValueError("mean_power must be finite and > 0")
+    if not (np.isfinite(A) and A > 0.0):
+        raise ValueError("A must be finite and > 0")
+    return float(A * np.sqrt(10.0 ** (-float(backoff_db) / 10.0) / mean_power))
+
+
+class AmplifierModel(_Kernel):
+    """The transmitter's power amplifier on a stream, on the device (contract in include/gfdm_hip.h, gfdm_hip_amplifier_model), between
+    BurstShaper.place (or Resampler.resample) and FadingModel.apply / ChannelModel.apply.  With u = drive * x and r = |u|^2:
+    clip(A): u where r <= A^2, else u A / |u|;  rapp(g, A, p): g u (1 + (g^2 r / A^2)^p)^(-1 / (2 p));  saleh(aa, ba, ap, bp): u aa / (1 +
+    ba r) exp(j ap r / (1 + bp r));  poly(c): y[i] = sum_q sum_k c[q][k] u[i - q] r[i - q]^k, c complex of shape (n_delays <= 16, n_orders
+    <= 5), the odd orders 1, 3, ...  The kind and its parameters (kept as float32) are fixed; drive has a setter that is read when a call is
+    enqueued, and a captured graph keeps the value it was captured with."""
+    _destroy = "gfdm_hip_amplifier_model_destroy"
+
+    def __init__(self, kind, params=(), c=None, drive=1.0, device=None):
+        name, p, c = _amplifier_spec(kind, params, c)
+        Q, K = (0, 0) if c is None else c.shape
+        h = ctypes.c_void_p()
+        dev = 0 if device is None else int(device)
+        _check(lib().gfdm_hip_amplifier_model_create(ctypes.byref(h), AMPLIFIER_KINDS[name], p.ctypes.data if p.size else None, p.size,
+                                                     None if c is None else c.ctypes.data, Q, K, float(drive), dev))
+        self._h = h
+        self._dev = dev
+
+    @classmethod
+    def clip(cls, A, drive=1.0, device=None):
+        return cls("clip", (A,), drive=drive, device=device)
+
+    @classmethod
+    def rapp(cls, g, A, p, drive=1.0, device=None):
+        return cls("rapp", (g, A, p), drive=drive, device=device)
+
+    @classmethod
+    def saleh(cls, aa, ba, ap, bp, drive=1.0, device=None):
+        return cls("saleh", (aa, ba, ap, bp), drive=drive, device=device)
+
+    @classmethod
+    def poly(cls, c, drive=1.0, device=None):
+        return cls("poly", (), c, drive=drive, device=device)
+
+    def kind(self):
+        """'clip' | 'rapp' | 'saleh' | 'poly'"""
+        return {v: k for k, v in AMPLIFIER_KINDS.items()}[lib().gfdm_hip_amplifier_model_kind(self._h)]
+
+    def params(self):
+        """the kind's parameters as the handle keeps them: float64 values of the float32 roundings"""
+        p = np.empty(lib().gfdm_hip_amplifier_model_n_params(self._h), np.float64)
+        _check(lib().gfdm_hip_amplifier_model_params(self._h, p.ctypes.data))
+        return p
+
+    def n_delays(self):
+        return lib().gfdm_hip_amplifier_model_n_delays(self._h)
+
+    def n_orders(self):
+        return lib().gfdm_hip_amplifier_model_n_orders(self._h)
+
+    def coefficients(self):
+        """c as given at create (complex64 (n_delays, n_orders), bit for bit); None for a kind without"""
+        if self.kind() != "poly":
+            return None
+        c = np.empty((self.n_delays(), self.n_orders()), np.complex64)
+        _check(lib().gfdm_hip_amplifier_model_coefficients(self._h, c.ctypes.data))
+        return c
+
+    @property
+    def drive(self):
+        v = ctypes.c_double()
+        _check(lib().gfdm_hip_amplifier_model_drive(self._h, ctypes.byref(v)))
+        return v.value
+
+    @drive.setter
+    def drive(self, drive):
+        _check(lib().gfdm_hip_amplifier_model_set_drive(self._h, float(drive)))
+
+    def set_drive(self, drive):
+        self.drive = drive
+
+    def apply(self, x, history=0, out=None, sc16=None, gain=1.0, stream=None):
+        """x holds history + n samples, the result has n: sample i of the result is the amplifier's output for x[history + i]; the first
+        `history` samples are the memory polynomial's past (what lies before them is zeros; the memoryless kinds read none of it).  A
+        stream cut into calls gives the samples of one call, to the bit, when each piece passes history = min(n_delays - 1, samples before
+        it).  numpy x -> numpy result (host path); a torch complex64 device tensor -> a tensor on its device (device path, current stream
+        unless given).  An int16 `out` (or sc16=True) selects int16 I/Q of shape (n, 2), truncated and saturated, of y * gain."""
+        if sc16 is None:
+            sc16 = out is not None and str(getattr(out, "dtype", "")).replace("torch.", "") == "int16"
+        sc16 = bool(sc16)
+        if not sc16 and float(gain) != 1.0:
+            raise ValueError("gain scales sc16 output: pass an int16 out or sc16=True (complex64 output is not scaled)")
+        return _apply_stream(self, "gfdm_hip_amplifier_model_apply", x, history, None, sc16, gain, out, stream)
 
 
 def resampler_step(x):

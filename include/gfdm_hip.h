@@ -979,6 +979,78 @@ int gfdm_hip_fading_model_apply_sc16_host(gfdm_hip_fading_model* m, int16_t* out
 int gfdm_hip_fading_model_apply_sc16_device(gfdm_hip_fading_model* m, void* out, const void* in, int64_t n, int64_t history, int64_t offset,
                                             double gain, void* stream);
 
+/* ---- gfdm_hip_amplifier_model: the transmitter's power amplifier on a stream, complex64 or sc16 out ---------------------------------
+ * The stage between the burst shaper (or the resampler) and the fading / channel model: place -> [resample] -> amplify -> [fade] ->
+ * apply.  Four kinds, fixed at create; drive is host state with a setter, read when a call is enqueued (a back-off sweep needs one
+ * handle; a captured graph keeps the value it was captured with).  Nothing depends on the absolute sample index: there is no offset.
+ * With d = (float)drive, for 0 <= i < n:
+ *     x[j] = in[j] for -history <= j < n,  0 for j < -history
+ *     u[j] = d * x[j] (the fp32 product of each component),  r[j] = |u[j]|^2
+ *   kind    params            y[i]
+ *   CLIP    A                 u where r <= A^2, bit for bit; else u * A / sqrt(r)
+ *   RAPP    g, A, p           g u (1 + t^p)^(-1 / (2 p)),  t = g^2 r / A^2
+ *   SALEH   aa, ba, ap, bp    u * aa / (1 + ba r) * exp(j ap r / (1 + bp r))
+ *   POLY    none              sum_{q < Q} sum_{k < K} c[q][k] u[i - q] r[i - q]^k      (the odd orders 1, 3, .. 2 K - 1)
+ * params are doubles that create rounds to fp32: the formulas hold for the rounded values, and the getter returns those.  POLY takes
+ *   Q = n_delays, K = n_orders and 2 Q K floats (re, im of c[q][k], k fastest) instead; the other kinds take n_delays = n_orders = 0.
+ * Arithmetic: fp32 without contraction, every fused multiply-add written out, correctly rounded division and sqrtf, the accurate powf
+ *   and sincosf.  r = fma(u.re, u.re, u.im * u.im).  CLIP compares r with fl32(A^2), s = A / sqrt(r), y = u * s.  RAPP: t = fl32(g^2 /
+ *   A^2) * r; where t <= 1, s = g * powf(1 + powf(t, p), -h) with h = fl32(1 / (2 p)); else s = (A / sqrt(r)) * powf(1 + powf(t, -p), -h)
+ *   -- the same curve from its saturated end, which holds for every finite r where t^p would overflow; y = u * s.  SALEH: am = aa /
+ *   fma(ba, r, 1), phi = (ap * r) / fma(bp, r, 1), sincosf(phi), y = (u * am) times the phasor, one complex product.  POLY: q ascending;
+ *   per delay G = c[q][K - 1], then G = fma(G, r, c[q][k]) for k = K - 2 .. 0, then y += G * u by fma (re: G.re u.re, then -G.im u.im;
+ *   im: G.re u.im, then G.im u.re), starting from y = 0; where every coefficient has imaginary part 0 the products with it are left out.
+ *   A sample is a pure function of its 1 (POLY: Q) input samples: a stream cut into calls at any point (each piece passing history =
+ *   min(Q - 1, samples before it)), or written to an `out` of another alignment, gives the same bits.
+ * A non-finite input sample spoils its own output sample (POLY: the Q outputs that read it) and nothing else.
+ * sc16 twin: interleaved int16 q(y.re * gain), q(y.im * gain), the products in fp32, q the burst shaper's rule.
+ * Error budget against the same formulas in float64 on the same complex64 inputs (u the exact product d * x there):
+ *     CLIP, RAPP   |y - y64| <= 8 * 2^-23 * |y64|          SALEH   |y - y64| <= 16 * 2^-23 * |y64|  while |phi| <= pi
+ *     POLY         |y - y64| <= (4 K + Q + 8) * 2^-23 * S_i,  S_i = sum_q sum_k |c[q][k]| |u[i - q]|^(2 k + 1)
+ *   (RAPP: the outer root 1 / (2 p) cancels the p-fold amplification of t's error.  POLY: the roundings of Horner, of r, of the product
+ *   and of the sum over q.)  Derived, not measured.
+ * *_device: in and out are device arrays with the alignment of one element and no more (8 bytes, sc16 out 4 bytes); byte offsets are
+ *   64-bit.  out overlapping [in - history, in + n) is GFDM_HIP_EINVAL for every kind: there is no in-place call.  No workspace, no
+ *   allocation, no synchronisation: one kernel, hipGraph-capturable.  The stream is written in 16-byte stores aligned in memory whatever
+ *   the alignment of out is, the first and last samples of an unaligned stream one by one; the memoryless kinds read 16 bytes a load
+ *   where `in` is aligned under an output vector and 8 where it is not, POLY reads every input sample once per tile of 2048 output
+ *   samples (plus the Q - 1 in front of the tile).  At most 2048 workgroups per launch, which stride over the tiles beyond.
+ * *_host: a convenience, not a pipeline: uploads history + n samples, runs the device call, downloads n.
+ * GFDM_HIP_EINVAL from check (the argument table alone, without a handle or a device), from create, set_drive and every call: kind
+ *   outside the enum; n_params other than 1 / 3 / 4 / 0 for the kind; a param that is not finite in fp32; A <= 0, g <= 0, p outside
+ *   0.5 .. 16, fl32(g^2 / A^2) zero or not finite, ba < 0, bp < 0; n_delays outside 1 .. 16 or n_orders outside 1 .. 5 (POLY), either non-zero (the others); a NULL or
+ *   non-finite coefficient table (create); drive negative or not finite in fp32; a non-finite gain; n or history negative; n > 2^62; a
+ *   byte size (8 (history + n)) that overflows int64.  Also: a NULL buffer that the call would touch.  n == 0 returns GFDM_HIP_OK
+ *   without a launch.
+ * Not here: AM/PM for Rapp, even orders and cross terms (the generalised memory polynomial), sc16 input, setters other than drive,
+ *   digital predistortion, fusing into place or apply.
+ * Tested range and measured shares of the budgets: tests/amplifier_model_ref.py, profiles/r23/amplifier_accuracy.json. */
+typedef enum gfdm_hip_amplifier_kind {
+    GFDM_HIP_AMPLIFIER_CLIP = 0,
+    GFDM_HIP_AMPLIFIER_RAPP = 1,
+    GFDM_HIP_AMPLIFIER_SALEH = 2,
+    GFDM_HIP_AMPLIFIER_POLY = 3
+} gfdm_hip_amplifier_kind;
+typedef struct gfdm_hip_amplifier_model gfdm_hip_amplifier_model;
+int gfdm_hip_amplifier_model_create(gfdm_hip_amplifier_model** out, int kind, const double* params, int n_params, const float* coefficients,
+                                    int n_delays, int n_orders, double drive, int device);
+int gfdm_hip_amplifier_model_destroy(gfdm_hip_amplifier_model* m);
+int gfdm_hip_amplifier_model_kind(const gfdm_hip_amplifier_model* m);
+int gfdm_hip_amplifier_model_n_params(const gfdm_hip_amplifier_model* m);
+int gfdm_hip_amplifier_model_n_delays(const gfdm_hip_amplifier_model* m);
+int gfdm_hip_amplifier_model_n_orders(const gfdm_hip_amplifier_model* m);
+int gfdm_hip_amplifier_model_params(const gfdm_hip_amplifier_model* m, double* params);               /* n_params */
+int gfdm_hip_amplifier_model_coefficients(const gfdm_hip_amplifier_model* m, float* coefficients);     /* 2 * n_delays * n_orders */
+int gfdm_hip_amplifier_model_drive(const gfdm_hip_amplifier_model* m, double* drive);
+int gfdm_hip_amplifier_model_set_drive(gfdm_hip_amplifier_model* m, double drive);
+int gfdm_hip_amplifier_model_check(int kind, const double* params, int n_params, int n_delays, int n_orders, double drive, int64_t n,
+                                   int64_t history, double gain);
+int gfdm_hip_amplifier_model_apply_host(gfdm_hip_amplifier_model* m, float* out, const float* in, int64_t n, int64_t history);
+int gfdm_hip_amplifier_model_apply_device(gfdm_hip_amplifier_model* m, void* out, const void* in, int64_t n, int64_t history, void* stream);
+int gfdm_hip_amplifier_model_apply_sc16_host(gfdm_hip_amplifier_model* m, int16_t* out, const float* in, int64_t n, int64_t history, double gain);
+int gfdm_hip_amplifier_model_apply_sc16_device(gfdm_hip_amplifier_model* m, void* out, const void* in, int64_t n, int64_t history, double gain,
+                                               void* stream);
+
 /* ---- gfdm_hip_link_meter: which burst a detection is, bit errors and error-vector power per row, counters on the device ------------
  * Behind the receivers and beside the symbol mapper's decode: what a BER or EVM curve point needs so that it is one fixed-shape,
  * hipGraph-capturable sequence of launches with one 96-byte read at the end.  Rows are bursts or frames as for the symbol mapper.
